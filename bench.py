@@ -4,6 +4,7 @@
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+  python bench.py ... --dump-outputs DIR   (also: the last timed step's groups and per-worker rows as DIR/*.npy)
 
 One step = one full-swarm match from a cold group state through the C ABI: compat sweep (W x C) -> greedy
 proximity carve -> solo merge -> T x W pair sweep + claim -> published assignment table, tables resident in HBM
@@ -54,12 +55,52 @@ FP64_VECTOR_TFLOPS = 78.6               # half the FP32 vector rate (157.3 TFLOP
 FLOP_PER_KEY = 9.0                      # chord form of the Haversine term: 3 subtractions, 1 multiply, 2 fma, 1 scale
 VALU_OPS_PER_KEY = 45.0                 # proposer hot loop, counted in the gfx950 ISA: ~40 VALU instructions per
                                         # 64-key stride (LDS reads aside) + the amortised insertions, per lane = per key
-HIP_HW_QUEUES = "16"                    # hardware queues asked of the HIP runtime (GPU_MAX_HW_QUEUES; its default is 4)
 LDS_ROUND_TRIP_CYC, CLOCK_GHZ = 50.0, 2.4   # MI355X_MICROARCH.md: ds_read issue->use ~50 cycles
 
 
 def med(stats, k):
     return statistics.median(s[k] for s in stats)
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(eng, W: int, out_dir: str) -> dict:
+    """What a caller of the timed path receives after its last step, as DIR/<name>.npy (float64, which holds every u32
+    exactly; PM_NONE and "no group" are -1; the u64 group ids are split into their 32-bit halves): the group list of
+    pm_get_groups and every worker's row of the published table (pm_lookup_task_for_worker).  At the BASELINE sizes
+    (W <= 100k) this is a few MB; the 64 MB cap is checked, not sampled."""
+    from protocol_amd.engine import PM_NONE
+    gow, groups, members = eng.get_groups()
+    rows = [eng.lookup(w) for w in range(W)]
+
+    def col(values):
+        a = np.asarray(values, dtype=np.float64)
+        a[a == PM_NONE] = -1.0
+        return a
+
+    ids = groups["id"].astype(np.uint64)
+    arrays = {
+        "group_of_worker": gow.astype(np.float64),
+        "worker_task": col([r.task for r in rows]),
+        "worker_group_index": col([r.group_index for r in rows]),
+        "worker_group_size": col([r.group_size for r in rows]),
+        "worker_next_worker": col([r.next_worker for r in rows]),
+        "group_id_hi": (ids >> np.uint64(32)).astype(np.float64),
+        "group_id_lo": (ids & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "group_config": groups["config"].astype(np.float64),
+        "group_task": col(groups["task"]),
+        "group_n_members": groups["n_members"].astype(np.float64),
+        "group_member_begin": groups["member_begin"].astype(np.float64),
+        "group_members": members.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_CAP_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": total}
 
 
 def cpu_baseline(sw, budget_s: float = 25.0) -> dict:
@@ -569,16 +610,15 @@ def main() -> int:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the configs2 / churn / per_task sub-objects")
     ap.add_argument("--check", action="store_true", help="also verify the groups against the oracle (slow)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    # The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 unless the environment
-    # says otherwise) and runs two streams that share one in turn: with K engines (one stream each; two until round 5)
-    # in one process, K = 4 pools matched one behind the other in pairs (1.4x the one-pool rate; 3.4x with 8 or more
-    # queues — `pools_on_one_gpu`).  Read once, when the runtime starts: set before anything touches HIP.  One engine
-    # is indifferent to it (1.31 vs 1.32 ms per match).  Only the N = 1 line runs several engines in one process; the
-    # N > 1 ranks (one engine each, beside RCCL's own streams) keep the runtime's default, as they were measured.
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", HIP_HW_QUEUES)
+    # The HIP runtime's hardware-queue count (GPU_MAX_HW_QUEUES) is left as the environment sets it: the GPU may be shared,
+    # and one engine is indifferent to it (1.31 vs 1.32 ms per match).  Only `pools_on_one_gpu` (K engines in one process)
+    # depends on it, and it reports the value it ran under.
     import torch
     import torch.distributed as dist
 
@@ -645,6 +685,7 @@ def main() -> int:
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         elapsed = float(tmax[0].item())
         ranks_seen = int(round(float(t[1].item())))
+    dumped = dump_outputs(eng, sw.W, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     T, W = sw.T, sw.W
     value = world * float(T) * float(W) * args.steps / elapsed   # whole job: every rank matched its own pool K times
@@ -692,6 +733,8 @@ def main() -> int:
                      "chain": chain_model(carve["steps"], carve["ms"], kt["carve_propose_kernel"]["ms"])},
         "kernels": kt,
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if world > 1:
         out["ranks_seen"] = ranks_seen
         out["cpu_baseline"] = None

@@ -8,7 +8,10 @@ storage], every `ComputeRequirements::from_str(..)` its requirement string (thro
 POLARITY; `assert!(ComputeRequirements::from_str(..).is_err())` the parser's error vectors.  The fixture must hold exactly
 these triples, per test function, in the reference's order.  (Until round 5 this only looked for the strings.)
 
-The GPU box has no /root/reference: a container-only integrity check, not a run-time dependency.
+Where the reference is absent the structural part still runs: node_rs_reference_vectors.json, beside this file, holds what
+reference_vectors() parsed out of that module (data only: spec tuples, requirement strings, expected outcomes), and
+check_structure() compares the fixture with it.  `python check_kats_against_reference.py --write-snapshot` refreshes it
+from the reference; with the reference present, the test suite also checks that the snapshot is what a fresh parse gives.
 """
 import json
 import os
@@ -17,6 +20,7 @@ import sys
 
 REF = "/root/reference/crates/shared/src/models/node.rs"
 HERE = os.path.dirname(os.path.abspath(__file__))
+SNAPSHOT = os.path.join(HERE, "node_rs_reference_vectors.json")
 _STR = r"\"((?:[^\"\\]|\\.)*)\""
 
 
@@ -105,13 +109,22 @@ def _fn_of(kat_name):
     return re.match(r"\w+", kat_name).group(0)
 
 
-def main() -> int:
-    if not os.path.exists(REF):
-        print("reference not present; nothing to check")
-        return 0
-    src = open(REF).read()
-    kats = json.load(open(os.path.join(HERE, "node_rs_kats.json")))
-    ref = reference_vectors(src)
+def load_snapshot():
+    """the stored reference_vectors() of the reference's test module, in the same shape (vectors as lists)"""
+    return json.load(open(SNAPSHOT))["vectors"]
+
+
+def as_json(vectors):
+    """reference_vectors() with tuples as lists: what the snapshot stores, comparable with load_snapshot()"""
+    return json.loads(json.dumps(vectors))
+
+
+def check_structure(ref, kats=None):
+    """the fixture's meets triples and parser-error vectors against the reference's (`ref`: reference_vectors() or the
+    snapshot) -> (vectors checked, mismatches, meets triples of the reference, is_err vectors of the reference)"""
+    if kats is None:
+        kats = json.load(open(os.path.join(HERE, "node_rs_kats.json")))
+    ref = {f: [tuple(v) for v in vs] for f, vs in ref.items()}
     bad = n = 0
     # ---- meets: per test function the same (specs, requirement, expected) triples in the same order, nothing left over
     by_fn = {}
@@ -136,6 +149,18 @@ def main() -> int:
         if r not in fix_err:
             bad += 1
             print(f"[parser_errors] the reference's is_err() vector is missing from the fixture: {r!r}")
+    return n, bad, sum(len(v) for v in ref_meets.values()), len(ref_err)
+
+
+def main() -> int:
+    if not os.path.exists(REF):
+        print("reference not present; nothing to check")
+        return 0
+    src = open(REF).read()
+    kats = json.load(open(os.path.join(HERE, "node_rs_kats.json")))
+    ref = reference_vectors(src)
+    n, bad, n_meets, n_err = check_structure(ref, kats)
+    ref_meets = {f for f, vs in ref.items() if any(v[0] == "meets" for v in vs)}
     ref_ok = {v[1] for vs in ref.values() for v in vs if v[0] == "parse" and v[2] == "ok"}
     fixture_reqs = {k["req"] for k in kats["parser"]} | {k["req"] for k in kats["meets"]}
     for r in sorted(ref_ok - fixture_reqs):
@@ -162,11 +187,22 @@ def main() -> int:
             if "$" in k["in"] and f'"{k["in"]}"' not in src2 and k["in"] not in src2:
                 print(f"[{sec}] {k['name']}: template not found verbatim: {k['in']!r}")
                 bad += 1
-    n_meets = sum(len(v) for v in ref_meets.values())
     print(f"checked {n} vectors ({n_meets} meets triples with their polarity parsed out of {len(ref_meets)} reference tests, "
-          f"{len(ref_err)} is_err vectors), {bad} mismatches")
+          f"{n_err} is_err vectors), {bad} mismatches")
     return 1 if bad else 0
 
 
+def write_snapshot() -> int:
+    if not os.path.exists(REF):
+        print("reference not present; the snapshot is left as it is")
+        return 1
+    with open(SNAPSHOT, "w") as f:
+        json.dump({"source": "reference_vectors() of crates/shared/src/models/node.rs (mod tests), written by "
+                             "tests/golden/check_kats_against_reference.py --write-snapshot",
+                   "vectors": as_json(reference_vectors(open(REF).read()))}, f, indent=1)
+        f.write("\n")
+    return 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(write_snapshot() if sys.argv[1:] == ["--write-snapshot"] else main())

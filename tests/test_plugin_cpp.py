@@ -48,6 +48,10 @@ def test_plugin_under_thread_sanitizer(tmp_path):
         pytest.skip("ThreadSanitizer does not link here: " + err[-300:])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 second_deadlock_stack=1 exitcode=66")
     out = _run(exe, env=env)
+    if "ThreadSanitizer: unexpected memory mapping" in out.stderr and shutil.which("setarch"):
+        # GCC 11's TSan runtime cannot lay out its shadow memory in a process the kernel randomised with more than 28 bits
+        # of mmap entropy: the same binary again, with address randomisation off for that one process
+        out = _run(shutil.which("setarch"), os.uname().machine, "-R", exe, env=env)
     assert "ThreadSanitizer" not in out.stderr, out.stderr[-4000:]
     assert out.returncode == 0, out.stdout + out.stderr
 

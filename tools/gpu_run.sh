@@ -6,7 +6,7 @@
 # Steps run in the order given; their logs go to gpurun_out/<out-subdir>/ and a short digest of each to stdout (what gpurun
 # shows).  A step is a word, or word:argument[:argument]:
 #
-#   suite[:q16][:<pytest args>]  pytest tests -m gpu -x (q16: under PM_TEST_HW_QUEUES=16)
+#   suite[:<pytest args>]    pytest tests -m gpu -x
 #   tests:<file>[,<file>]    the named test files only (tests/ is implied), e.g. tests:test_gpu_plugin_cxx.py
 #   bench[:<bench.py args>]  the default bench line -> bench.json (+ one-line digest)
 #   benchn:<N>[:<bench.py args>]  bench.py --gpus N as the driver launches it, but on ONE GPU: N ranks over gloo sharing device 0
@@ -45,8 +45,7 @@ for step in "$@"; do
   echo "##### [$n] $step"
   case $name in
     suite)
-      q=""; [ "${arg%%:*}" = "q16" ] && { q="PM_TEST_HW_QUEUES=16"; arg=${arg#q16}; arg=${arg#:}; }
-      env $q timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider -rfE -x $arg > "$out/${n}_suite.log" 2>&1
+      timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider -rfE -x $arg > "$out/${n}_suite.log" 2>&1
       echo "suite rc=$?" | tee -a "$out/${n}_suite.log"; tail -4 "$out/${n}_suite.log" ;;
     tests)
       files=$(echo "$arg" | tr ',' '\n' | sed 's#^#tests/#' | tr '\n' ' ')

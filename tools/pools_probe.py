@@ -3,10 +3,11 @@
 bench.py on its own (K Python threads calling pm_tick; pm_tick_many from one thread and with a thread per engine),
 printed as a table.  The runtime reads GPU_MAX_HW_QUEUES once, when it starts, so one process = one setting:
 
-    for q in 4 8 16 32; do python tools/pools_probe.py --queues $q; done
+    for q in default 2 1; do python tools/pools_probe.py --queues $q; done
 
-profiles/r04_pools_hw_queues.json is this for 4 / 8 / 16 / 32 (taken through bench.py itself).  Next:
-an engine that owns one stream instead of two, pm_tick_many in chunks of eight."""
+The probe never raises the count above 2 (the GPU may be shared); profiles/r04_pools_hw_queues.json holds the same legs
+under 4 / 8 / 16 / 32 (taken through bench.py itself).  Next: an engine that owns one stream instead
+of two, pm_tick_many in chunks of eight."""
 import argparse
 import json
 import os
@@ -18,7 +19,8 @@ sys.path.insert(0, ROOT)
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--queues", default="16", help="GPU_MAX_HW_QUEUES for this process ('default' = leave the runtime's 4)")
+    ap.add_argument("--queues", default="default", choices=["default", "1", "2"],
+                    help="GPU_MAX_HW_QUEUES for this process ('default' = leave it as the environment sets it)")
     ap.add_argument("--ks", default="2,4,8", help="pool counts for the Python-thread leg (pm_tick_many adds 16)")
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1)
