@@ -311,7 +311,11 @@ int32_t pm_get_groups(pm_engine*, int32_t* group_of_worker, pm_group* groups, ui
  * (Ok(None) in the reference) — PM_OK either way.  out->member_begin is 0; members (cap_members entries, BTreeSet order:
  * the position of a worker in it is get_idx_in_group, mod.rs:424-434) may be NULL; with a members buffer that is too small
  * the call returns PM_ERANGE after filling *out (out->n_members says what is needed).  Host-side state only: no HIP call,
- * but the engine's mutex (a tick in flight finishes first). */
+ * but the engine's mutex (a tick in flight finishes first).
+ * Between pm_dist_tick_begin and pm_dist_tick_end (a stepwise tick, which holds no lock between its phases) these two
+ * and pm_get_groups answer from the host list as it stands, without compacting it under the carve (dissolved
+ * entries are skipped; slots are numbered as pm_get_groups would number them): the groups the tick forms appear once
+ * its merge pass (pm_dist_match_begin) or pm_dist_tick_end has taken them in, and their tasks with pm_dist_tick_end. */
 int32_t pm_get_group_by_id(pm_engine*, uint64_t group_id, pm_group* out, uint32_t* members, uint32_t cap_members,
                            uint32_t* slot);
 int32_t pm_get_group_of_worker(pm_engine*, uint32_t worker, pm_group* out, uint32_t* members, uint32_t cap_members,

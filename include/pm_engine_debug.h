@@ -17,7 +17,12 @@ extern "C" {
 /* Counters of the last carve.  out[0..32) and out[56..88): s_memtime phase counters (all zero unless the library was
  * built with -DPM_CARVE_PROF: tools/stream_prof.py, tools/carve_prof.py); out[32..56): how the carve went — reasons
  * its launches ended, index geometry, streaming-carve tickets / timeouts / switches (protocol_amd/engine.py
- * debug_carve_counters names them).  Copies min(cap, 88) words (out[72..88): the row makers' anatomy, tools/stream_prof.py). */
+ * debug_carve_counters names them).  out[72..88): the row makers' anatomy, tools/stream_prof.py.  out[88..97): the
+ * incremental state a long-running engine keeps, not the last carve's (engine.py debug_task_space;
+ * tests/test_gpu_soak.py bounds it) — t_lo, t_cap (the task index space: the swept range is [t_lo, t_cap)), T (live
+ * tasks), t_dead (tombstones inside the range), regrowths and compactions of the index space since creation, entries
+ * of the host group list, its tombstones (dissolved, not yet compacted), retired snapshot buffers.  Copies
+ * min(cap, 97) words. */
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap);
 
 /* Timeline of the last streaming carve launch (PM_CARVE_PROF builds; otherwise *n = 0): up to cap events of two words

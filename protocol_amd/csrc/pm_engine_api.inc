@@ -149,30 +149,47 @@ static int32_t give_group(pm_engine* e, uint32_t slot, pm_group* out, uint32_t* 
   return PM_OK;
 }
 
+// A read between pm_dist_tick_begin and pm_dist_tick_end must not renumber the list: the carve in flight appends its groups
+// behind the slots the device holds (absorb_groups, from d_n_groups on, tombstones counted) and the claim's task words are
+// indexed by them.  Such a read takes nothing in and compacts nothing: it skips the tombstones, and reports the slot the
+// group would have in the compacted list (what pm_get_groups would number it).
+static uint32_t compacted_slot(const pm_engine* e, uint32_t g) {
+  uint32_t dead = 0;
+  for (uint32_t k = 0; k < g; ++k) dead += e->groups[k].dead;
+  return g - dead;
+}
+
 int32_t pm_get_group_by_id(pm_engine* e, uint64_t group_id, pm_group* out, uint32_t* members, uint32_t cap_members,
                            uint32_t* slot) {
   if (!e || !out || !slot) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
-  ABSORB_PENDING(e);
-  compact_groups(e);  // (slots are numbers of the compacted list, as in pm_get_groups)
+  const bool stepwise = e->dist_phase != 0;
+  if (!stepwise) {
+    ABSORB_PENDING(e);
+    compact_groups(e);  // (slots are numbers of the compacted list, as in pm_get_groups)
+  }
   std::memset(out, 0, sizeof(*out));
   out->task = PM_NONE;
-  *slot = slot_of_group_id(e, group_id);
-  if (*slot == PM_NONE) return PM_OK;
-  return give_group(e, *slot, out, members, cap_members);
+  const uint32_t g = slot_of_group_id(e, group_id);  // (skips tombstones)
+  *slot = g == PM_NONE || !stepwise ? g : compacted_slot(e, g);
+  if (g == PM_NONE) return PM_OK;
+  return give_group(e, g, out, members, cap_members);
 }
 
 int32_t pm_get_group_of_worker(pm_engine* e, uint32_t worker, pm_group* out, uint32_t* members, uint32_t cap_members,
                                uint32_t* slot) {
   if (!e || !out || !slot) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
-  ABSORB_PENDING(e);
-  compact_groups(e);
+  const bool stepwise = e->dist_phase != 0;
+  if (!stepwise) {
+    ABSORB_PENDING(e);
+    compact_groups(e);
+  }
   if (worker >= e->W) return set_error(PM_ERANGE, "worker index out of range");
   std::memset(out, 0, sizeof(*out));
   out->task = PM_NONE;
-  const int32_t g = e->h_group_of[worker];
-  *slot = g < 0 ? PM_NONE : uint32_t(g);
+  const int32_t g = e->h_group_of[worker];  // (a dissolved group's workers read -1: never a tombstone)
+  *slot = g < 0 ? PM_NONE : (stepwise ? compacted_slot(e, uint32_t(g)) : uint32_t(g));
   if (g < 0) return PM_OK;
   return give_group(e, uint32_t(g), out, members, cap_members);
 }
@@ -231,19 +248,31 @@ int32_t pm_get_groups(pm_engine* e, int32_t* group_of_worker, pm_group* groups, 
                       uint32_t* n_groups, uint32_t* members, uint32_t cap_members, uint32_t* n_members) {
   if (!e) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
-  ABSORB_PENDING(e);
-  compact_groups(e);
-  const uint32_t G = uint32_t(e->groups.size());
+  const bool stepwise = e->dist_phase != 0;  // (the list is not compacted under a stepwise tick: tombstones are skipped)
+  if (!stepwise) {
+    ABSORB_PENDING(e);
+    compact_groups(e);
+  }
+  const uint32_t G = uint32_t(e->groups.size() - (stepwise ? e->n_dead_groups : 0));
   uint32_t M = 0;
-  for (const Group& g : e->groups) M += uint32_t(g.members.size());
+  for (const Group& g : e->groups) M += g.dead ? 0u : uint32_t(g.members.size());
   if (n_groups) *n_groups = G;
   if (n_members) *n_members = M;
-  if (group_of_worker) std::copy(e->h_group_of.begin(), e->h_group_of.end(), group_of_worker);
+  if (group_of_worker) {
+    std::copy(e->h_group_of.begin(), e->h_group_of.end(), group_of_worker);
+    if (stepwise && e->n_dead_groups) {
+      std::vector<int32_t> to_slot(e->groups.size());
+      for (size_t g = 0, k = 0; g < e->groups.size(); ++g) to_slot[g] = int32_t(k), k += !e->groups[g].dead;
+      for (uint32_t w = 0; w < e->W; ++w)
+        if (group_of_worker[w] >= 0) group_of_worker[w] = to_slot[size_t(group_of_worker[w])];
+    }
+  }
   if (groups && cap_groups < G) return set_error(PM_ERANGE, "groups buffer too small");
   if (members && cap_members < M) return set_error(PM_ERANGE, "members buffer too small");
   uint32_t off = 0;
-  for (uint32_t g = 0; g < G; ++g) {
-    const Group& gr = e->groups[g];
+  for (uint32_t g = 0, src = 0; g < G; ++g, ++src) {
+    while (e->groups[src].dead) ++src;  // (none outside a stepwise tick: the list was compacted above)
+    const Group& gr = e->groups[src];
     if (groups) {
       groups[g].id = gr.id;
       groups[g].config = gr.cfg;

@@ -1,5 +1,5 @@
 // pm_engine_debug.inc — part of pm_engine.cpp (one translation unit; included in place): C ABI: test and measuring hooks of include/pm_engine_debug.h (inside extern "C").
-// debug (include/pm_engine_debug.h): counters of the last carve; copies min(cap, 72) words
+// debug (include/pm_engine_debug.h): counters of the last carve and of the engine's incremental state; copies min(cap, 97) words
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap) {
   if (!e || !out) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
@@ -7,6 +7,10 @@ int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap)
   std::memcpy(out, e->carve_prof, size_t(n) * sizeof(unsigned long long));
   for (uint32_t k = 32; k < cap && k < 56; ++k) out[k] = e->carve_why[k - 32];
   for (uint32_t k = 56; k < cap && k < 88; ++k) out[k] = e->carve_prof[k - 56 + 32];  // (phase counters 32..47)  // (how the validation launches ended; the index)
+  // (the incremental state a long-running engine keeps: the task index space, the group list, the snapshot buffers)
+  const unsigned long long inc[9] = {e->t_lo, e->t_cap, e->T, e->t_dead, e->t_regrowths, e->t_compactions,
+                                     e->groups.size(), e->n_dead_groups, e->pub_retired.size()};
+  for (uint32_t k = 88; k < cap && k < 97; ++k) out[k] = inc[k - 88];
   return PM_OK;
 }
 

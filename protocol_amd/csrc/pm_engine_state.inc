@@ -79,7 +79,10 @@ struct pm_engine {
   // claim); its position in the caller's current list — what the ABI reports — is the number of live tasks in
   // front of it (live bitmap + per-word prefix, on the device and lazily on the host).
   uint32_t T = 0;  // live tasks
+  // Tombstones are reclaimed: the index space is rebuilt from the live rows alone when it regrows, and when more than
+  // T + PM_TASK_DEAD_SLACK of them lie inside [t_lo, t_cap) (tasks_rebuild): the swept range stays within 2T + slack.
   uint32_t t_cap = 0, t_lo = 0, t_dead = 0;
+  uint32_t t_regrowths = 0, t_compactions = 0;  // rebuilds of the index space since creation (pm_debug_carve_prof words 88..96)
   bool have_tasks = false;
   std::vector<uint64_t> h_tmask, h_tuid, h_tlive;  // indexed by u (h_tlive: bitmap words)
   std::vector<int64_t> h_created;

@@ -30,35 +30,47 @@ static int32_t tasks_push_range(pm_engine* e, uint32_t u0, uint32_t u1) {
   return PM_OK;
 }
 
-// The table outgrew the room in front of it: a larger index space, the used part moves to its top.  Handles
-// shift by (new capacity - old capacity): the groups' claims are shifted with them.
-static int32_t tasks_grow(pm_engine* e, uint32_t cap) {
-  const uint32_t old_cap = e->t_cap, old_lo = e->t_lo, used = old_cap - old_lo, new_lo = cap - used;
-  const uint32_t shift = new_lo - old_lo;
-  std::vector<uint64_t> tmask(e->h_tmask.begin() + old_lo, e->h_tmask.end());
-  std::vector<int64_t> created(e->h_created.begin() + old_lo, e->h_created.end());
-  std::vector<uint64_t> tuid;
-  if (e->tasks_have_uid) tuid.assign(e->h_tuid.begin() + old_lo, e->h_tuid.end());
-  std::vector<uint64_t> live_old = e->h_tlive;
-  const uint32_t T = e->T, dead = e->t_dead;
+// Tombstones a rebuild leaves standing inside the swept range [t_lo, t_cap) beyond the live count: more than
+// T + PM_TASK_DEAD_SLACK of them and the next delta rebuilds the index space (tasks_rebuild).
+static constexpr uint32_t PM_TASK_DEAD_SLACK = 4096;
+
+// A fresh index space of capacity `cap` holding the LIVE rows only, in list order, at its top: the regrowth (the table
+// outgrew the room in front of it) and the compaction (too many tombstones in the swept range) both come here.  A
+// handle moves by the number of tombstones behind it, so the claims (Group::task) and uid_to_u go through a per-row
+// old -> new map.  Positions in the caller's list count live rows only: they do not change, and neither do the published
+// rows (pub_patch / pub_shift_tasks hold positions, not handles).
+static int32_t tasks_rebuild(pm_engine* e, uint32_t cap) {
+  const uint32_t old_cap = e->t_cap, old_lo = e->t_lo, T = e->T;
+  const uint32_t new_lo = cap - T;
+  std::vector<uint32_t> to_new(old_cap - old_lo, PM_NONE);  // handle - old_lo -> new handle (PM_NONE: a tombstone)
+  std::vector<uint64_t> tmask(T), tuid;
+  std::vector<int64_t> created(T);
+  if (e->tasks_have_uid) tuid.resize(T);
+  uint32_t k = 0;
+  for (uint32_t u = old_lo; u < old_cap; ++u)
+    if ((e->h_tlive[u >> 6] >> (u & 63u)) & 1ull) {
+      to_new[u - old_lo] = new_lo + k;
+      tmask[k] = e->h_tmask[u];
+      created[k] = e->h_created[u];
+      if (e->tasks_have_uid) tuid[k] = e->h_tuid[u];
+      ++k;
+    }
+  if (k != T) return set_error(PM_ESTATE, "task table: the live bitmap and the live count disagree");
   int32_t rc = tasks_alloc(e, cap);
   if (rc) return rc;
   std::copy(tmask.begin(), tmask.end(), e->h_tmask.begin() + new_lo);
   std::copy(created.begin(), created.end(), e->h_created.begin() + new_lo);
   if (e->tasks_have_uid) std::copy(tuid.begin(), tuid.end(), e->h_tuid.begin() + new_lo);
-  for (uint32_t u = old_lo; u < old_cap; ++u)
-    if ((live_old[u >> 6] >> (u & 63u)) & 1ull) {
-      const uint32_t v = u + shift;
-      e->h_tlive[v >> 6] |= 1ull << (v & 63u);
-    }
+  for (uint32_t u = new_lo; u < cap; ++u) e->h_tlive[u >> 6] |= 1ull << (u & 63u);
   e->t_lo = new_lo;
   e->T = T;
-  e->t_dead = dead;
-  for (Group& g : e->groups)
-    if (g.task != PM_NONE) g.task += shift;
-  e->groups_dirty = true, e->groups_delta_ok = false;
+  e->t_dead = 0;
+  auto remap = [&](uint32_t u) { return u >= old_lo && u < old_cap ? to_new[u - old_lo] : PM_NONE; };
+  for (Group& g : e->groups)  // (a standing group's task is live: a deleted task dissolves the groups that held it)
+    if (g.task != PM_NONE) g.task = remap(g.task);
+  e->groups_dirty = true, e->groups_delta_ok = false;  // the device's claims are handles: the list goes up whole
   if (e->uid_map_valid)
-    for (auto& kv : e->uid_to_u) kv.second += shift;
+    for (auto& kv : e->uid_to_u) kv.second = remap(kv.second);
   rc = tasks_push_range(e, new_lo, cap);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -207,8 +219,13 @@ static int32_t tasks_insert_front_locked(pm_engine* e, const pm_task_soa* t) {
   if (!e->T && !e->t_dead) e->tasks_have_uid = t->uid != nullptr;
   if (e->t_lo < n) {  // out of room in front: a larger index space, everything moves to its top
     if (e->tasks_have_uid && e->h_tuid.size() != e->t_cap) e->h_tuid.assign(e->t_cap, 0);
-    int32_t rc = tasks_grow(e, task_capacity_for(e->t_cap - e->t_lo + n));
+    int32_t rc = tasks_rebuild(e, task_capacity_for(e->T + n));
     if (rc) return rc;
+    e->t_regrowths++;
+  } else if (e->t_dead > e->T + PM_TASK_DEAD_SLACK) {  // room enough, but the swept range is mostly tombstones
+    int32_t rc = tasks_rebuild(e, e->t_cap);
+    if (rc) return rc;
+    e->t_compactions++;
   }
   if (e->tasks_have_uid && e->h_tuid.size() != e->t_cap) e->h_tuid.assign(e->t_cap, 0);
   const uint32_t lo = e->t_lo - n;
@@ -312,6 +329,11 @@ int32_t pm_tasks_delete(pm_engine* e, const uint64_t* uids, uint32_t n, uint32_t
   }
   e->tprefix_dirty = true;
   e->h_tprefix_valid = false;
+  if (e->t_dead > e->T + PM_TASK_DEAD_SLACK) {  // the swept range is mostly tombstones: the live rows alone, same capacity
+    int32_t rc = tasks_rebuild(e, e->t_cap);
+    if (rc) return rc;
+    e->t_compactions++;
+  }
   if (n_deleted) *n_deleted = uint32_t(slots.size());
   pub_patch(e, nullptr);  // a deleted task (and the group that held it) is gone, the tasks behind it move up
   return PM_OK;

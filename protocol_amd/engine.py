@@ -544,6 +544,17 @@ class Engine:
         check(L.pm_debug_delta_pushes(self._h, C.byref(n)))
         return n.value
 
+    def debug_task_space(self) -> dict:
+        """the task index space, the group list and the snapshot buffers (include/pm_engine_debug.h: pm_debug_carve_prof
+        words 88..96)"""
+        L = lib()
+        L.pm_debug_carve_prof.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint32]
+        L.pm_debug_carve_prof.restype = C.c_int32
+        out = (C.c_ulonglong * 97)()
+        check(L.pm_debug_carve_prof(self._h, out, 97))
+        keys = ("t_lo", "t_cap", "T", "t_dead", "regrowths", "compactions", "n_groups", "n_dead_groups", "retired_buffers")
+        return dict(zip(keys, (int(v) for v in out[88:97])))
+
     def debug_row_networks(self, keys, sites, n_per_wave: int, slot_bits: int, ulps: int, upto: int):
         """test hook (include/pm_engine_debug.h): rows from keys[n_waves * n_per_wave] by the insertion and by the sorting
         networks, compared on the device -> (mismatch bits, rows that differ, the networks' rows as u64[n_waves, 64])"""
