@@ -432,9 +432,10 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
   emit_group_webhooks();  // tombstoned nodes dissolved their groups
 }
 
-// scheduler_impl.rs:44-59: any None on the way => every configuration allowed
-uint64_t GpuMatchPlugin::topology_mask(const Task& t) const {
-  if (!t.allowed_topologies) return ~0ull;
+// scheduler_impl.rs:44-59: any None on the way => every configuration allowed (nullopt).  "Unrestricted" is not a
+// mask value: with 64 configurations a task that names all of them has mask ~0 too, and still enables all of them.
+std::optional<uint64_t> GpuMatchPlugin::topology_mask(const Task& t) const {
+  if (!t.allowed_topologies) return std::nullopt;
   uint64_t m = 0;
   for (const std::string& name : *t.allowed_topologies) {
     const auto it = std::find(config_names_.begin(), config_names_.end(), name);
@@ -443,13 +444,14 @@ uint64_t GpuMatchPlugin::topology_mask(const Task& t) const {
   return m;
 }
 
+// the engine's task mask: an unrestricted task selects every configuration
+uint64_t GpuMatchPlugin::engine_mask(const Task& t) const { return topology_mask(t).value_or(~0ull); }
+
 void GpuMatchPlugin::push_enabled(const std::vector<Task>& tasks) {
   // available_node_group_configs: every topology some task names (on_task_created, mod.rs:1224-1243)
   uint64_t enabled = 0;
-  for (const Task& t : tasks) {
-    const uint64_t m = topology_mask(t);
-    if (m != ~0ull) enabled |= m;
-  }
+  for (const Task& t : tasks)
+    if (const std::optional<uint64_t> m = topology_mask(t)) enabled |= *m;
   check(pm_set_enabled_mask(engine_, enabled));
   enabled_mask_.store(enabled);
 }
@@ -463,7 +465,7 @@ void GpuMatchPlugin::sync_tasks_locked(std::vector<Task>& guard, std::vector<Tas
   std::vector<uint64_t> masks, uid;
   std::vector<int64_t> created;
   for (const Task& t : tasks) {
-    masks.push_back(topology_mask(t));
+    masks.push_back(engine_mask(t));
     created.push_back(t.created_at);
     uid.push_back(task_uid(t));
   }
@@ -484,7 +486,7 @@ void GpuMatchPlugin::sync_tasks(std::vector<Task> tasks) {
 }
 
 void GpuMatchPlugin::on_task_created(const Task& task, const std::function<std::vector<Task>()>& all_tasks) {
-  const uint64_t mask = topology_mask(task), uid = task_uid(task);
+  const uint64_t mask = engine_mask(task), uid = task_uid(task);
   const int64_t created = task.created_at;
   pm_task_soa soa{};
   soa.n = 1;

@@ -298,7 +298,8 @@ class GpuMatchPlugin : public SchedulerPlugin {
   void push_model_table(const NodeTable& nodes) const;
   static Row project(const OrchestratorNode& node, NodeTable& table, bool* new_model);
   static std::vector<uint32_t> address_ranks(const std::vector<uint32_t>& by_address, size_t known);
-  uint64_t topology_mask(const Task& t) const;
+  std::optional<uint64_t> topology_mask(const Task& t) const;
+  uint64_t engine_mask(const Task& t) const;
   void push_enabled(const std::vector<Task>& tasks);
   void sync_tasks_locked(std::vector<Task>& guard, std::vector<Task> tasks);
   void emit_group_webhooks();

@@ -283,6 +283,126 @@ def make_swarm(seed: int, n_tasks: int, n_workers: int, *, configs: str = "mixed
                  meta=dict(n_tasks=n_tasks, n_workers=n_workers, configs=configs, zipf=zipf))
 
 
+# ---- wide configuration tables: up to PM_MAX_CONFIGS (64) configurations over 70 GPU model classes
+
+# 58 synthetic models after the 12 real ones: 70 classes, so the model table has three 32-bit words and requirements
+# can select classes >= 32.  "zeta-kNN" (a requirement model) matches exactly class NN (the substring rule,
+# node.rs:463-484); each real class has a token that selects it (a100 / h100 select a few).
+WIDE_MODELS = GPU_MODELS + ["Zeta-K%02d Compute" % c for c in range(len(GPU_MODELS), 70)]
+WIDE_MEMORY_MB = GPU_MEMORY_MB + [16384 * (1 + c % 12) for c in range(len(GPU_MODELS), 70)]
+_REAL_TOKENS = ["h100", "a100", "a6000", "rtx4090", "h100 pcie", "a100-sxm4-40gb", "a100 80gb pcie", "rtx_3090", "l40s",
+                "h200", "v100", "mi300x"]
+WIDE_MAX_TOPO = 4   # topology names per task (the oracle's ORC_MAX_TOPO)
+
+
+def _model_req(cls: int) -> str:
+    return _REAL_TOKENS[cls] if cls < len(_REAL_TOKENS) else "zeta-k%02d" % cls
+
+
+def _gen_wide_configs(seed: int, C: int):
+    """C distinct configurations and, per configuration, the specs of a worker that meets it:
+    [(name, min, max, requirement | None)], [dict(gpu_count, model, mem, cores, ram, storage)]"""
+    s = lambda salt: Stream(seed, 5000 + salt)
+    kind = s(1).randint(C, 0, 7)
+    kind[np.arange(C) % 16 == 7] = 0                  # some configurations without a requirement
+    cnt = np.array([1, 2, 4, 8])[s(2).randint(C, 0, 3)]
+    cnt2 = np.array([1, 2, 4, 8])[s(3).randint(C, 0, 3)]
+    cls = s(4).randint(C, 0, len(WIDE_MODELS) - 1)
+    cls_hi = s(5).randint(C, 32, len(WIDE_MODELS) - 1)   # (a second alternative in the model table's second / third word)
+    mem_lo = np.array([16000, 24000, 40000, 80000])[s(6).randint(C, 0, 3)]
+    mem_hi = mem_lo + np.array([20000, 60000, 150000])[s(7).randint(C, 0, 2)]
+    cores = np.array([8, 16, 32, 64, 128])[s(8).randint(C, 0, 4)]
+    ram = s(9).randint(C, 16000, 1000000)
+    sto = s(10).randint(C, 100, 20000)
+    mn = s(11).randint(C, 1, 16)
+    mx = mn + (s(12).uniform(C) * (17 - mn)).astype(np.int64)
+    configs, witness = [], []
+    for i in range(C):
+        k, m1, m2 = int(kind[i]), _model_req(int(cls[i])), _model_req(int(cls_hi[i]))
+        w = dict(gpu_count=int(cnt[i]), model=int(cls[i]), mem=int(mem_lo[i]) + 1000, cores=256, ram=2000000,
+                 storage=30000)
+        req = [None,
+               f"gpu:count={cnt[i]}",
+               f"gpu:count={cnt[i]};gpu:model={m1}",
+               f"gpu:memory_mb_min={mem_lo[i]};gpu:memory_mb_max={mem_hi[i]}",
+               f"cpu:cores={cores[i]};ram_mb={ram[i]}",
+               f"storage_gb={sto[i]};gpu:model={m2},{m1}",
+               f"gpu:count={cnt[i]};gpu:model={m2};gpu:count={cnt2[i]};gpu:memory_mb_min={mem_lo[i]}",
+               f"gpu:total_memory_min={int(cnt[i]) * int(mem_lo[i])};cpu:cores={cores[i]}"][k]
+        if k in (5, 6):
+            w["model"] = int(cls_hi[i])
+        configs.append(("wide%02d-k%d" % (i, k), int(mn[i]), int(mx[i]), req))
+        witness.append(w)
+    return configs, witness
+
+
+def _gen_wide_tasks(seed: int, T: int, C: int, t0_ms: int = 1_754_000_000_000):
+    """Tasks over a pool of 2 C + 16 topology lists of 1..4 names: list p < C names configuration p, task i < C takes
+    list i (every configuration is named once T >= C); few distinct masks, so a reference can group tasks by mask."""
+    s = lambda salt: Stream(seed, 6000 + salt)
+    P = 2 * C + 16
+    pool = s(1).randint(P * WIDE_MAX_TOPO, 0, C - 1).reshape(P, WIDE_MAX_TOPO).astype(np.int16)
+    pool[:C, 0] = np.arange(C)
+    pool_n = (1 + s(2).choice(P, [0.5, 0.3, 0.15, 0.05])).astype(np.uint8)
+    pick = s(3).randint(T, 0, P - 1)
+    first = np.arange(min(T, C))
+    pick[first] = first
+    topo = pool[pick].copy()
+    n_topo = pool_n[pick].copy()
+    topo[n_topo[:, None] <= np.arange(WIDE_MAX_TOPO)[None, :]] = -2
+    kind = s(4).uniform(T)
+    kind[first] = 1.0
+    kind[C:C + 2] = [0.0, 0.025][:max(0, min(T - C, 2))]   # (with T >= C + 2: one unrestricted task, one ghost)
+    restricted = kind >= 0.02                          # 2 % unrestricted
+    ghost = (kind >= 0.02) & (kind < 0.03)             # 1 % name only a topology no configuration has
+    topo[ghost, 0] = -1
+    topo[ghost, 1:] = -2
+    n_topo = np.where(ghost, 1, n_topo)
+    n_topo = np.where(restricted, n_topo, 0).astype(np.uint8)
+    topo[~restricted] = -2
+    created = t0_ms + s(5).randint(T, 0, 86_400_000)
+    dupe = s(6).uniform(T) < 0.05                      # exact duplicates of created_at
+    created = np.where(dupe, created[s(7).randint(T, 0, max(T - 1, 0))], created).astype(np.int64)
+    uid = mix64(np.arange(T, dtype=np.uint64) ^ np.uint64((seed * 0x9E3779B1 + 17) & 0xFFFFFFFFFFFFFFFF))
+    order = np.argsort(-created, kind="stable")
+    return dict(created_at=created[order], task_uid=uid[order], restricted=restricted[order], n_topo=n_topo[order],
+                topo=topo[order])
+
+
+def wide_config_swarm(seed: int, n_tasks: int, n_workers: int, n_configs: int, n_models: int = 70) -> Swarm:
+    """A swarm with 1 <= n_configs <= 64 distinct configurations (gpu:count, gpu:model, memory bounds, cpu cores, ram,
+    storage, some without requirement; group sizes 1..16) over len(WIDE_MODELS) = 70 model classes.  With n_workers >=
+    n_configs every configuration has a worker that meets it (healthy, with p2p), and with n_tasks >= n_configs a task
+    that names it.  Tasks name at most 4 configurations (2 % unrestricted, 1 % a name no configuration has); topo has 4
+    columns.  make_swarm's output is untouched (the committed digests depend on it)."""
+    if not 1 <= n_configs <= 64:
+        raise ValueError(f"n_configs must be in 1..64, not {n_configs}")
+    if n_models != len(WIDE_MODELS):
+        raise ValueError(f"the wide swarm has {len(WIDE_MODELS)} model classes")
+    W, C = n_workers, n_configs
+    w = _gen_workers(seed, W, uniform_gpu=False)
+    model = Stream(seed, 40).randint(W, 0, n_models - 1).astype(np.uint32)
+    w["gpu_model_id"] = model
+    w["gpu_mem_mb"] = np.array(WIDE_MEMORY_MB, dtype=np.uint32)[model]
+    configs, witness = _gen_wide_configs(seed, C)
+    if W >= C:   # one witness per configuration, spread over the table
+        for i, spec in enumerate(witness):
+            r = i * W // C
+            for k in ("has_specs", "has_gpu", "gpu_count_some", "gpu_mem_some", "gpu_model_some", "has_cpu",
+                      "cpu_cores_some", "ram_some", "storage_some", "has_p2p"):
+                w[k][r] = True
+            w["status"][r] = ST_HEALTHY
+            w["gpu_count"][r] = spec["gpu_count"]
+            w["gpu_model_id"][r] = spec["model"]
+            w["gpu_mem_mb"][r] = spec["mem"]
+            w["cpu_cores"][r] = spec["cores"]
+            w["ram_mb"][r] = spec["ram"]
+            w["storage_gb"][r] = spec["storage"]
+    t = _gen_wide_tasks(seed, n_tasks, C)
+    return Swarm(seed=seed, model_names=list(WIDE_MODELS), configs=configs, **w, **t,
+                 meta=dict(n_tasks=n_tasks, n_workers=n_workers, configs="wide", n_configs=C))
+
+
 # The five BASELINE.json configurations.
 def baseline_config(i: int, seed: int = 1, scale: float = 1.0) -> Swarm:
     sz = lambda n: max(1, int(n * scale))

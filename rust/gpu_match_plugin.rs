@@ -624,16 +624,20 @@ impl GpuMatchPlugin {
         rank
     }
 
-    /// scheduler_impl.rs:44-59: any None on the way => every configuration allowed.
-    fn topology_mask(&self, t: &Task) -> u64 {
-        let Some(list) = t.scheduling_config.as_ref().and_then(|c| c.plugins.as_ref())
-            .and_then(|p| p.get("node_groups")).and_then(|n| n.get("allowed_topologies")) else { return u64::MAX };
-        list.iter().filter_map(|name| self.config_names.iter().position(|c| c == name)).fold(0, |m, i| m | (1u64 << i))
+    /// scheduler_impl.rs:44-59: any None on the way => every configuration allowed (None).  "Unrestricted" is not a
+    /// mask value: with 64 configurations a task that names all of them has mask u64::MAX too, and still enables them.
+    fn topology_mask(&self, t: &Task) -> Option<u64> {
+        let list = t.scheduling_config.as_ref().and_then(|c| c.plugins.as_ref())
+            .and_then(|p| p.get("node_groups")).and_then(|n| n.get("allowed_topologies"))?;
+        Some(list.iter().filter_map(|name| self.config_names.iter().position(|c| c == name)).fold(0, |m, i| m | (1u64 << i)))
     }
+
+    /// the engine's task mask: an unrestricted task selects every configuration
+    fn engine_mask(&self, t: &Task) -> u64 { self.topology_mask(t).unwrap_or(u64::MAX) }
 
     fn push_enabled(&self, tasks: &[Task]) -> Result<()> {
         // available_node_group_configs: every topology some task names (on_task_created, mod.rs:1224-1243)
-        let enabled = tasks.iter().map(|t| self.topology_mask(t)).filter(|m| *m != u64::MAX).fold(0u64, |a, m| a | m);
+        let enabled = tasks.iter().filter_map(|t| self.topology_mask(t)).fold(0u64, |a, m| a | m);
         check(unsafe { pm_set_enabled_mask(self.engine, enabled) })?;
         self.enabled_mask.store(enabled, Ordering::Release);
         Ok(())
@@ -648,7 +652,7 @@ impl GpuMatchPlugin {
 
     /// the snapshot upload with `tasks` already locked for writing
     fn sync_tasks_locked(&self, guard: &mut Vec<Task>, tasks: Vec<Task>) -> Result<()> {
-        let masks: Vec<u64> = tasks.iter().map(|t| self.topology_mask(t)).collect();
+        let masks: Vec<u64> = tasks.iter().map(|t| self.engine_mask(t)).collect();
         let created: Vec<i64> = tasks.iter().map(|t| t.created_at).collect();
         let uid: Vec<u64> = tasks.iter().map(task_uid).collect();
         let soa = pm_task_soa { n: tasks.len() as u32, topo_mask: masks.as_ptr(), created_at: created.as_ptr(), uid: uid.as_ptr() };
@@ -668,7 +672,7 @@ impl GpuMatchPlugin {
     /// TaskStore observer (task_store.rs:46-52 -> on_task_created, mod.rs:1224-1243): the new task is the newest, so
     /// it goes in front; only this row travels to the GPU.  Equal or older timestamps fall back to the snapshot.
     pub fn on_task_created(&self, task: &Task, all_tasks: impl FnOnce() -> Vec<Task>) -> Result<()> {
-        let (mask, created, uid) = (self.topology_mask(task), task.created_at, task_uid(task));
+        let (mask, created, uid) = (self.engine_mask(task), task.created_at, task_uid(task));
         let soa = pm_task_soa { n: 1, topo_mask: &mask, created_at: &created, uid: &uid };
         let mut tasks = self.tasks.write();                 // (before the engine call: see LOCK ORDER)
         let rc = if self.republish_on_insert { unsafe { pm_tasks_insert_front_ex(self.engine, &soa, 1) } }

@@ -401,6 +401,39 @@ static void task_observers_follow_deltas() {
   for (int k = 0; k < 5; ++k) CHECK_EQ(served(k), std::string("task-5"));   // they hold task-5: a group keeps its task
 }
 
+// available_node_group_configs at PM_MAX_CONFIGS: a restricted task that names all 64 configurations has mask ~0, the
+// mask an unrestricted task has too; the first enables every configuration (on_task_created, mod.rs:1224-1243), the
+// second none.
+static void sixty_four_configs_enabled_mask() {
+  std::vector<NodeGroupConfiguration> cfgs;
+  std::vector<std::string> names;
+  for (int i = 0; i < 64; ++i) {
+    names.push_back("c" + std::to_string(i));
+    cfgs.push_back(NodeGroupConfiguration{names.back(), 1, 1, std::nullopt});
+  }
+  GpuMatchPlugin p(cfgs, 0, nullptr, {});
+  p.sync_nodes({node(0), node(1)});
+  const Task t_open = task(1, 100, std::nullopt), t_all = task(2, 90, names);
+  const Task t_top = task(3, 80, std::vector<std::string>{"c63"});
+  pm_mock_reset_calls();
+  p.sync_tasks({t_open});
+  CHECK_EQ(calls_named("set_enabled_mask").back(), std::string("set_enabled_mask 0"));
+  pm_mock_reset_calls();
+  p.sync_tasks({t_open, t_all});
+  CHECK_EQ(calls_named("set_enabled_mask").back(), std::string("set_enabled_mask 18446744073709551615"));
+  pm_mock_reset_calls();
+  p.on_task_deleted(t_all);
+  CHECK_EQ(calls_named("set_enabled_mask").back(), std::string("set_enabled_mask 0"));
+  pm_mock_reset_calls();
+  p.on_task_created(t_top, [&] { return std::vector<Task>{t_open, t_top}; });   // (older: the snapshot goes up)
+  CHECK_EQ(calls_named("set_enabled_mask").back(), std::string("set_enabled_mask 9223372036854775808"));
+  pm_mock_reset_calls();
+  const Task t_all_new = task(4, 200, names);
+  p.on_task_created(t_all_new, [&] { return std::vector<Task>{t_all_new, t_open, t_top}; });
+  CHECK(starts_with(calls()[0], "tasks_insert_front n=1"));
+  CHECK_EQ(calls_named("set_enabled_mask").back(), std::string("set_enabled_mask 18446744073709551615"));
+}
+
 static void status_changes() {
   auto rec = std::make_shared<Recorder>();
   GpuMatchPlugin p(two_configs(), 0, nullptr, {rec});
@@ -910,6 +943,7 @@ int main(int argc, char** argv) {
       {"tick_lookup_templating_and_webhooks", tick_lookup_templating_and_webhooks},
       {"task_observers_follow_deltas", task_observers_follow_deltas},
       {"status_changes", status_changes},
+      {"sixty_four_configs_enabled_mask", sixty_four_configs_enabled_mask},
       {"pools_tick_in_one_call", pools_tick_in_one_call},
       {"scheduler_returns_the_stores_task", scheduler_returns_the_stores_task},
       {"scheduler_replaces_task_and_node_variables", scheduler_replaces_task_and_node_variables},

@@ -32,7 +32,6 @@ def main(lib_path: str, seeds=(3, 4, 5)) -> int:
     L.pm_mock_calls.restype = C.c_char_p
     L.pm_mock_reset_calls.restype = None
 
-    ALL = 0xFFFFFFFFFFFFFFFF
     W_store = 160
     rng = np.random.default_rng(11)
 
@@ -44,12 +43,14 @@ def main(lib_path: str, seeds=(3, 4, 5)) -> int:
         r = np.random.default_rng(seed)
         trace = []
         masks, created, uid = sw.task_masks(), sw.created_at.copy(), sw.task_uid.copy()
-        cur = [(int(m), int(c), int(u)) for m, c, u in zip(masks, created, uid)]
+        cur = [(int(m), int(c), int(u), bool(rs)) for m, c, u, rs in zip(masks, created, uid, sw.restricted)]
 
         def enabled():
+            """every configuration a RESTRICTED task names: an unrestricted task enables nothing, and a restricted one
+            that names all 64 configurations (mask ALL as well) enables all of them"""
             e = 0
-            for m, _c, _u in cur:
-                if m != ALL:
+            for m, _c, _u, restricted in cur:
+                if restricted:
                     e |= m
             return e
 
@@ -105,7 +106,7 @@ def main(lib_path: str, seeds=(3, 4, 5)) -> int:
         for k in range(3):
             src = int(r.integers(0, len(masks)))
             t_max += 1
-            new = (int(masks[src]), t_max, (1 << 40) + k)
+            new = (int(masks[src]), t_max, (1 << 40) + k, bool(sw.restricted[src]))
             cur.insert(0, new)
             shim.on_task_created(new[0], new[1], new[2], enabled())
             step(f"on_task_created {k}", present[:20])
