@@ -41,7 +41,9 @@ extern "C" {
                             carve_next / carve_validate pair became pm_dist_carve_wait; pm_upload_workers(keep_groups = 1)
                             accepts new rows behind the known ones; + pm_host_to_lowercase (the model rule is Unicode now); carve_variant 2 / 4
                             are PM_EINVAL (since round 5); pm_stats of a pm_tick / pm_tick_many: ms_publish is 0 (the claim publishes),
-                            ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only */
+                            ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only;
+                            + pm_adopt_groups / pm_group_id_state (restart and switch-over): compatible additions, the version
+                            stays 3 */
 
 enum {
   PM_OK = 0,
@@ -320,6 +322,28 @@ int32_t pm_get_group_by_id(pm_engine*, uint64_t group_id, pm_group* out, uint32_
                            uint32_t* slot);
 int32_t pm_get_group_of_worker(pm_engine*, uint32_t worker, pm_group* out, uint32_t* members, uint32_t cap_members,
                                uint32_t* slot);
+
+/* Restart and switch-over: install the groups a store already holds (node_group:<id> + group_task:<id>,
+ * node_groups/mod.rs:25-28) into an engine that holds none — what pm_get_groups returns, pm_adopt_groups takes.
+ * Preconditions (PM_ESTATE otherwise): configurations and workers uploaded; no live group; no stepwise tick in progress
+ * (dist_phase != 0); no carve records waiting to be absorbed; tasks uploaded if some group names a task.
+ * Validation is all or nothing — PM_EINVAL, pm_last_error naming the group's index and the rule, and the engine exactly as
+ * it was (no groups, the id stream unchanged) — per group:
+ *   config < n_cfgs;  1 <= n_members <= max_group_size of that configuration;  member_begin + n_members <= n_members (of
+ *   the call);  every member < W;  no worker twice (in one group or in two);  no id another group's;  task < T or PM_NONE.
+ * Accepted as they are, like the reference, which reads such groups back and never re-checks them: a configuration that is
+ * disabled or that the members no longer meet; a size below min_group_size; dead or unhealthy members (dissolved only by a
+ * later status change, status_update_impl.rs:8-39); a claimed task whose topologies do not include the configuration.
+ * After success the groups hold slots 0..n-1 in the given order (their creation order), each claimed task is bound by its
+ * identity (uid, or position without uids) like any claim, the published table reads "no group" until the next
+ * pm_match / pm_tick publishes, the device mirror goes up whole before the next kernel that reads it, and the id stream's
+ * state is id_state (ids need not come from the stream: any u64 is an id).  Nothing goes into the life-cycle feed (the
+ * reference sends no webhook when it reads groups back). */
+int32_t pm_adopt_groups(pm_engine*, const pm_group* groups, uint32_t n_groups, const uint32_t* members, uint32_t n_members,
+                        uint64_t id_state);
+/* The state of the group id stream (the next pm_form_groups / merge draws from it: splitmix64), for handing over to a
+ * successor's pm_adopt_groups.  PM_ESTATE inside a stepwise tick. */
+int32_t pm_group_id_state(pm_engine*, uint64_t* state);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

@@ -275,6 +275,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_workers.inc"
 #include "pm_engine_tasks.inc"
 #include "pm_engine_api.inc"
+#include "pm_engine_adopt.inc"
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

@@ -9,6 +9,18 @@ static int32_t upload(DevBuf<T>& d, const T* src, size_t n, hipStream_t s) {
   return PM_OK;
 }
 
+// every row of the published table reads "no group, no task" until the next publish
+static void pub_clear(pm_engine* e) {
+  const int cur = e->pub_cur.load(std::memory_order_relaxed);
+  if (cur < 0) return;
+  PubTable& t = e->pub[cur];
+  const uint64_t s0 = t.seq.load(std::memory_order_relaxed);
+  t.seq.store(s0 + 1, std::memory_order_relaxed);
+  std::atomic_thread_fence(std::memory_order_release);
+  t.cleared.store(1u, std::memory_order_relaxed);
+  t.seq.store(s0 + 2, std::memory_order_release);
+}
+
 static void reset_groups_locked(pm_engine* e) {
   e->groups.clear();
   e->n_dead_groups = 0;
@@ -20,15 +32,7 @@ static void reset_groups_locked(pm_engine* e) {
   // name other groups): a heartbeat before the next publish is told "no group", and pub_patch resolves nothing
   // against the new list.
   e->groups_epoch++;
-  const int cur = e->pub_cur.load(std::memory_order_relaxed);
-  if (cur >= 0) {
-    PubTable& t = e->pub[cur];
-    const uint64_t s0 = t.seq.load(std::memory_order_relaxed);
-    t.seq.store(s0 + 1, std::memory_order_relaxed);
-    std::atomic_thread_fence(std::memory_order_release);
-    t.cleared.store(1u, std::memory_order_relaxed);
-    t.seq.store(s0 + 2, std::memory_order_release);
-  }
+  pub_clear(e);
 }
 
 // dissolve_group (mod.rs:1423-1487).  A status storm dissolves hundreds of groups per tick; removing each from

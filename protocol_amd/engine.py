@@ -99,6 +99,7 @@ EXPORTS = [
     "pm_append_workers", "pm_set_addr_ranks", "pm_tasks_insert_front", "pm_tasks_insert_front_ex", "pm_tasks_delete", "pm_set_stream", "pm_set_carve_workgroups", "pm_tick_many", "pm_dist_configure", "pm_dist_tick_begin", "pm_dist_carve_wait",
     "pm_dist_match_begin", "pm_dist_tick_end", "pm_match_per_task_device",
     "pm_dissolve_group_by_id", "pm_get_group_by_id", "pm_get_group_of_worker", "pm_host_to_lowercase",
+    "pm_adopt_groups", "pm_group_id_state",
 ]
 
 _lib = None
@@ -162,6 +163,8 @@ def lib() -> C.CDLL:
         L.pm_dissolve_group_by_id.argtypes = [vp, u64, C.POINTER(u32)]
         L.pm_get_group_by_id.argtypes = [vp, u64, vp, vp, u32, C.POINTER(u32)]
         L.pm_get_group_of_worker.argtypes = [vp, u32, vp, vp, u32, C.POINTER(u32)]
+        L.pm_adopt_groups.argtypes = [vp, vp, u32, vp, u32, u64]
+        L.pm_group_id_state.argtypes = [vp, C.POINTER(u64)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -407,6 +410,20 @@ class Engine:
 
     def reset_groups(self):
         check(lib().pm_reset_groups(self._h))
+
+    def adopt_groups(self, groups, members, id_state: int):
+        """pm_adopt_groups: install a group list into an engine that holds none -- `groups` (group_dt records) and `members`
+        exactly as get_groups() returns them, `id_state` as group_id_state() returned it"""
+        g = np.ascontiguousarray(groups, dtype=group_dt)
+        m = _arr(members, np.uint32)
+        check(lib().pm_adopt_groups(self._h, g.ctypes.data if len(g) else None, len(g), m.ctypes.data if len(m) else None,
+                                    len(m), int(id_state) & 0xFFFFFFFFFFFFFFFF))
+
+    def group_id_state(self) -> int:
+        """the state of the group id stream (splitmix64), for a successor's adopt_groups"""
+        s = C.c_uint64(0)
+        check(lib().pm_group_id_state(self._h, C.byref(s)))
+        return s.value
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

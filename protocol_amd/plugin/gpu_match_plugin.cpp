@@ -1,6 +1,7 @@
 // gpu_match_plugin.cpp — see gpu_match_plugin.hpp.  Statement for statement the sequence of rust/gpu_match_plugin.rs
 // over the C ABI (include/pm_engine.h); comments name the Rust function or the reference lines a block follows.
 #include "gpu_match_plugin.hpp"
+#include "group_id_text.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -22,28 +23,6 @@ std::string replace_all(std::string s, const std::string& from, const std::strin
     at += to.size();
   }
   return s;
-}
-
-std::string hex_lower(uint64_t v) {  // format!("{:x}", v): generate_group_id, mod.rs:1489-1493
-  char buf[24];
-  std::snprintf(buf, sizeof(buf), "%llx", (unsigned long long)v);
-  return buf;
-}
-
-// the inverse of format!("{:x}", u64): lower-case hex digits, no sign, no prefix, no leading zero (but "0"), <= 16 of them.
-// Anything else is the text of no group id (a Redis key that does not exist in the reference).
-bool parse_group_id(const std::string& s, uint64_t* out) {
-  if (s.empty() || s.size() > 16 || (s.size() > 1 && s[0] == '0')) return false;
-  uint64_t v = 0;
-  for (char c : s) {
-    uint64_t d;
-    if (c >= '0' && c <= '9') d = uint64_t(c - '0');
-    else if (c >= 'a' && c <= 'f') d = uint64_t(c - 'a' + 10);
-    else return false;
-    v = (v << 4) | d;
-  }
-  *out = v;
-  return true;
 }
 
 // the two-call convention of the pm_host_* string helpers: size, then fill
@@ -378,6 +357,7 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
         check(pm_on_worker_status_many(engine_, gone.data(), gone_flags.data(), dead.data(), uint32_t(gone.size())));
       }
       engine_rows_stale_ = false;
+      nodes_synced_.store(true);
       lk.unlock();
       emit_group_webhooks();
       return;
@@ -428,6 +408,7 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
       check(pm_set_addr_ranks(engine_, ranks.data(), uint32_t(ranks.size())));
     }
     engine_rows_stale_ = false;
+    nodes_synced_.store(true);
   }
   emit_group_webhooks();  // tombstoned nodes dissolved their groups
 }
@@ -478,6 +459,7 @@ void GpuMatchPlugin::sync_tasks_locked(std::vector<Task>& guard, std::vector<Tas
   check(pm_upload_tasks(engine_, &soa));
   push_enabled(tasks);
   guard = std::move(tasks);
+  tasks_synced_.store(true);
 }
 
 void GpuMatchPlugin::sync_tasks(std::vector<Task> tasks) {
@@ -522,6 +504,7 @@ void GpuMatchPlugin::on_task_deleted(const Task& task) {
 }
 
 pm_stats GpuMatchPlugin::tick() {
+  ticked_.store(true);
   pm_stats s{};
   check(pm_tick(engine_, &s));
   emit_group_webhooks();
@@ -530,7 +513,7 @@ pm_stats GpuMatchPlugin::tick() {
 
 std::vector<pm_stats> GpuMatchPlugin::tick_many(const std::vector<GpuMatchPlugin*>& pools) {
   std::vector<pm_engine*> engines;
-  for (GpuMatchPlugin* p : pools) engines.push_back(p->engine_);
+  for (GpuMatchPlugin* p : pools) engines.push_back(p->engine_), p->ticked_.store(true);
   std::vector<pm_stats> stats(pools.size());
   if (pools.empty()) return stats;
   pools[0]->check(pm_tick_many(engines.data(), uint32_t(engines.size()), stats.data(), 0));
@@ -562,6 +545,7 @@ uint32_t shard_of(const Address& a, uint32_t world) {
 pm_stats GpuMatchPlugin::tick_dist(AllGather& comm) {
   const uint32_t rank = comm.rank(), world = comm.world();
   if (world == 0 || rank >= world) throw std::invalid_argument("tick_dist: rank outside the communicator");
+  ticked_.store(true);
   {
     std::shared_lock<std::shared_mutex> lk(nodes_mu_);
     if (dist_stream_ != comm.stream()) {

@@ -256,6 +256,29 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // dissolve_group (mod.rs:1002-1004 -> :1423-1487): by id text; an unknown id is not an error; sends the webhook
   void dissolve_group(const std::string& group_id);
 
+  // ---- restart and switch-over (INTEGRATION.md "Restart and switch-over"; gpu_match_restore.cpp).
+  struct RestoreReport {
+    std::vector<std::pair<std::string, std::string>> dropped;  // (group id text, reason)
+    std::vector<std::string> task_cleared;                     // group_task:<id> naming no known task
+  };
+  // The groups a store holds (orchestrator:groups_index / node_group:<id> in get_all_groups order, group_task:<id>) into the
+  // engine: after sync_nodes and sync_tasks, before the first tick — EngineError(PM_ESTATE) at any other time.  A group is
+  // dropped (and reported, not thrown) when its id is not the "{:x}" text of a u64, its configuration name is unknown, a node
+  // address is not in the node table, a node is in an earlier group, it has no nodes, more than max_group_size nodes, or the
+  // id of an earlier group.  A group_task naming an unknown task leaves the group without one (get_current_group_task,
+  // mod.rs:436-469) and is listed in task_cleared.  created_at is kept.  An absent id_state is drawn from
+  // std::random_device (the reference's ids are random, mod.rs:1489-1493) — std::invalid_argument on a multi-GPU pool
+  // (multi_gpu below), whose ranks must draw the same ids.  Ends with one pm_match: heartbeats are served from the adopted
+  // groups at once, and a taskless group claims a task there, as at its first filter_tasks.
+  RestoreReport restore_groups(const std::vector<NodeGroup>& groups, const std::unordered_map<std::string, std::string>& group_tasks,
+                               std::optional<uint64_t> id_state);
+  // group id text -> task id of every group that holds a task (what group_task:<id> holds), for the store's write-through
+  std::unordered_map<std::string, std::string> group_tasks() const;
+  // the state of the group id stream, for a successor's restore_groups (persisted under a key of the plugin's own)
+  uint64_t group_id_state() const;
+  // this plugin is one rank of a pool that runs tick_dist: restore_groups needs an id_state (set before calling it)
+  bool multi_gpu = false;
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -313,6 +336,8 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::optional<uint32_t> row_of_address_text(const NodeTable& t, const std::string& text) const;
 
   pm_engine* engine_ = nullptr;
+  // restore_groups' window: after a node and a task snapshot, before the first tick
+  std::atomic<bool> nodes_synced_{false}, tasks_synced_{false}, ticked_{false};
   std::vector<NodeGroupConfiguration> templates_;   // caller order: the engine's configuration index
   std::vector<pm_config_row> config_rows_;          // what pm_set_configs was given (pm_host_config_order reads sizes + PM_R_HAS_REQ)
   std::atomic<uint64_t> enabled_mask_{0};           // "available_node_group_configs" as last pushed (push_enabled)

@@ -99,6 +99,11 @@ std::string group_line(const NodeGroup& g) {
 
 }  // namespace
 
+namespace pmx_detail {
+void set_error(const std::string& what) { g_error = what; }
+int32_t give_text(const std::string& text, char* out, size_t cap, size_t* needed) { return give(text, out, cap, needed); }
+}  // namespace pmx_detail
+
 #define PMX_TRY(...)                  \
   try {                               \
     __VA_ARGS__;                      \

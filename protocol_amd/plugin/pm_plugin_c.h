@@ -102,6 +102,16 @@ int32_t pmx_dissolve_group(pmx_plugin*, const char* group_id);
  * pmx_set_upload_count's value.  Two lines: the name, then the group id the route keys its counter by ("no-group" if none). */
 int32_t pmx_upload_file_name(pmx_plugin*, const char* file_name, const char* address, char* out, size_t cap, size_t* needed);
 
+/* ---- restart and switch-over (pm_plugin_restore_c.cpp): GpuMatchPlugin::restore_groups / group_tasks / group_id_state.
+ * groups: group lines in the pmx_get_all_groups format, one per line; group_tasks: lines "<group id>\t<task id>";
+ * has_id_state = 0: no id_state (None).  The report waits for pmx_take_restore_report: "dropped\t<id>\t<reason>" lines,
+ * then "task_cleared\t<id>" lines. */
+int32_t pmx_restore_groups(pmx_plugin*, const char* groups, const char* group_tasks, uint32_t has_id_state, uint64_t id_state);
+int32_t pmx_take_restore_report(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_group_tasks(pmx_plugin*, char* out, size_t cap, size_t* needed); /* "<group id>\t<task id>" lines, by group id */
+int32_t pmx_group_id_state(pmx_plugin*, uint64_t* state);
+void pmx_set_multi_gpu(pmx_plugin*, uint32_t on); /* GpuMatchPlugin::multi_gpu */
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,10 @@ struct ListStore : TaskStore {
   }
 };
 
+// (pm_plugin_c.cpp) for the other files of the C face: what pmx_last_error reports, and the two-call text convention
+void set_error(const std::string& what);
+int32_t give_text(const std::string& text, char* out, size_t cap, size_t* needed);
+
 }  // namespace pmx_detail
 
 struct pmx_plugin {
@@ -55,6 +59,7 @@ struct pmx_plugin {
   std::shared_ptr<orchestrator::GpuMatchPlugin> plugin;
   std::unique_ptr<orchestrator::Scheduler> scheduler;
   std::atomic<uint64_t> upload_count{0};
+  std::string restore_report;  // the last pmx_restore_groups' report (pmx_take_restore_report)
 };
 
 #endif

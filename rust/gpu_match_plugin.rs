@@ -27,7 +27,7 @@
 use std::collections::{BTreeSet, HashMap};
 use std::ffi::{c_char, CStr, CString};
 use std::os::raw::c_void;
-use std::sync::atomic::{AtomicU32, AtomicU64, Ordering};
+use std::sync::atomic::{AtomicBool, AtomicU32, AtomicU64, Ordering};
 
 use alloy::primitives::Address;
 use anyhow::{anyhow, Error, Result};
@@ -216,6 +216,10 @@ extern "C" {
     fn pm_dist_carve_wait(e: *mut c_void) -> i32;
     fn pm_dist_match_begin(e: *mut c_void, x: *mut pm_dist_xfer) -> i32;
     fn pm_dist_tick_end(e: *mut c_void, stats: *mut pm_stats) -> i32;
+    fn pm_match(e: *mut c_void, task_of_worker: *mut u32, applicable_count: *mut u32) -> i32;
+    fn pm_adopt_groups(e: *mut c_void, groups: *const pm_group, n_groups: u32, members: *const u32, n_members: u32,
+                       id_state: u64) -> i32;
+    fn pm_group_id_state(e: *mut c_void, state: *mut u64) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -355,6 +359,19 @@ pub struct GpuMatchPlugin {
     /// holds no task is served the new one at its next heartbeat, as in the reference (scheduler_impl.rs:33-74),
     /// instead of after the next tick.  Costs one pair sweep + publish (~0.2 ms at 100k x 10k) per created task.
     pub republish_on_insert: bool,
+    /// restore_groups' window: after a node and a task snapshot, before the first tick
+    nodes_synced: AtomicBool,
+    tasks_synced: AtomicBool,
+    ticked: AtomicBool,
+    /// this plugin is one rank of a pool that runs tick_dist: restore_groups needs an id_state (set before calling it)
+    pub multi_gpu: bool,
+}
+
+/// what restore_groups left out (gpu_match_restore.cpp's RestoreReport)
+#[derive(Default, Debug)]
+pub struct RestoreReport {
+    pub dropped: Vec<(String, String)>,   // (group id text, reason)
+    pub task_cleared: Vec<String>,        // group_task:<id> naming no known task
 }
 
 unsafe impl Send for DistState {}
@@ -396,7 +413,9 @@ impl GpuMatchPlugin {
                               dist_rank: AtomicU32::new(0),
                               config_names: templates.iter().map(|t| t.name.clone()).collect(),
                               req_models: Vec::new(), nodes: Default::default(), tasks: Default::default(),
-                              upload_counter, webhook_plugins, republish_on_insert: false };
+                              upload_counter, webhook_plugins, republish_on_insert: false,
+                              nodes_synced: AtomicBool::new(false), tasks_synced: AtomicBool::new(false),
+                              ticked: AtomicBool::new(false), multi_gpu: false };
         this.set_configs(&templates);
         // an empty worker / task table, so that the delta calls have something to extend
         let empty = RowColumns::default();
@@ -565,6 +584,7 @@ impl GpuMatchPlugin {
                 check(unsafe { pm_on_worker_status_many(self.engine, gone.as_ptr(), gone_flags.as_ptr(), dead.as_ptr(), gone.len() as u32) })?;
             }
             t.engine_rows_stale = false;
+            self.nodes_synced.store(true, Ordering::Release);
             drop(t);
             return self.emit_group_webhooks();
         }
@@ -609,6 +629,7 @@ impl GpuMatchPlugin {
             check(unsafe { pm_set_addr_ranks(self.engine, ranks.as_ptr(), ranks.len() as u32) })?;
         }
         t.engine_rows_stale = false;
+        self.nodes_synced.store(true, Ordering::Release);
         drop(t);
         self.emit_group_webhooks()      // tombstoned nodes dissolved their groups
     }
@@ -659,6 +680,7 @@ impl GpuMatchPlugin {
         check(unsafe { pm_upload_tasks(self.engine, &soa) })?;
         self.push_enabled(&tasks)?;
         *guard = tasks;
+        self.tasks_synced.store(true, Ordering::Release);
         Ok(())
     }
 
@@ -697,6 +719,7 @@ impl GpuMatchPlugin {
     /// One body of run_group_management_loop (mod.rs:180-203) + every worker's filter_tasks, then the webhooks the
     /// reference sends from inside try_form_new_groups / execute_group_merge (mod.rs:612-625, 974-1000).
     pub fn tick(&self) -> Result<pm_stats> {
+        self.ticked.store(true, Ordering::Release);
         let mut s = pm_stats::default();
         check(unsafe { pm_tick(self.engine, &mut s) })?;
         self.emit_group_webhooks()?;
@@ -711,6 +734,7 @@ impl GpuMatchPlugin {
     pub fn tick_dist(&self, comm: &dyn AllGather) -> Result<pm_stats> {
         let (rank, world) = (comm.rank(), comm.world());
         if world == 0 || rank >= world { return Err(anyhow!("tick_dist: rank outside the communicator")); }
+        self.ticked.store(true, Ordering::Release);
         {
             let t = self.nodes.read();
             let mut d = self.dist.lock();
@@ -987,6 +1011,104 @@ impl GpuMatchPlugin {
         check(unsafe { pm_dissolve_group_by_id(self.engine, id, &mut dissolved) })?;
         if dissolved != 0 { self.emit_group_webhooks()?; }                              // send_group_destroyed, mod.rs:1469-1481
         Ok(())
+    }
+
+    /// Restart and switch-over: the groups the store holds (orchestrator:groups_index / node_group:<id> in
+    /// get_all_groups order, group_task:<id>) into the engine — after sync_nodes and sync_tasks, before the first tick
+    /// (PM_ESTATE at any other time).  A group that cannot be taken over is dropped and reported, not an error: an id that is
+    /// not "{:x}" text, an unknown configuration name, an address outside the node table, a node of an earlier group, no
+    /// nodes, more than max_group_size nodes, the id of an earlier group.  A group_task naming an unknown task leaves the
+    /// group without one (get_current_group_task, mod.rs:436-469): task_cleared.  created_at is kept.  id_state None draws
+    /// one from the OS (the reference's ids are random, mod.rs:1489-1493) — an error on a multi-GPU pool, whose ranks must
+    /// draw the same ids.  Ends with one pm_match: heartbeats are served from the adopted groups at once.
+    pub fn restore_groups(&self, groups: &[NodeGroup], group_tasks: &HashMap<String, String>, id_state: Option<u64>)
+                          -> Result<RestoreReport> {
+        if self.ticked.load(Ordering::Acquire) || !self.nodes_synced.load(Ordering::Acquire) || !self.tasks_synced.load(Ordering::Acquire) {
+            return Err(anyhow!("pm_engine error {PM_ESTATE}: restore_groups: after sync_nodes and sync_tasks, before the first tick"));
+        }
+        if id_state.is_none() && (self.multi_gpu || self.dist.lock().world > 1) {
+            return Err(anyhow!("restore_groups: the ranks of a multi-GPU pool must draw the same ids: pass id_state"));
+        }
+        let mut report = RestoreReport::default();
+        let t = self.nodes.read();          // (LOCK ORDER: nodes, tasks, the engine)
+        let tasks = self.tasks.read();
+        let task_position: HashMap<String, u32> =
+            tasks.iter().enumerate().rev().map(|(i, task)| (task.id.to_string(), i as u32)).collect();   // (first occurrence wins)
+        let (mut records, mut members, mut created) = (Vec::<pm_group>::new(), Vec::<u32>::new(), Vec::new());
+        let mut ids = std::collections::HashSet::new();
+        let mut taken = vec![false; t.rows.len()];
+        'groups: for g in groups {
+            let Some(id) = Self::parse_group_id(&g.id) else {
+                report.dropped.push((g.id.clone(), "the id is not the {:x} text of a u64".into()));
+                continue;
+            };
+            let Some(cfg) = self.config_names.iter().position(|n| *n == g.configuration_name) else {
+                report.dropped.push((g.id.clone(), format!("unknown configuration {}", g.configuration_name)));
+                continue;
+            };
+            let mut rows = Vec::<u32>::new();
+            for a in &g.nodes {
+                let Some(row) = Self::row_of_address_text(&t, a) else {
+                    report.dropped.push((g.id.clone(), format!("node {a} is not in the node table")));
+                    continue 'groups;
+                };
+                if taken[row as usize] || rows.contains(&row) {
+                    report.dropped.push((g.id.clone(), format!("node {a} is already in an earlier group")));
+                    continue 'groups;
+                }
+                rows.push(row);
+            }
+            let max_size = self.templates[cfg].max_group_size;
+            if rows.is_empty() || rows.len() > max_size {
+                let why = if rows.is_empty() { "the group has no nodes".to_string() }
+                          else { format!("{} nodes, more than max_group_size {}", rows.len(), max_size) };
+                report.dropped.push((g.id.clone(), why));
+                continue;
+            }
+            if !ids.insert(id) {
+                report.dropped.push((g.id.clone(), "the id of an earlier group".into()));
+                continue;
+            }
+            let mut task = PM_NONE;
+            if let Some(task_id) = group_tasks.get(&g.id) {                              // get_current_group_task (mod.rs:436-469)
+                match task_position.get(task_id) {
+                    Some(&at) => task = at,
+                    None => report.task_cleared.push(g.id.clone()),
+                }
+            }
+            for &r in &rows { taken[r as usize] = true; }
+            records.push(pm_group { id, config: cfg as u32, n_members: rows.len() as u32, member_begin: members.len() as u32, task });
+            members.extend_from_slice(&rows);
+            created.push((id, g.created_at));
+        }
+        let state = match id_state {
+            Some(s) => s,
+            None => rand::random::<u64>(),   // (generate_group_id draws from rand::rng(), mod.rs:1489-1493)
+        };
+        check(unsafe { pm_adopt_groups(self.engine, if records.is_empty() { std::ptr::null() } else { records.as_ptr() }, records.len() as u32,
+                                       if members.is_empty() { std::ptr::null() } else { members.as_ptr() }, members.len() as u32, state) })?;
+        {
+            let mut stamps = self.group_created_at.lock();
+            for (id, at) in created { stamps.insert(id, at); }
+        }
+        check(unsafe { pm_match(self.engine, std::ptr::null_mut(), std::ptr::null_mut()) })?;   // heartbeats served from here on
+        Ok(report)
+    }
+
+    /// group id text -> task id of every group that holds a task (what group_task:<id> holds): the store's write-through
+    pub fn group_tasks(&self) -> Result<HashMap<String, String>> {
+        let t = self.nodes.read();
+        let tasks = self.tasks.read();      // (task positions are positions in this Vec)
+        let (_, groups, _) = self.snapshot_groups(t.rows.len(), false)?;
+        Ok(groups.iter().filter(|g| g.task != PM_NONE && (g.task as usize) < tasks.len())
+                 .map(|g| (format!("{:x}", g.id), tasks[g.task as usize].id.to_string())).collect())
+    }
+
+    /// the state of the group id stream, for a successor's restore_groups (persisted under a key of the plugin's own)
+    pub fn group_id_state(&self) -> Result<u64> {
+        let mut state = 0u64;
+        check(unsafe { pm_group_id_state(self.engine, &mut state) })?;
+        Ok(state)
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).
