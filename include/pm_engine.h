@@ -42,8 +42,8 @@ extern "C" {
                             accepts new rows behind the known ones; + pm_host_to_lowercase (the model rule is Unicode now); carve_variant 2 / 4
                             are PM_EINVAL (since round 5); pm_stats of a pm_tick / pm_tick_many: ms_publish is 0 (the claim publishes),
                             ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only;
-                            + pm_adopt_groups / pm_group_id_state (restart and switch-over): compatible additions, the version
-                            stays 3 */
+                            + pm_adopt_groups / pm_group_id_state (restart and switch-over), + pm_explain_workers /
+                            pm_config_report / pm_task_report (diagnostics): compatible additions, the version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -344,6 +344,61 @@ int32_t pm_adopt_groups(pm_engine*, const pm_group* groups, uint32_t n_groups, c
 /* The state of the group id stream (the next pm_form_groups / merge draws from it: splitmix64), for handing over to a
  * successor's pm_adopt_groups.  PM_ESTATE inside a stepwise tick. */
 int32_t pm_group_id_state(pm_engine*, uint64_t* state);
+
+/* ------------------------------------------------------------------ diagnostics (read-only reports)
+ * Why a node sits idle, why a task runs on no group, how much room each configuration has left.  The reference has
+ * debug! lines for the first (node_groups/mod.rs:478-628) and scans the store for the others (get_groups_for_task,
+ * mod.rs:1350-1386; nodes_per_task, metrics/sync_service.rs:243-267).  All three reports are computed on the device from
+ * the tables the engine holds and reflect every call made before them, status changes that have not gone up yet included.
+ * None of them changes what the next tick does: nothing is compacted, no pending delta is consumed, the compat masks are
+ * not read (they may be stale).  PM_ESTATE inside a stepwise tick (dist_phase != 0) and before configurations and workers
+ * are uploaded (pm_task_report: tasks too).  The version stays 3 (compatible additions).
+ *
+ * Reason codes: the first clause of ComputeSpecs::meets a worker fails for a configuration, in the reference's order
+ * (shared/src/models/node.rs:377-541).  Over GPU alternatives (OR) the code is the LARGEST of the alternatives' codes
+ * when all of them fail: the alternative that got furthest.  code == PM_WHY_OK exactly when the pm_compat_masks bit is set. */
+enum {
+  PM_WHY_OK = 0,         /* meets it; also every worker when the configuration has no requirements (mod.rs:211) */
+  PM_WHY_NO_SPECS = 1,   /* requirements present, compute_specs None (mod.rs:212) */
+  PM_WHY_CPU = 2,        /* cpu required: no cpu, or its cores missing or too few (node.rs:381-393, 531-540) */
+  PM_WHY_RAM = 3,        /* node.rs:396-404 */
+  PM_WHY_STORAGE = 4,    /* node.rs:407-418 */
+  PM_WHY_GPU_NONE = 5,   /* GPU alternatives listed, the spec has no gpu (node.rs:420-435) */
+  PM_WHY_GPU_COUNT = 6,  /* node.rs:447-461 */
+  PM_WHY_GPU_MODEL = 7,  /* node.rs:463-484 */
+  PM_WHY_GPU_MEM = 8,    /* memory_mb, its min or its max (node.rs:487-503) */
+  PM_WHY_GPU_TOTAL = 9,  /* count x memory_mb (u32, wrapping) below the min or above the max (node.rs:506-522) */
+  PM_WHY_N = 10
+};
+/* A worker's state, first match wins: in a group; status not Healthy; no p2p id; else idle — a candidate of the next carve
+ * (mod.rs:492-497). */
+enum { PM_WS_IDLE = 0, PM_WS_IN_GROUP = 1, PM_WS_UNHEALTHY = 2, PM_WS_NO_P2P = 3 };
+
+/* The reason code of every (worker, configuration) pair for workers[0..n): why[i * n_cfgs + c] (configurations in
+ * pm_set_configs row order), state[i] a PM_WS_* value.  state may be NULL.  A worker index >= W: PM_ERANGE, nothing
+ * written. */
+int32_t pm_explain_workers(pm_engine*, const uint32_t* workers, uint32_t n, uint8_t* why, uint32_t* state);
+
+/* One row per configuration (pm_set_configs row order).  "Eligible" workers are Healthy with a p2p id. */
+typedef struct pm_config_report_row {
+  uint32_t enabled;             /* bit of pm_set_enabled_mask */
+  uint32_t eligible_meets;      /* eligible workers that meet it, grouped or not (== why[PM_WHY_OK]) */
+  uint32_t idle_meets;          /* ... of them in no group: the next carve's candidates for it */
+  uint32_t why[PM_WHY_N];       /* eligible workers by reason code (their sum is the eligible row count) */
+  uint32_t groups;              /* live groups of this configuration */
+  uint32_t members;             /* their workers */
+  uint32_t groups_without_task; /* of them without a claimed task */
+  uint32_t tasks_allowing;      /* live tasks whose topology mask has the bit (unrestricted tasks included) */
+} pm_config_report_row;
+/* *n_cfgs = the number of configurations always; cap < n_cfgs: PM_ERANGE, nothing written (out may be NULL then). */
+int32_t pm_config_report(pm_engine*, pm_config_report_row* out, uint32_t cap, uint32_t* n_cfgs);
+
+/* Per task, indexed by position in the caller's CURRENT task list (as pm_match_per_task reports them; T entries each):
+ *   groups_running   live groups that hold the task (get_groups_for_task, mod.rs:1350-1386)
+ *   workers_running  their workers (nodes_per_task, metrics/sync_service.rs:243-267)
+ *   groups_allowed   live groups whose configuration the task's topologies allow
+ * Any output may be NULL. */
+int32_t pm_task_report(pm_engine*, uint32_t* groups_running, uint32_t* workers_running, uint32_t* groups_allowed);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

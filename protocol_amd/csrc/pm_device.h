@@ -95,6 +95,31 @@ struct CompatArgs {
   uint64_t* compat;
 };
 
+// counters of one configuration in ReportArgs::out / the LDS copy (REP_STRIDE words a configuration)
+enum : uint32_t {
+  REP_WHY = 0,  // [0, PM_WHY_N): eligible workers by code
+  REP_IDLE = PM_WHY_N,
+  REP_GROUPS,
+  REP_MEMBERS,
+  REP_NO_TASK,
+  REP_TASKS,
+  REP_STRIDE = 16
+};
+
+struct ReportArgs {
+  CompatArgs c;                 // worker columns (flags: the current host column), configurations, alternatives, model rule
+  const int32_t* group_of;      // current (host truth): -1 = in no group
+  // the group list: slots [0, G); live_bits (one bit a slot) marks the live ones, nullptr = all of them
+  const uint32_t *g_cfg, *g_n, *g_task, *live_bits;
+  uint32_t G;
+  // the task index space [t_lo, t_cap): topology masks, live bitmap, per-word live prefix (positions)
+  const uint64_t *tmask, *tlive;
+  const uint32_t* tprefix;
+  uint32_t t_lo, t_cap;
+  uint32_t* out;                // pm_config_report: [n_cfgs][REP_STRIDE]; pm_task_report: [PM_MAX_CONFIGS] groups per config
+  uint32_t *running, *workers, *allowed;  // pm_task_report, T entries each (running / workers zeroed beforehand)
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -322,6 +347,10 @@ struct CarveArgs {
 };
 
 void launch_compat(const CompatArgs& a, hipStream_t s);
+// diagnostics (pm_report.inc)
+void launch_explain(const CompatArgs& p, const uint32_t* rows, uint32_t n, uint32_t stride, uint32_t* why_out, hipStream_t s);
+void launch_config_report(const ReportArgs& a, uint32_t max_blocks, hipStream_t s);
+void launch_task_report(const ReportArgs& a, uint32_t max_blocks, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

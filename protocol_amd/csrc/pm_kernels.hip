@@ -6,6 +6,8 @@
 //   pair_sweep_*         orchestrator/src/plugins/node_groups/scheduler_impl.rs:42-61 /
 //                        mod.rs:1134-1162 (topology filter), one row per heartbeat
 //   newest_kernel        orchestrator/src/plugins/newest_task/mod.rs:8-19
+//   explain_kernel,      the same clauses as compat_kernel, as reason codes, and the read-only reports
+//   *_report_kernel      (pm_report.inc)
 //   carve_kernel         orchestrator/src/plugins/node_groups/mod.rs:478-628 (try_form_new_groups)
 //                        with :218-255 (Haversine proximity) and, in MERGE mode, the selection half
 //                        of :752-860 (attempt_group_merge)
@@ -777,5 +779,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_carve_kernel.inc"  // carve_kernel: the batch pipeline's validator (and the merge pass)
 #include "pm_stream.inc"        // the streaming carve (carve_variant 0): one launch per pass
 
+#include "pm_report.inc"        // diagnostics: reason codes, the config and task reports, their launchers
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

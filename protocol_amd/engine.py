@@ -35,6 +35,12 @@ group_dt = np.dtype([("id", "<u8"), ("config", "<u4"), ("n_members", "<u4"), ("m
 GROUP_EVENT = np.dtype([("group_id", "<u8"), ("kind", "<u4"), ("config", "<u4"), ("member_begin", "<u4"),
                         ("n_members", "<u4")])   # pm_group_event
 GROUP_CREATED, GROUP_DESTROYED = 1, 2
+# pm_config_report_row (include/pm_engine.h)
+config_report_dt = np.dtype([("enabled", "<u4"), ("eligible_meets", "<u4"), ("idle_meets", "<u4"), ("why", "<u4", (10,)),
+                             ("groups", "<u4"), ("members", "<u4"), ("groups_without_task", "<u4"), ("tasks_allowing", "<u4")])
+# reason codes (PM_WHY_*, first failing clause of ComputeSpecs::meets) and worker states (PM_WS_*)
+WHY_NAMES = ["ok", "no_specs", "cpu", "ram", "storage", "gpu_none", "gpu_count", "gpu_model", "gpu_mem", "gpu_total"]
+WS_IDLE, WS_IN_GROUP, WS_UNHEALTHY, WS_NO_P2P = 0, 1, 2, 3
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -100,6 +106,7 @@ EXPORTS = [
     "pm_dist_match_begin", "pm_dist_tick_end", "pm_match_per_task_device",
     "pm_dissolve_group_by_id", "pm_get_group_by_id", "pm_get_group_of_worker", "pm_host_to_lowercase",
     "pm_adopt_groups", "pm_group_id_state",
+    "pm_explain_workers", "pm_config_report", "pm_task_report",
 ]
 
 _lib = None
@@ -165,6 +172,9 @@ def lib() -> C.CDLL:
         L.pm_get_group_of_worker.argtypes = [vp, u32, vp, vp, u32, C.POINTER(u32)]
         L.pm_adopt_groups.argtypes = [vp, vp, u32, vp, u32, u64]
         L.pm_group_id_state.argtypes = [vp, C.POINTER(u64)]
+        L.pm_explain_workers.argtypes = [vp, vp, u32, vp, vp]
+        L.pm_config_report.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_task_report.argtypes = [vp, vp, vp, vp]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -235,6 +245,7 @@ class Engine:
         self._h = C.c_void_p()
         check(L.pm_engine_create(C.byref(cfg), C.byref(self._h)))
         self.W = 0
+        self.C = 0
         self.T = 0
 
     def close(self):
@@ -424,6 +435,30 @@ class Engine:
         s = C.c_uint64(0)
         check(lib().pm_group_id_state(self._h, C.byref(s)))
         return s.value
+
+    # ---- diagnostics (read-only reports; they change nothing the next tick does)
+    def explain_workers(self, workers=None):
+        """pm_explain_workers -> (why: uint8 [n, C], the PM_WHY_* code of every (worker, configuration) pair; state: uint32 [n],
+        PM_WS_*).  workers=None: every row."""
+        w = np.arange(self.W, dtype=np.uint32) if workers is None else _arr(workers, np.uint32)
+        why = np.zeros((len(w), self.C), dtype=np.uint8)
+        state = np.zeros(len(w), dtype=np.uint32)
+        check(lib().pm_explain_workers(self._h, w.ctypes.data if len(w) else None, len(w),
+                                       why.ctypes.data if why.size else None, state.ctypes.data if len(w) else None))
+        return why, state
+
+    def config_report(self) -> np.ndarray:
+        """pm_config_report -> one config_report_dt record per configuration (pm_set_configs row order)"""
+        out = np.zeros(self.C, dtype=config_report_dt)
+        n = C.c_uint32(0)
+        check(lib().pm_config_report(self._h, out.ctypes.data if self.C else None, self.C, C.byref(n)))
+        return out[:n.value]
+
+    def task_report(self):
+        """pm_task_report -> (groups_running, workers_running, groups_allowed), uint32 [T] each, by task position"""
+        outs = [np.zeros(self.T, dtype=np.uint32) for _ in range(3)]
+        check(lib().pm_task_report(self._h, *[o.ctypes.data if self.T else None for o in outs]))
+        return tuple(outs)
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

@@ -34,6 +34,7 @@
 #ifndef PM_GPU_MATCH_PLUGIN_HPP
 #define PM_GPU_MATCH_PLUGIN_HPP
 
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdint>
@@ -278,6 +279,34 @@ class GpuMatchPlugin : public SchedulerPlugin {
   uint64_t group_id_state() const;
   // this plugin is one rank of a pool that runs tick_dist: restore_groups needs an id_state (set before calling it)
   bool multi_gpu = false;
+
+  // ---- diagnostics (INTEGRATION.md "Diagnostics"; gpu_match_report.cpp): the engine's three read-only reports by name.
+  // Reason names, PM_WHY_* order: "ok", "no_specs", "cpu", "ram", "storage", "gpu_none", "gpu_count", "gpu_model", "gpu_mem",
+  // "gpu_total"; states: "in_group", "unhealthy", "no_p2p", "idle".
+  struct NodeExplanation {
+    std::string state;
+    std::vector<std::pair<std::string, std::string>> configs;  // (configuration name, reason name), constructor order
+  };
+  // why a node sits idle: nullopt when the node table does not hold the address
+  std::optional<NodeExplanation> explain_node(const std::string& address) const;
+  struct ConfigurationReport {
+    std::string name;
+    bool enabled = false;
+    uint32_t eligible_meets = 0, idle_meets = 0;
+    std::array<uint32_t, 10> why{};  // Healthy nodes with a p2p id by reason code (why[0] == eligible_meets)
+    uint32_t groups = 0, members = 0, groups_without_task = 0, tasks_allowing = 0;
+  };
+  // how much room each configuration has left, constructor order
+  std::vector<ConfigurationReport> configuration_report() const;
+  struct TaskReport {
+    uint32_t groups_running = 0;   // get_groups_for_task (mod.rs:1350-1386)
+    uint32_t workers_running = 0;  // nodes_per_task (metrics/sync_service.rs:243-267)
+    uint32_t groups_allowed = 0;   // live groups whose configuration the task's topologies allow
+  };
+  // by task id, every task of the last sync_tasks / on_task_created / on_task_deleted
+  std::unordered_map<std::string, TaskReport> task_report() const;
+  static const char* why_name(uint32_t code);
+  static const char* state_name(uint32_t state);
 
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {

@@ -112,6 +112,16 @@ int32_t pmx_group_tasks(pmx_plugin*, char* out, size_t cap, size_t* needed); /* 
 int32_t pmx_group_id_state(pmx_plugin*, uint64_t* state);
 void pmx_set_multi_gpu(pmx_plugin*, uint32_t on); /* GpuMatchPlugin::multi_gpu */
 
+/* ---- diagnostics (pm_plugin_report_c.cpp): GpuMatchPlugin::explain_node / configuration_report / task_report.
+ *   pmx_explain_node           empty = the node table does not hold the address; else "state\t<state>", then one line
+ *                              "<configuration name>\t<reason name>" per configuration (constructor order)
+ *   pmx_configuration_report   one line per configuration: "<name>\t<enabled 0|1>\t<eligible_meets>\t<idle_meets>\t<groups>\t
+ *                              <members>\t<groups_without_task>\t<tasks_allowing>\t<why[0]>\t...\t<why[9]>"
+ *   pmx_task_report            "<task id>\t<groups_running>\t<workers_running>\t<groups_allowed>", by task id */
+int32_t pmx_explain_node(pmx_plugin*, const char* address, char* out, size_t cap, size_t* needed);
+int32_t pmx_configuration_report(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_task_report(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

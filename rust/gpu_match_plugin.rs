@@ -153,6 +153,20 @@ pub struct pm_stats {
     pub ms_propose_kernel: f32, pub proposals: u32, pub propose_keys: u64,
 }
 
+/// pm_config_report_row (include/pm_engine.h)
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_config_report_row {
+    pub enabled: u32,
+    pub eligible_meets: u32,
+    pub idle_meets: u32,
+    pub why: [u32; 10],
+    pub groups: u32,
+    pub members: u32,
+    pub groups_without_task: u32,
+    pub tasks_allowing: u32,
+}
+
 #[repr(C)]
 pub struct pm_group_vars {
     pub group_index: u32,
@@ -220,6 +234,9 @@ extern "C" {
     fn pm_adopt_groups(e: *mut c_void, groups: *const pm_group, n_groups: u32, members: *const u32, n_members: u32,
                        id_state: u64) -> i32;
     fn pm_group_id_state(e: *mut c_void, state: *mut u64) -> i32;
+    fn pm_explain_workers(e: *mut c_void, workers: *const u32, n: u32, why: *mut u8, state: *mut u32) -> i32;
+    fn pm_config_report(e: *mut c_void, out: *mut pm_config_report_row, cap: u32, n_cfgs: *mut u32) -> i32;
+    fn pm_task_report(e: *mut c_void, groups_running: *mut u32, workers_running: *mut u32, groups_allowed: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -372,6 +389,42 @@ pub struct GpuMatchPlugin {
 pub struct RestoreReport {
     pub dropped: Vec<(String, String)>,   // (group id text, reason)
     pub task_cleared: Vec<String>,        // group_task:<id> naming no known task
+}
+
+/// explain_node's answer (gpu_match_report.cpp's NodeExplanation)
+#[derive(Default, Debug)]
+pub struct NodeExplanation {
+    pub state: String,                        // "in_group", "unhealthy", "no_p2p", "idle"
+    pub configs: Vec<(String, String)>,       // (configuration name, reason name), constructor order
+}
+
+/// one row of configuration_report (gpu_match_report.cpp's ConfigurationReport)
+#[derive(Default, Debug)]
+pub struct ConfigurationReport {
+    pub name: String,
+    pub enabled: bool,
+    pub eligible_meets: u32,
+    pub idle_meets: u32,
+    pub why: [u32; 10],                       // Healthy nodes with a p2p id by reason code (why[0] == eligible_meets)
+    pub groups: u32,
+    pub members: u32,
+    pub groups_without_task: u32,
+    pub tasks_allowing: u32,
+}
+
+/// one task of task_report (gpu_match_report.cpp's TaskReport)
+#[derive(Default, Debug, Clone, Copy)]
+pub struct TaskReport {
+    pub groups_running: u32,                  // get_groups_for_task (mod.rs:1350-1386)
+    pub workers_running: u32,                 // nodes_per_task (metrics/sync_service.rs:243-267)
+    pub groups_allowed: u32,                  // live groups whose configuration the task's topologies allow
+}
+
+/// reason names in PM_WHY_* order
+const WHY_NAMES: [&str; 10] = ["ok", "no_specs", "cpu", "ram", "storage", "gpu_none", "gpu_count", "gpu_model", "gpu_mem", "gpu_total"];
+
+fn state_name(state: u32) -> &'static str {
+    match state { 1 => "in_group", 2 => "unhealthy", 3 => "no_p2p", 0 => "idle", _ => "unknown" }
 }
 
 unsafe impl Send for DistState {}
@@ -1109,6 +1162,55 @@ impl GpuMatchPlugin {
         let mut state = 0u64;
         check(unsafe { pm_group_id_state(self.engine, &mut state) })?;
         Ok(state)
+    }
+
+    // ---- diagnostics (INTEGRATION.md "Diagnostics"): the engine's three read-only reports by name
+
+    /// why a node sits idle: None when the node table does not hold the address
+    pub fn explain_node(&self, address: &str) -> Result<Option<NodeExplanation>> {
+        let t = self.nodes.read();           // (LOCK ORDER: nodes, the engine)
+        let Some(row) = Self::row_of_address_text(&t, address) else { return Ok(None) };
+        let mut why = vec![0u8; self.config_names.len()];
+        let mut state = 0u32;
+        check(unsafe { pm_explain_workers(self.engine, &row, 1, if why.is_empty() { std::ptr::null_mut() } else { why.as_mut_ptr() },
+                                          &mut state) })?;
+        Ok(Some(NodeExplanation {
+            state: state_name(state).to_string(),
+            configs: why.iter().enumerate()
+                        .map(|(c, &k)| (self.config_names[c].clone(), WHY_NAMES.get(k as usize).unwrap_or(&"unknown").to_string()))
+                        .collect(),
+        }))
+    }
+
+    /// how much room each configuration has left, constructor order
+    pub fn configuration_report(&self) -> Result<Vec<ConfigurationReport>> {
+        let mut rows = vec![pm_config_report_row::default(); self.config_names.len()];
+        let mut n = 0u32;
+        check(unsafe { pm_config_report(self.engine, if rows.is_empty() { std::ptr::null_mut() } else { rows.as_mut_ptr() },
+                                        rows.len() as u32, &mut n) })?;
+        Ok(rows.iter().take(n as usize).enumerate().map(|(c, r)| ConfigurationReport {
+            name: self.config_names[c].clone(),
+            enabled: r.enabled != 0,
+            eligible_meets: r.eligible_meets,
+            idle_meets: r.idle_meets,
+            why: r.why,
+            groups: r.groups,
+            members: r.members,
+            groups_without_task: r.groups_without_task,
+            tasks_allowing: r.tasks_allowing,
+        }).collect())
+    }
+
+    /// by task id, every task of the last sync_tasks / on_task_created / on_task_deleted
+    pub fn task_report(&self) -> Result<HashMap<String, TaskReport>> {
+        let tasks = self.tasks.read();      // (the engine's positions index this Vec)
+        let n = tasks.len();
+        let (mut running, mut workers, mut allowed) = (vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+        let ptr = |v: &mut Vec<u32>| if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() };
+        check(unsafe { pm_task_report(self.engine, ptr(&mut running), ptr(&mut workers), ptr(&mut allowed)) })?;
+        Ok(tasks.iter().enumerate().map(|(i, t)| (t.id.to_string(), TaskReport {
+            groups_running: running[i], workers_running: workers[i], groups_allowed: allowed[i],
+        })).collect())
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).
