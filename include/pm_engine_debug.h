@@ -80,6 +80,15 @@ int32_t pm_debug_park_records(pm_engine* e, unsigned long long* out, uint32_t ca
 int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave,
                               uint32_t slot_bits, uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches);
 
+/* The carve's distance key through the device functions the carve runs (tests/test_gpu_distance_key.py).  mode 0: in[5n] =
+ * lat[2n] (the n first points, then the n second points), lon[2n], slot[n] (integers as f64); geo_kernel gives each point its
+ * cos(lat) and unit vector, and per pair out[20n] holds, twenty f64 a pair: sin_band(dlat / 2), sin_band(dlon / 2), cos(lat)
+ * and ux, uy, uz of the first point, the same of the second, hav_a, prox_a, 1 if prox_a took the chord form (else 0),
+ * candidate_key's unpacked key (its f64 bits), then pack_key(prox_a, slot) at the 13, 18 and 21 slot bits of the library, and
+ * pack_key(hav_a, slot) at the same three widths (f64 bits; the slot taken modulo the width).  mode 1: out[n] = sin_band(in[n]).
+ * mode 2 (in, n unused): out[8] = PM_A_CHORD_MIN, PM_A_MAX_SAFE, the three certificate bands, the three slot widths. */
+int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,9 +12,11 @@ namespace pm {
 static constexpr double PM_RAD = 3.14159265358979323846 / 180.0;  // f64::to_radians factor
 static constexpr uint64_t PM_KEY_NOLOC = 0x7FEFFFFFFFFFFFFFull;   // bits of f64::MAX (mod.rs:244,249)
 static constexpr double PM_A_MAX_SAFE = 1.0 - 1.0 / 1048576.0;    // near-antipodal => settle on host
-// below this Haversine term (about 10 km) the chord-length form of the key is not accurate enough for the
-// certificate band and the proposer evaluates the sine form instead (see prox_key in pm_kernels.hip)
-static constexpr double PM_A_CHORD_MIN = 6.2e-7;
+// below this Haversine term (about 14.5 km) the chord-length form of the key is not accurate enough for the
+// certificate band and the proposer evaluates the sine form instead (see prox_a in pm_validate.inc): the chord form's
+// error against the reference's a is up to 2e-15 / sqrt(a), and at 1.3e-6 that is 1.75e-12, within an eighth of the
+// narrowest band (tests/test_distance_key_model.py)
+static constexpr double PM_A_CHORD_MIN = 1.3e-6;
 // carve kernel geometry
 static constexpr uint32_t PM_CARVE_SLOTS = 8192;       // candidate slots with positions/bitmaps in LDS, keys in VGPRs
 static constexpr uint32_t PM_CARVE_PART = 64;          // per-wave partial selection capacity (max_group_size - 1)
@@ -359,6 +361,9 @@ hipError_t launch_row_bench(const CarveArgs* d_args, uint32_t seed, uint32_t ci,
 #endif
 void launch_row_network_test(const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave, uint32_t slot_bits,
                              uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches, hipStream_t s);
+// debug (pm_debug_distance_keys): the distance key of n pairs through the carve's device functions; PM_DK_WORDS f64 per pair
+static constexpr uint32_t PM_DK_WORDS = 20;
+void launch_distance_key_test(const double* in, const double* geo, uint32_t n, uint32_t mode, double* out, hipStream_t s);
 void launch_update_rows(const RowUpdateArgs& a, hipStream_t s);
 void launch_worker_selector(const int32_t* group_of, const uint32_t* g_cfg, uint32_t R, const uint32_t* rows,
                             uint64_t* sel, hipStream_t s);

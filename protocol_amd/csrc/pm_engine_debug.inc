@@ -198,6 +198,39 @@ int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t
   return rc;
 }
 
+// debug (include/pm_engine_debug.h): the distance key of n pairs by geo_kernel and the carve's own device functions
+int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out) {
+  if (!e || !out || mode > 2u) return set_error(PM_EINVAL, "null argument");
+  if (mode == 2u) {
+    const double c[8] = {PM_A_CHORD_MIN, PM_A_MAX_SAFE, PM_TIE_BAND, PM_TIE_BAND_BIG, PM_TIE_BAND_MEM,
+                         double(PM_CARVE_SLOT_BITS), double(PM_CARVE_SLOT_BITS_BIG), double(PM_CARVE_SLOT_BITS_MEM)};
+    std::memcpy(out, c, sizeof(c));
+    return PM_OK;
+  }
+  if (!in || n == 0 || n > (1u << 26)) return set_error(PM_EINVAL, "distance keys: 1 to 2^26 inputs");
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const size_t n_in = mode == 0u ? size_t(5) * n : n, n_out = mode == 0u ? size_t(PM_DK_WORDS) * n : n;
+  double *d_in = nullptr, *d_geo = nullptr, *d_out = nullptr;
+  int32_t rc = PM_OK;
+  if (hipMalloc((void**)&d_in, n_in * 8) != hipSuccess || hipMalloc((void**)&d_out, n_out * 8) != hipSuccess ||
+      (mode == 0u && hipMalloc((void**)&d_geo, size_t(8) * n * 8) != hipSuccess)) {
+    rc = set_error(PM_ENOMEM, "distance key test buffers");
+  } else {
+    (void)hipMemcpyAsync(d_in, in, n_in * 8, hipMemcpyHostToDevice, e->stream);
+    if (mode == 0u)  // cos(lat), ux, uy, uz of the 2n points, by the kernel that makes the worker table's columns
+      launch_geo(d_in, d_in + size_t(2) * n, d_geo, d_geo + size_t(2) * n, d_geo + size_t(4) * n, d_geo + size_t(6) * n, 2u * n,
+                 e->stream);
+    launch_distance_key_test(d_in, d_geo, n, mode, d_out, e->stream);
+    (void)hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, e->stream);
+    if (hipStreamSynchronize(e->stream) != hipSuccess) rc = set_error(PM_ENODEV, "distance key test");
+  }
+  if (d_in) (void)hipFree(d_in);
+  if (d_geo) (void)hipFree(d_geo);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
 #ifdef PM_ROW_BENCH
 // A measuring build's entry (tools/row_bench.py; not in the headers: the product does not have it): the row of the kth candidate
 // of the ci-th available configuration of the LAST match, made `reps` times by one wave alone, every position of the

@@ -17,6 +17,10 @@ void launch_row_network_test(const uint64_t* keys, const uint32_t* sites, uint32
   hipLaunchKernelGGL(row_network_test_kernel, dim3(n_waves / 4u), dim3(256), 0, s, keys, sites, n_per_wave, slot_bits, ulps, upto, rows_out,
                      mismatches);
 }
+void launch_distance_key_test(const double* in, const double* geo, uint32_t n, uint32_t mode, double* out, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(distance_key_test_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, in, geo, n, mode, out);
+}
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s) {
   if (W == 0) return;

@@ -386,7 +386,7 @@ __device__ __forceinline__ void tile_keys(const CarveArgs& p, const TileBuf& tb,
       const bool counts = ((aw[v] >> lane) & 1ull) && t != s && !(shared && located && si[v] == ssite && t < s);
       const double dx = x[v] - sg.ux, dy = y[v] - sg.uy, dz = z[v] - sg.uz;
       double a = 0.25 * fma(dx, dx, fma(dy, dy, dz * dz));
-      // (see prox_a: the sine form below ~10 km.  A candidate at the seed's own site — identical coordinates — has the
+      // (see prox_a: the sine form below ~14.5 km.  A candidate at the seed's own site — identical coordinates — has the
       // Haversine term 0 in either form, exactly: sin(0) = 0; a city of co-located workers would otherwise send
       // nearly every stride of its seeds' sweeps through the sine polynomials)
       const bool same_site = located && si[v] == ssite;
@@ -1055,4 +1055,51 @@ __global__ __launch_bounds__(256) void row_network_test_kernel(const uint64_t* _
   }
   rows_out[(size_t)w * 64u + lane] = b.key;
   if (lane == 0u && bad) atomicOr(&mismatches[0], bad), atomicAdd(&mismatches[1], 1u);
+}
+
+// debug (pm_debug_distance_keys): the carve's distance key of n pairs through the device functions the carve runs.  in: lat[2n]
+// (first points, then second points), lon[2n], slot[n] (as f64); geo: what geo_kernel made of those 2n points (cos(lat), ux,
+// uy, uz: 2n each).  Per pair out[PM_DK_WORDS]: see include/pm_engine_debug.h.  mode 1: out[i] = sin_band(in[i]).
+struct DkNanCol {  // a coordinate column that is NaN everywhere: prox_a answers NaN iff it fell back to the sine form
+  __device__ double operator[](uint32_t) const { return __builtin_nan(""); }
+};
+__global__ __launch_bounds__(256) void distance_key_test_kernel(const double* __restrict__ in, const double* __restrict__ geo,
+                                                               uint32_t n, uint32_t mode, double* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (mode == 1u) {
+    if (i < n) out[i] = sin_band(in[i]);
+    return;
+  }
+  const uint32_t j = i < n ? i : 0u, k = n + j;  // (every lane takes part: candidate_key ballots)
+  const double *lat = in, *lon = in + 2u * (size_t)n, *cs = geo, *ux = cs + 2u * (size_t)n, *uy = ux + 2u * (size_t)n,
+               *uz = uy + 2u * (size_t)n;
+  const uint32_t slot = (uint32_t)in[4u * (size_t)n + j];
+  const SeedGeo sg = {lat[j], lon[j], cs[j], ux[j], uy[j], uz[j]};
+  const double h = hav_a(sg.lat, sg.lon, sg.cos, lat[k], lon[k], cs[k]);
+  const double pa = prox_a(sg, ux[k], uy[k], uz[k], lat, lon, cs, k);
+  const double pn = prox_a(sg, ux[k], uy[k], uz[k], DkNanCol{}, DkNanCol{}, DkNanCol{}, k);
+  // candidate_key with the candidate's columns based at it (t = 0) and no slot bits: the unpacked key, at another site
+  CarveArgs p = {};
+  p.cc_lat = (double*)lat + k;
+  p.cc_lon = (double*)lon + k;
+  p.cc_cos = (double*)cs + k;
+  NearRow q{};
+  const uint64_t ck = candidate_key(p, sg, 0u, ux[k], uy[k], uz[k], 1u, 0u, true, true, 0u, q);
+  if (i >= n) return;
+  double* o = out + (size_t)i * PM_DK_WORDS;
+  o[0] = sin_band((lat[k] - lat[j]) * PM_RAD * 0.5);
+  o[1] = sin_band((lon[k] - lon[j]) * PM_RAD * 0.5);
+  o[2] = cs[j], o[3] = ux[j], o[4] = uy[j], o[5] = uz[j];
+  o[6] = cs[k], o[7] = ux[k], o[8] = uy[k], o[9] = uz[k];
+  o[10] = h;
+  o[11] = pa;
+  o[12] = pn == pn ? 1.0 : 0.0;
+  o[13] = __longlong_as_double((long long)ck);
+  const uint32_t widths[3] = {PM_CARVE_SLOT_BITS, PM_CARVE_SLOT_BITS_BIG, PM_CARVE_SLOT_BITS_MEM};
+#pragma unroll
+  for (uint32_t w = 0; w < 3u; ++w) {
+    const uint32_t sl = slot & ((1u << widths[w]) - 1u);
+    o[14 + w] = __longlong_as_double((long long)pack_key((uint64_t)__double_as_longlong(pa), sl, widths[w]));
+    o[17 + w] = __longlong_as_double((long long)pack_key((uint64_t)__double_as_longlong(h), sl, widths[w]));
+  }
 }

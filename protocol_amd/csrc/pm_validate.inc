@@ -109,7 +109,7 @@ struct BlockRed {
 // exact to 1e-32) — those are two of every five pairs of a world-wide swarm, and the OCML path they used to take
 // (argument reduction with a table in memory) cost a wave more than everything else in a step of stream_small or a
 // sweep of carve_exact_step.  Only what is no difference of two longitudes still goes there.  The certificate band
-// (2^-35) is four orders of magnitude wider than this error.
+// (2^-36) is four orders of magnitude wider than this error.
 __device__ __forceinline__ double sin_band(double x) {
   double ax = fabs(x);
   if (ax > 1.5707963267948966) {
@@ -142,9 +142,11 @@ __device__ __forceinline__ double hav_a(double lat1, double lon1, double cos1, d
 // The proposer's Haversine term.  a = sin^2(dphi/2) + cos cos sin^2(dlam/2) is, exactly, a quarter of the squared
 // chord between the two unit vectors: a = |u1 - u2|^2 / 4 — three subtractions, a multiply and two fma instead of
 // two sine polynomials.  The unit vectors carry an absolute error of ~2e-16 per component, so the chord form has a
-// relative error of ~7e-16 / sqrt(a): under 1e-12 — a fifteenth of the certificate band (2^-36) — for a >=
-// PM_A_CHORD_MIN (about 10 km), and that is where it is used; nearer candidates (rare: a handful per seed) take the
-// sine form, whose error is independent of the distance.  Every path of the proposer goes through this one
+// relative error of ~6e-16 / sqrt(a) against the reference's a when the two longitudes lie less than 180 degrees apart.
+// The long way round the reference's own fl(fl(lon2 - lon1) * RAD) rounds by up to ~9e-16 radians, which the chord
+// never sees, and the error grows to ~1.3e-15 / sqrt(a) (measured; 2e-15 / sqrt(a) is the bound asserted).  That is
+// within an eighth of the certificate band (2^-36) for a >= PM_A_CHORD_MIN (about 14.5 km), and that is where it is used;
+// nearer candidates (rare: a handful per seed) take the sine form, whose error is independent of the distance.  Every path of the proposer goes through this one
 // function, so a candidate's key is the same bit pattern wherever it is computed.
 struct SeedGeo {
   double lat, lon, cos, ux, uy, uz;

@@ -625,6 +625,50 @@ class Engine:
                                       rows.ctypes.data, mism))
         return int(mism[0]), int(mism[1]), rows
 
+    def debug_distance_keys(self, lat1, lon1, lat2, lon2, slots=None):
+        """test hook (include/pm_engine_debug.h): the carve's distance key of the pairs (lat1, lon1) - (lat2, lon2) through the
+        device functions the carve runs -> dict of f64 columns (sin_dlat, sin_dlon, cos1, u1[n, 3], cos2, u2[n, 3], hav_a,
+        prox_a, candidate_key) + chord (bool: prox_a took the chord form), packed_prox / packed_hav (u64[n, 3]: the key
+        packed with the slot at the library's three slot widths)"""
+        import numpy as np
+        L = lib()
+        n = len(lat1)
+        if slots is None:
+            slots = np.zeros(n)
+        inp = np.concatenate([np.asarray(lat1, np.float64), np.asarray(lat2, np.float64), np.asarray(lon1, np.float64),
+                              np.asarray(lon2, np.float64), np.asarray(slots, np.float64)])
+        assert inp.size == 5 * n
+        out = np.zeros((n, 20), dtype=np.float64)
+        L.pm_debug_distance_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pm_debug_distance_keys.restype = C.c_int32
+        check(L.pm_debug_distance_keys(self._h, inp.ctypes.data, n, 0, out.ctypes.data))
+        bits = out.view(np.uint64)
+        return {"sin_dlat": out[:, 0].copy(), "sin_dlon": out[:, 1].copy(), "cos1": out[:, 2].copy(), "u1": out[:, 3:6].copy(),
+                "cos2": out[:, 6].copy(), "u2": out[:, 7:10].copy(), "hav_a": out[:, 10].copy(), "prox_a": out[:, 11].copy(),
+                "chord": out[:, 12] == 1.0, "candidate_key": out[:, 13].copy(), "packed_prox": bits[:, 14:17].copy(),
+                "packed_hav": bits[:, 17:20].copy()}
+
+    def debug_sin_band(self, x):
+        """test hook (include/pm_engine_debug.h): the carve's sine, sin_band, on the device at each x"""
+        import numpy as np
+        L = lib()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros(x.size, dtype=np.float64)
+        L.pm_debug_distance_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pm_debug_distance_keys.restype = C.c_int32
+        check(L.pm_debug_distance_keys(self._h, x.ctypes.data, x.size, 1, out.ctypes.data))
+        return out
+
+    def debug_key_geometry(self) -> dict:
+        """the library's key constants (include/pm_engine_debug.h, pm_debug_distance_keys mode 2)"""
+        L = lib()
+        out = (C.c_double * 8)()
+        L.pm_debug_distance_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pm_debug_distance_keys.restype = C.c_int32
+        check(L.pm_debug_distance_keys(self._h, None, 0, 2, out))
+        return {"chord_min": out[0], "a_max_safe": out[1], "bands": (out[2], out[3], out[4]),
+                "slot_bits": (int(out[5]), int(out[6]), int(out[7]))}
+
     def debug_carve_counters(self) -> dict:
         """how the last carve went (pm_internal.h, pm_debug_carve_prof words 32..45): how its validation launches ended,
         and what the proposer's spatial index did"""
