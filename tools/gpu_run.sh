@@ -21,7 +21,7 @@
 #   pipeline[:<args>]        a ticket's way through the streaming carve on one clock (prebuilt PM_ROW_REC library, tools/pipeline_probe.py)
 #   host                     PM_TRACE_HOST marks of a cold match and of churn ticks + the rocprofv3 kernel timeline of a match
 #   profiles:<rNN>           tools/collect_profiles.py <rNN>: kernel statistics, PMC passes, bench line -> gpurun_out/<rNN>/
-#   fuzz[:<swarms>[:<seed>]] tools/parity_fuzz.py (engine against oracle on random swarms)
+#   fuzz[:<swarms>[:<seed>[:<kind>,<kind>]]]  tools/parity_fuzz.py (engine against oracle on random swarms; all kinds unless named)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -134,8 +134,8 @@ PY
       timeout 1200 python tools/collect_profiles.py "$arg" > "$out/${n}_collect.log" 2>&1; echo "collect rc=$?"
       tail -3 "$out/${n}_collect.log" | cut -c1-600 ;;
     fuzz)
-      swarms=${arg%%:*}; seed=""; [ "$arg" != "$swarms" ] && seed=${arg#*:}
-      timeout 3000 python tools/parity_fuzz.py ${swarms:+--swarms $swarms} ${seed:+--seed $seed} > "$out/${n}_fuzz.txt" 2>&1; echo "fuzz rc=$?"
+      IFS=: read -r swarms seed kinds <<< "$arg"
+      timeout 3000 python tools/parity_fuzz.py ${swarms:+--swarms $swarms} ${seed:+--seed $seed} ${kinds:+--kinds $kinds} > "$out/${n}_fuzz.txt" 2>&1; echo "fuzz rc=$?"
       tail -15 "$out/${n}_fuzz.txt" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;

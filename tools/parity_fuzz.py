@@ -15,6 +15,9 @@ aim at where such an argument breaks — candidates that tie or nearly tie aroun
   ring         nodes on circles around a centre (equal great-circle distance up to rounding) + the centre's crowd
   wide         configurations with max_group_size 64..200 (more than a row holds: exact steps) and 65..128-candidate lists
   solos        a (1, 1) configuration over a large part of the swarm, then merging enabled (the merge pass's rules)
+  merge_rules  every node a solo group, then one to three merge configurations with min 1..8 and max up to 200 (a partial
+               proximity batch below min is thrown away and refilled first-come; the exact step's wide rounds), the located
+               share drawn from none / one / 1 % / 30 % / all, solos that hold tasks or not (tests/test_gpu_merge_rules.py)
   unlocated    most nodes without a location (first-come tails, seeds without location)
 
 A third of the swarms run with every n-th step forced through the exact host path (debug_uncertain_every).
@@ -37,7 +40,7 @@ from oracle import oracle_ffi as orc  # noqa: E402
 from protocol_amd import engine as E, host  # noqa: E402
 from protocol_amd.swarm import Stream, make_swarm  # noqa: E402
 
-KINDS = ["plain", "mirror", "near_mirror", "ulp", "fine_grid", "ring", "wide", "solos", "unlocated"]
+KINDS = ["plain", "mirror", "near_mirror", "ulp", "fine_grid", "ring", "wide", "solos", "unlocated", "merge_rules"]
 
 
 def set_configs(sw, configs):
@@ -78,6 +81,21 @@ def generate(kind, seed, max_w):
     if kind == "solos":
         sw = set_configs(sw, [("solo", 1, 1, "gpu:count=1"), ("merge-into", 2, int(rng.integers(2, 9)), "gpu:count=1"),
                               ("rest", 2, 4, None)])
+        return sw
+    if kind == "merge_rules":
+        configs = [("solo", 1, 1, None)]
+        for k, req in enumerate([None, "gpu:count=1", "gpu:model=h100,a100"][:int(rng.integers(1, 4))]):
+            mn = int(rng.integers(1, 9))
+            mx = max(mn, int(rng.choice([mn, 8, 16, 63, 64, 70, 200])))
+            configs.append((f"m{k}", mn, mx, req))
+        sw = set_configs(sw, configs)
+        share = rng.choice([0.0, -1.0, 0.01, 0.30, 1.0])                  # (-1: exactly one located node)
+        sw.has_loc[:] = rng.random(W) < share
+        if share < 0.0:
+            sw.has_loc[int(rng.integers(0, W))] = True
+        # solos that hold tasks before the merge or not; with prefer_larger_groups = false a held task blocks a batch
+        sw.meta["hold_tasks"] = bool(rng.integers(0, 2))
+        sw.meta["policy"] = dict(prefer_larger=bool(rng.integers(0, 2)))
         return sw
     sw = set_configs(sw, size_configs(rng, wide=(kind == "wide")))
     sw.has_loc[:] = rng.random(W) < 0.95
@@ -122,19 +140,28 @@ def run_case(kind, seed, max_w):
     h = (seed * 2654435761) >> 11                          # (not seed % n: the kinds go round with the seed)
     every = (0, 0, 3, 0, 0, 7)[h % 6]                     # a third of the swarms with forced host steps
     nodes, cfgs, tasks, enabled = orc.from_swarm(sw)
-    merge = kind == "solos"
+    merge = kind in ("solos", "merge_rules")
     if merge:
         enabled_first = np.zeros(len(sw.configs), dtype=np.uint8)
         enabled_first[0] = 1
-    st = orc.State(nodes, cfgs, enabled=(enabled_first if merge else enabled), tasks=tasks, reference_shaped=False, group_id_seed=seed)
-    eng = E.Engine(group_id_seed=seed, debug_uncertain_every=every)
+    policy = sw.meta.get("policy", {})
+    hold = sw.meta.get("hold_tasks", kind == "solos")     # (a tick matches: the solo groups claim their tasks before the merge)
+    st = orc.State(nodes, cfgs, enabled=(enabled_first if merge else enabled), tasks=tasks, reference_shaped=False, group_id_seed=seed,
+                   **policy)
+    eng = E.Engine(group_id_seed=seed, debug_uncertain_every=every, **policy)
     host.load_swarm(eng, sw)
     t0 = time.perf_counter()
     if merge:                                             # solos first, then the merge pass with everything enabled
         eng.set_enabled_mask(1)
-        eng.tick()
+        if hold:
+            eng.tick()
+        else:
+            eng.form_groups()
         st.try_form_new_groups()
         st.try_merge_solo_groups()
+        if hold:
+            for w in range(sw.W):
+                st.get_task_for_node(w)
         eng.set_enabled_mask((1 << len(sw.configs)) - 1)
         st.set_enabled(np.ones(len(sw.configs), dtype=np.uint8))
     stats = eng.tick()
