@@ -43,7 +43,8 @@ extern "C" {
                             are PM_EINVAL (since round 5); pm_stats of a pm_tick / pm_tick_many: ms_publish is 0 (the claim publishes),
                             ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only;
                             + pm_adopt_groups / pm_group_id_state (restart and switch-over), + pm_explain_workers /
-                            pm_config_report / pm_task_report (diagnostics): compatible additions, the version stays 3 */
+                            pm_config_report / pm_task_report (diagnostics), + pm_group_spread / pm_config_spread /
+                            pm_force_regroup (group geography): compatible additions, the version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -399,6 +400,61 @@ int32_t pm_config_report(pm_engine*, pm_config_report_row* out, uint32_t cap, ui
  *   groups_allowed   live groups whose configuration the task's topologies allow
  * Any output may be NULL. */
 int32_t pm_task_report(pm_engine*, uint32_t* groups_running, uint32_t* workers_running, uint32_t* groups_allowed);
+
+/* ------------------------------------------------------------------ group geography (read-only reports + force-regroup)
+ * How tight the standing groups are, whatever formed them (carve, merge, adoption), and the route that dissolves the loose
+ * ones.  Two distances, both with the reference's formula (calculate_distance, node_groups/mod.rs:218-231): the DIAMETER,
+ * the largest distance between two located members, and the RING, the hops from each member to the one after it in
+ * BTreeSet<String> order, cyclically: the peer a worker is handed as NEXT_P2P_ADDRESS (scheduler_impl.rs:115-116,
+ * mod.rs:424-434).  Ring order: members ascending by addr_rank (the worker index when the column was NULL), ties by
+ * worker index.  A group of one has no hop; two located members have two (there and back: ring_km = 2 d).
+ *
+ * Distance: the term a of the pair in the sine form (the key the carve certifies), then
+ * d = 6371.0 * 2.0 * atan2(sqrt(a), sqrt(1.0 - a)) in f64.  DEVIATION: a > 1 is taken as 1 (the reference yields NaN
+ * there).  Members with bit-identical coordinates are at exactly 0.  The maximum over pairs is taken on a, of which d is a
+ * non-decreasing function; far_a, far_b is the lexicographically smallest (a, b) among the pairs at that maximum, hop_from
+ * the smallest worker index among the hops at longest_hop_km.
+ *
+ * "Located" is PM_W_HAS_LOC of the current flags column, status changes that have not gone up yet included.  The two
+ * reports leave the engine as they found it (no pending delta consumed, nothing compacted).  All three calls: PM_ESTATE
+ * inside a stepwise tick (dist_phase != 0) and before configurations and workers are uploaded. */
+typedef struct pm_group_spread_row {
+  uint32_t located;      /* members with PM_W_HAS_LOC */
+  uint32_t ring_hops;    /* hops i -> next(i) whose two ends are both located and distinct workers */
+  uint32_t far_a, far_b; /* worker indices, far_a < far_b, of a pair at diameter_km; PM_NONE both when located < 2 */
+  uint32_t hop_from;     /* worker whose hop to its next member is longest_hop_km; PM_NONE when ring_hops == 0 */
+  uint32_t _pad;
+  double diameter_km;    /* max pairwise distance of located members; 0 when located < 2 */
+  double ring_km;        /* sum of the measured hops */
+  double longest_hop_km;
+} pm_group_spread_row;   /* 48 B */
+/* One row per live group, in the slot order pm_get_groups would give now (the list is not compacted).  *n_groups = the
+ * number of live groups always; cap < n_groups: PM_ERANGE, nothing written (out may be NULL then). */
+int32_t pm_group_spread(pm_engine*, pm_group_spread_row* out, uint32_t cap, uint32_t* n_groups);
+
+#define PM_SPREAD_BUCKETS 5 /* diameter < 10, < 100, < 1000, < 5000, >= 5000 km */
+static const double PM_SPREAD_EDGES_KM[PM_SPREAD_BUCKETS - 1] = {10.0, 100.0, 1000.0, 5000.0};
+typedef struct pm_config_spread_row {
+  uint32_t groups, measured;         /* live groups; of them with located >= 2 */
+  uint32_t hist[PM_SPREAD_BUCKETS];  /* measured groups by diameter */
+  uint32_t _pad;
+  double max_diameter_km, max_hop_km;
+  uint64_t sum_diameter_m, sum_ring_m; /* sums of llrint(km * 1000.0) per group: integers, so order-independent */
+} pm_config_spread_row;
+/* One row per configuration (pm_set_configs row order), size query as pm_config_report. */
+int32_t pm_config_spread(pm_engine*, pm_config_spread_row* out, uint32_t cap, uint32_t* n_cfgs);
+
+/* POST /groups/force-regroup (api/routes/groups.rs:319-380) with a selection.  PM_REGROUP_ALL is the route: every live
+ * group of `config` is dissolved, located or not; threshold_km is ignored.  PM_REGROUP_DIAMETER: groups with located >= 2
+ * and diameter_km >= threshold_km; PM_REGROUP_LONGEST_HOP: groups with ring_hops >= 1 and longest_hop_km >= threshold_km
+ * (the values pm_group_spread would report now).  The selected groups are dissolved in get_all_groups order — ascending
+ * "{:x}" text of the id, compared as a string ("10" < "9"; mod.rs:1040) — each exactly as pm_dissolve_group_by_id does
+ * it: the published rows read "no group" before the call returns, one PM_GROUP_DESTROYED per group in that order, the
+ * claimed task released.  *dissolved_groups / *affected_workers: the route's dissolved_groups / affected_nodes (either
+ * may be NULL).  config >= n_cfgs: PM_ERANGE; an unknown metric, or a NaN or negative threshold with a metric: PM_EINVAL. */
+enum { PM_REGROUP_ALL = 0, PM_REGROUP_DIAMETER = 1, PM_REGROUP_LONGEST_HOP = 2 };
+int32_t pm_force_regroup(pm_engine*, uint32_t config, uint32_t metric, double threshold_km, uint32_t* dissolved_groups,
+                         uint32_t* affected_workers);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

@@ -122,6 +122,24 @@ struct ReportArgs {
   uint32_t *running, *workers, *allowed;  // pm_task_report, T entries each (running / workers zeroed beforehand)
 };
 
+// pm_group_spread / pm_config_spread (pm_spread.inc).  Output row k is the k-th live group; it reads slot slot_of_row[k]
+// of the group arrays (the device mirror in place, or a dense scratch copy).  `small` / `big` list the rows of groups of
+// at most 64 / more than 64 members.
+struct SpreadArgs {
+  const uint32_t *g_n, *g_off, *members, *slot_of_row, *small, *big;
+  uint32_t n_small, n_big, W;
+  const uint32_t *flags, *addr_rank;  // flags: the current host column
+  const double *lat, *lon, *coslat;
+  pm_group_spread_row* out;
+};
+// one configuration's accumulators of config_spread_kernel
+enum : uint32_t { SPC_GROUPS = 0, SPC_MEASURED = 1, SPC_HIST = 2, SPC_N = 2 + PM_SPREAD_BUCKETS, SPC_STRIDE = 8 };
+enum : uint32_t { SPV_MAX_DIAMETER = 0, SPV_MAX_HOP = 1, SPV_SUM_DIAMETER = 2, SPV_SUM_RING = 3 };
+struct SpreadCfgAcc {
+  uint32_t cnt[SPC_STRIDE];
+  unsigned long long v[4];
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -353,6 +371,10 @@ void launch_compat(const CompatArgs& a, hipStream_t s);
 void launch_explain(const CompatArgs& p, const uint32_t* rows, uint32_t n, uint32_t stride, uint32_t* why_out, hipStream_t s);
 void launch_config_report(const ReportArgs& a, uint32_t max_blocks, hipStream_t s);
 void launch_task_report(const ReportArgs& a, uint32_t max_blocks, hipStream_t s);
+// group geography (pm_spread.inc)
+void launch_group_spread(const SpreadArgs& a, hipStream_t s);
+void launch_config_spread(const pm_group_spread_row* rows, const uint32_t* row_cfg, uint32_t n_rows, uint32_t n_cfgs,
+                          SpreadCfgAcc* out, uint32_t max_blocks, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

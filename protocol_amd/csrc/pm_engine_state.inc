@@ -192,6 +192,10 @@ struct pm_engine {
   // ---- diagnostics scratch (pm_engine_report.inc): the reports read the engine's tables and write only these
   DevBuf<uint32_t> d_rep_rows, d_rep_why, d_rep_flags, d_rep_live, d_rep_g, d_rep_tprefix, d_rep_cnt, d_rep_task;
   DevBuf<int32_t> d_rep_gof;
+  // ... of the group geography reports (pm_engine_spread.inc)
+  DevBuf<uint32_t> d_spr_idx;
+  DevBuf<pm_group_spread_row> d_spr_rows;
+  DevBuf<SpreadCfgAcc> d_spr_acc;
 
   // ---- multi-GPU (pm_dist_*): this engine is rank `dist_rank` of `dist_world`, every rank holds the whole swarm
   uint32_t dist_rank = 0, dist_world = 1;

@@ -8,6 +8,8 @@
 //   newest_kernel        orchestrator/src/plugins/newest_task/mod.rs:8-19
 //   explain_kernel,      the same clauses as compat_kernel, as reason codes, and the read-only reports
 //   *_report_kernel      (pm_report.inc)
+//   group_spread_*,      mod.rs:218-231 (calculate_distance) over the members of every live group: diameter and
+//   config_spread_kernel the NEXT_P2P_ADDRESS ring (scheduler_impl.rs:115-116) (pm_spread.inc)
 //   carve_kernel         orchestrator/src/plugins/node_groups/mod.rs:478-628 (try_form_new_groups)
 //                        with :218-255 (Haversine proximity) and, in MERGE mode, the selection half
 //                        of :752-860 (attempt_group_merge)
@@ -780,5 +782,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_stream.inc"        // the streaming carve (carve_variant 0): one launch per pass
 
 #include "pm_report.inc"        // diagnostics: reason codes, the config and task reports, their launchers
+#include "pm_spread.inc"        // group geography: per-group and per-configuration spread, their launchers
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

@@ -41,6 +41,16 @@ config_report_dt = np.dtype([("enabled", "<u4"), ("eligible_meets", "<u4"), ("id
 # reason codes (PM_WHY_*, first failing clause of ComputeSpecs::meets) and worker states (PM_WS_*)
 WHY_NAMES = ["ok", "no_specs", "cpu", "ram", "storage", "gpu_none", "gpu_count", "gpu_model", "gpu_mem", "gpu_total"]
 WS_IDLE, WS_IN_GROUP, WS_UNHEALTHY, WS_NO_P2P = 0, 1, 2, 3
+# pm_group_spread_row / pm_config_spread_row (include/pm_engine.h): group geography
+group_spread_dt = np.dtype([("located", "<u4"), ("ring_hops", "<u4"), ("far_a", "<u4"), ("far_b", "<u4"), ("hop_from", "<u4"),
+                            ("_pad", "<u4"), ("diameter_km", "<f8"), ("ring_km", "<f8"), ("longest_hop_km", "<f8")])
+SPREAD_BUCKETS = 5
+SPREAD_EDGES_KM = (10.0, 100.0, 1000.0, 5000.0)  # PM_SPREAD_EDGES_KM
+config_spread_dt = np.dtype([("groups", "<u4"), ("measured", "<u4"), ("hist", "<u4", (SPREAD_BUCKETS,)), ("_pad", "<u4"),
+                             ("max_diameter_km", "<f8"), ("max_hop_km", "<f8"), ("sum_diameter_m", "<u8"),
+                             ("sum_ring_m", "<u8")])
+assert group_spread_dt.itemsize == 48 and config_spread_dt.itemsize == 64
+REGROUP_ALL, REGROUP_DIAMETER, REGROUP_LONGEST_HOP = 0, 1, 2
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -107,6 +117,7 @@ EXPORTS = [
     "pm_dissolve_group_by_id", "pm_get_group_by_id", "pm_get_group_of_worker", "pm_host_to_lowercase",
     "pm_adopt_groups", "pm_group_id_state",
     "pm_explain_workers", "pm_config_report", "pm_task_report",
+    "pm_group_spread", "pm_config_spread", "pm_force_regroup",
 ]
 
 _lib = None
@@ -175,6 +186,9 @@ def lib() -> C.CDLL:
         L.pm_explain_workers.argtypes = [vp, vp, u32, vp, vp]
         L.pm_config_report.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_task_report.argtypes = [vp, vp, vp, vp]
+        L.pm_group_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_config_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_force_regroup.argtypes = [vp, u32, u32, C.c_double, C.POINTER(u32), C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -459,6 +473,31 @@ class Engine:
         outs = [np.zeros(self.T, dtype=np.uint32) for _ in range(3)]
         check(lib().pm_task_report(self._h, *[o.ctypes.data if self.T else None for o in outs]))
         return tuple(outs)
+
+    # ---- group geography (read-only reports) and the force-regroup route
+    def group_spread(self) -> np.ndarray:
+        """pm_group_spread -> one group_spread_dt record per live group, in the slot order get_groups would give now"""
+        n = C.c_uint32(0)
+        rc = lib().pm_group_spread(self._h, None, 0, C.byref(n))
+        if rc != -5:  # PM_ERANGE: the size query
+            check(rc)
+        out = np.zeros(n.value, dtype=group_spread_dt)
+        if n.value:
+            check(lib().pm_group_spread(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
+
+    def config_spread(self) -> np.ndarray:
+        """pm_config_spread -> one config_spread_dt record per configuration (pm_set_configs row order)"""
+        out = np.zeros(self.C, dtype=config_spread_dt)
+        n = C.c_uint32(0)
+        check(lib().pm_config_spread(self._h, out.ctypes.data if self.C else None, self.C, C.byref(n)))
+        return out[:n.value]
+
+    def force_regroup(self, config, metric=0, threshold_km=0.0):
+        """pm_force_regroup -> (dissolved_groups, affected_workers)"""
+        g, w = C.c_uint32(0), C.c_uint32(0)
+        check(lib().pm_force_regroup(self._h, int(config), int(metric), float(threshold_km), C.byref(g), C.byref(w)))
+        return g.value, w.value
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

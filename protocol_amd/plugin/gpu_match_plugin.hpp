@@ -308,6 +308,33 @@ class GpuMatchPlugin : public SchedulerPlugin {
   static const char* why_name(uint32_t code);
   static const char* state_name(uint32_t state);
 
+  // ---- group geography (INTEGRATION.md "Diagnostics"; gpu_match_spread.cpp): pm_group_spread / pm_config_spread by name, and
+  // POST /groups/force-regroup (api/routes/groups.rs:319-380) as one call with a selection.
+  struct GroupSpread {
+    uint32_t located = 0, ring_hops = 0;
+    std::string far_a, far_b, hop_from;  // node addresses; empty = none (fewer than two located nodes / no measured hop)
+    double diameter_km = 0.0, ring_km = 0.0, longest_hop_km = 0.0;
+  };
+  // every live group by id text ("{:x}")
+  std::unordered_map<std::string, GroupSpread> group_spread() const;
+  struct ConfigurationSpread {
+    std::string name;
+    uint32_t groups = 0, measured = 0;
+    std::array<uint32_t, PM_SPREAD_BUCKETS> hist{};  // measured groups by diameter (PM_SPREAD_EDGES_KM)
+    double max_diameter_km = 0.0, max_hop_km = 0.0;
+    uint64_t sum_diameter_m = 0, sum_ring_m = 0;
+  };
+  // constructor order
+  std::vector<ConfigurationSpread> configuration_spread() const;
+  struct ForceRegroupResult {
+    uint32_t dissolved_groups = 0, affected_nodes = 0;
+  };
+  // metric: PM_REGROUP_ALL (the route as the reference has it), PM_REGROUP_DIAMETER or PM_REGROUP_LONGEST_HOP with
+  // threshold_km.  nullopt: no configuration has this name (the route's 404).  Sends the destroyed webhooks, in
+  // get_all_groups order.
+  std::optional<ForceRegroupResult> force_regroup(const std::string& configuration_name, uint32_t metric = PM_REGROUP_ALL,
+                                                  double threshold_km = 0.0);
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());

@@ -122,6 +122,17 @@ int32_t pmx_explain_node(pmx_plugin*, const char* address, char* out, size_t cap
 int32_t pmx_configuration_report(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_task_report(pmx_plugin*, char* out, size_t cap, size_t* needed);
 
+/* ---- group geography (pm_plugin_spread_c.cpp): GpuMatchPlugin::group_spread / configuration_spread / force_regroup.
+ *   pmx_group_spread           one line per live group, by group id text: "<group id>\t<located>\t<ring_hops>\t<far_a>\t<far_b>\t
+ *                              <hop_from>\t<diameter_km>\t<ring_km>\t<longest_hop_km>" (addresses, "-" = none; %.17g)
+ *   pmx_configuration_spread   one line per configuration: "<name>\t<groups>\t<measured>\t<hist[0]>\t...\t<hist[4]>\t
+ *                              <max_diameter_km>\t<max_hop_km>\t<sum_diameter_m>\t<sum_ring_m>"
+ *   pmx_force_regroup          *found = 0: no configuration has this name (the route's 404), nothing done */
+int32_t pmx_group_spread(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_configuration_spread(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_force_regroup(pmx_plugin*, const char* configuration_name, uint32_t metric, double threshold_km, int32_t* found,
+                          uint32_t* dissolved_groups, uint32_t* affected_nodes);
+
 #ifdef __cplusplus
 }
 #endif

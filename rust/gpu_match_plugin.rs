@@ -167,6 +167,40 @@ pub struct pm_config_report_row {
     pub tasks_allowing: u32,
 }
 
+/// pm_group_spread_row (include/pm_engine.h)
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_group_spread_row {
+    pub located: u32,
+    pub ring_hops: u32,
+    pub far_a: u32,
+    pub far_b: u32,
+    pub hop_from: u32,
+    pub _pad: u32,
+    pub diameter_km: f64,
+    pub ring_km: f64,
+    pub longest_hop_km: f64,
+}
+
+/// pm_config_spread_row (include/pm_engine.h)
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_config_spread_row {
+    pub groups: u32,
+    pub measured: u32,
+    pub hist: [u32; 5],
+    pub _pad: u32,
+    pub max_diameter_km: f64,
+    pub max_hop_km: f64,
+    pub sum_diameter_m: u64,
+    pub sum_ring_m: u64,
+}
+
+/// pm_force_regroup's metrics (PM_REGROUP_*)
+pub const REGROUP_ALL: u32 = 0;
+pub const REGROUP_DIAMETER: u32 = 1;
+pub const REGROUP_LONGEST_HOP: u32 = 2;
+
 #[repr(C)]
 pub struct pm_group_vars {
     pub group_index: u32,
@@ -237,6 +271,10 @@ extern "C" {
     fn pm_explain_workers(e: *mut c_void, workers: *const u32, n: u32, why: *mut u8, state: *mut u32) -> i32;
     fn pm_config_report(e: *mut c_void, out: *mut pm_config_report_row, cap: u32, n_cfgs: *mut u32) -> i32;
     fn pm_task_report(e: *mut c_void, groups_running: *mut u32, workers_running: *mut u32, groups_allowed: *mut u32) -> i32;
+    fn pm_group_spread(e: *mut c_void, out: *mut pm_group_spread_row, cap: u32, n_groups: *mut u32) -> i32;
+    fn pm_config_spread(e: *mut c_void, out: *mut pm_config_spread_row, cap: u32, n_cfgs: *mut u32) -> i32;
+    fn pm_force_regroup(e: *mut c_void, config: u32, metric: u32, threshold_km: f64, dissolved_groups: *mut u32,
+                        affected_workers: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -418,6 +456,39 @@ pub struct TaskReport {
     pub groups_running: u32,                  // get_groups_for_task (mod.rs:1350-1386)
     pub workers_running: u32,                 // nodes_per_task (metrics/sync_service.rs:243-267)
     pub groups_allowed: u32,                  // live groups whose configuration the task's topologies allow
+}
+
+/// one group of group_spread (gpu_match_spread.cpp's GroupSpread)
+#[derive(Default, Debug, Clone)]
+pub struct GroupSpread {
+    pub located: u32,
+    pub ring_hops: u32,
+    pub far_a: String,                        // node addresses; empty = none
+    pub far_b: String,
+    pub hop_from: String,
+    pub diameter_km: f64,
+    pub ring_km: f64,
+    pub longest_hop_km: f64,
+}
+
+/// one row of configuration_spread (gpu_match_spread.cpp's ConfigurationSpread)
+#[derive(Default, Debug)]
+pub struct ConfigurationSpread {
+    pub name: String,
+    pub groups: u32,
+    pub measured: u32,
+    pub hist: [u32; 5],                       // measured groups by diameter: < 10, < 100, < 1000, < 5000, >= 5000 km
+    pub max_diameter_km: f64,
+    pub max_hop_km: f64,
+    pub sum_diameter_m: u64,
+    pub sum_ring_m: u64,
+}
+
+/// force_regroup's answer: the route's dissolved_groups / affected_nodes (api/routes/groups.rs:319-380)
+#[derive(Default, Debug, Clone, Copy, PartialEq, Eq)]
+pub struct ForceRegroupResult {
+    pub dissolved_groups: u32,
+    pub affected_nodes: u32,
 }
 
 /// reason names in PM_WHY_* order
@@ -1211,6 +1282,66 @@ impl GpuMatchPlugin {
         Ok(tasks.iter().enumerate().map(|(i, t)| (t.id.to_string(), TaskReport {
             groups_running: running[i], workers_running: workers[i], groups_allowed: allowed[i],
         })).collect())
+    }
+
+    // ---- group geography (INTEGRATION.md "Diagnostics"): pm_group_spread / pm_config_spread by name, and the force-regroup route
+
+    /// every live group by id text ("{:x}")
+    pub fn group_spread(&self) -> Result<HashMap<String, GroupSpread>> {
+        let t = self.nodes.read();           // (LOCK ORDER: nodes, the engine)
+        // the ids in slot order, then the rows in the same order; another thread's call in between changes the count: ask again
+        for _attempt in 0..8 {
+            let (_, groups, _) = self.snapshot_groups(t.rows.len(), false)?;
+            let mut rows = vec![pm_group_spread_row::default(); groups.len()];
+            let mut n = 0u32;
+            let rc = unsafe { pm_group_spread(self.engine, if rows.is_empty() { std::ptr::null_mut() } else { rows.as_mut_ptr() },
+                                              rows.len() as u32, &mut n) };
+            if rc == PM_ERANGE && n as usize != rows.len() { continue; }
+            check(rc)?;
+            if n as usize != rows.len() { continue; }
+            let addr = |w: u32| if w == PM_NONE { String::new() } else { t.address_strings[w as usize].clone() };
+            return Ok(groups.iter().zip(rows.iter()).map(|(g, r)| (format!("{:x}", g.id), GroupSpread {
+                located: r.located,
+                ring_hops: r.ring_hops,
+                far_a: addr(r.far_a),
+                far_b: addr(r.far_b),
+                hop_from: addr(r.hop_from),
+                diameter_km: r.diameter_km,
+                ring_km: r.ring_km,
+                longest_hop_km: r.longest_hop_km,
+            })).collect());
+        }
+        Err(anyhow!("pm_engine error {PM_ESTATE}: group_spread: the group list kept changing under the report"))
+    }
+
+    /// constructor order
+    pub fn configuration_spread(&self) -> Result<Vec<ConfigurationSpread>> {
+        let mut rows = vec![pm_config_spread_row::default(); self.config_names.len()];
+        let mut n = 0u32;
+        check(unsafe { pm_config_spread(self.engine, if rows.is_empty() { std::ptr::null_mut() } else { rows.as_mut_ptr() },
+                                        rows.len() as u32, &mut n) })?;
+        Ok(rows.iter().take(n as usize).enumerate().map(|(c, r)| ConfigurationSpread {
+            name: self.config_names[c].clone(),
+            groups: r.groups,
+            measured: r.measured,
+            hist: r.hist,
+            max_diameter_km: r.max_diameter_km,
+            max_hop_km: r.max_hop_km,
+            sum_diameter_m: r.sum_diameter_m,
+            sum_ring_m: r.sum_ring_m,
+        }).collect())
+    }
+
+    /// POST /groups/force-regroup (api/routes/groups.rs:319-380) with a selection: metric REGROUP_ALL is the route as the
+    /// reference has it, REGROUP_DIAMETER / REGROUP_LONGEST_HOP dissolve the groups at or above threshold_km.  None: no
+    /// configuration has this name (the route's 404).  Sends the destroyed webhooks, in get_all_groups order.
+    pub fn force_regroup(&self, configuration_name: &str, metric: u32, threshold_km: f64) -> Result<Option<ForceRegroupResult>> {
+        let Some(config) = self.config_names.iter().position(|n| n == configuration_name) else { return Ok(None) };
+        let mut out = ForceRegroupResult::default();
+        check(unsafe { pm_force_regroup(self.engine, config as u32, metric, threshold_km, &mut out.dissolved_groups,
+                                        &mut out.affected_nodes) })?;
+        if out.dissolved_groups != 0 { self.emit_group_webhooks()?; }                    // send_group_destroyed, mod.rs:1469-1481
+        Ok(Some(out))
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What the diagnostics reports cost (pm_explain_workers over every row, pm_config_report, pm_task_report) at BASELINE
+"""What the diagnostics reports cost (pm_explain_workers over every row, pm_config_report, pm_task_report, and the group
+geography reports pm_group_spread / pm_config_spread) at BASELINE
 configs[1] and configs[2] after a cold match, and beside them a churn tick's ms_compat (BASELINE configs[4], the stream of
 bench.py's `churn` sub-object).  Host wall clock per call, median of `reps` calls after one warm-up; prints one JSON line.
 usage: python tools/report_probe.py [reps]"""
@@ -36,7 +37,8 @@ for cfg in (1, 2):
     s = eng.tick()
     out[f"cfg{cfg}"] = dict(W=sw.W, T=sw.T, C=len(sw.configs), n_groups=s["n_groups"], ms_tick=round(s["ms_total"], 3),
                             ms_explain_all=timed(eng.explain_workers), ms_explain_one=timed(lambda: eng.explain_workers([0])),
-                            ms_config_report=timed(eng.config_report), ms_task_report=timed(eng.task_report))
+                            ms_config_report=timed(eng.config_report), ms_task_report=timed(eng.task_report),
+                            ms_group_spread=timed(eng.group_spread), ms_config_spread=timed(eng.config_spread))
     eng.close()
 
 # a churn tick's ms_compat, and the reports in the middle of the stream (status changes pending, the group list carrying
@@ -62,7 +64,8 @@ for t in range(4):
     eng.tasks_insert_front(*new_tasks[:3])
     if t == 3:
         out["churn_pending"] = dict(W=cs.W, ms_explain_all=timed(eng.explain_workers), ms_config_report=timed(eng.config_report),
-                                    ms_task_report=timed(eng.task_report))
+                                    ms_task_report=timed(eng.task_report), ms_group_spread=timed(eng.group_spread),
+                                    ms_config_spread=timed(eng.config_spread))
     s = eng.tick()
     compat.append(s["ms_compat"])
     tick.append(s["ms_total"])
