@@ -44,7 +44,8 @@ extern "C" {
                             ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only;
                             + pm_adopt_groups / pm_group_id_state (restart and switch-over), + pm_explain_workers /
                             pm_config_report / pm_task_report (diagnostics), + pm_group_spread / pm_config_spread /
-                            pm_force_regroup (group geography): compatible additions, the version stays 3 */
+                            pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates): compatible additions, the
+                            version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -455,6 +456,55 @@ int32_t pm_config_spread(pm_engine*, pm_config_spread_row* out, uint32_t cap, ui
 enum { PM_REGROUP_ALL = 0, PM_REGROUP_DIAMETER = 1, PM_REGROUP_LONGEST_HOP = 2 };
 int32_t pm_force_regroup(pm_engine*, uint32_t config, uint32_t metric, double threshold_km, uint32_t* dissolved_groups,
                          uint32_t* affected_workers);
+
+/* ---- nearest candidates (kernels in pm_near.inc) -------------------------------------------------------------------------------
+ * What is near a worker right now that could be grouped with it, and what the next carve would pick: sort_nodes_by_proximity
+ * (node_groups/mod.rs:234-255) applied to the carve's candidate set (:492-497, :511-515, :526-551), per query, on the GPU.
+ *
+ * CANDIDATES of a query (origin, config): the workers other than the origin that are in the pool and whose reason code for
+ * `config` is PM_WHY_OK (as pm_explain_workers computes it: the compat masks are not read).  The configuration need not be
+ * enabled.  Pools: PM_NEAR_IDLE — Healthy, with a p2p id, in no group: the next carve's candidates (mod.rs:492-497);
+ * PM_NEAR_ELIGIBLE — Healthy with a p2p id, grouped or not.  Flags and group membership are the host's current ones, status
+ * changes and dissolutions that have not gone up yet included, exactly as the reports read them.  An origin given by index
+ * may be any row < W — grouped, unhealthy, incompatible: it is the point to measure from, not a candidate.
+ *
+ * PM_NEAR_SEED as origin: the seed try_form_new_groups would take for the configuration now (mod.rs:526-530) — the
+ * lowest-index located candidate of the IDLE pool, or, when none of that pool's candidates is located, its lowest-index
+ * candidate — whatever `pool` the call was given.  No candidate in the IDLE pool: the row's origin is PM_NONE, n = candidates =
+ * located = 0.
+ *
+ * ORDER: the one sort_nodes_by_proximity gives the caller's list (a stable sort; unlocated nodes sit at f64::MAX).  With a
+ * located origin: the located candidates ascending by the pair's Haversine term a in the sine form (the key the carve
+ * certifies; DEVIATION, the spread report's: a > 1 is taken as 1), ties by worker index; the unlocated candidates follow in
+ * index order.  With an unlocated origin: all candidates in index order (the reference does not sort).  Non-finite
+ * coordinates are outside what the order pins; the call still terminates and returns distinct candidates.
+ *
+ * OUTPUT: rows[i] for query i; workers[i * k + j], j < rows[i].n, the j-th candidate in that order, and km[i * k + j] =
+ * 6371 * 2 * atan2(sqrt(a), sqrt(1 - a)) for a measured pair (origin and candidate both located), DBL_MAX otherwise.  The
+ * unused tail of a query's k slots reads PM_NONE / DBL_MAX.  km may be NULL.
+ *
+ * ERRORS: k == 0, k > PM_NEAR_MAX_K, n_q > PM_NEAR_MAX_QUERIES, an unknown pool, or NULL rows / workers with n_q > 0:
+ * PM_EINVAL.  An origin >= W that is not PM_NEAR_SEED, or config >= n_cfgs: PM_ERANGE.  Inside a stepwise tick, or before
+ * configurations and workers are uploaded: PM_ESTATE.  An error leaves the output buffers untouched.
+ *
+ * The call leaves the engine as it found it, as the reports do: no pending delta consumed, nothing compacted, no cache flag of
+ * the tick cleared; its scratch is its own. */
+enum { PM_NEAR_IDLE = 0,       /* pool: the next carve's candidates — Healthy, p2p id, in no group (mod.rs:492-497) */
+       PM_NEAR_ELIGIBLE = 1 }; /* pool: Healthy with a p2p id, grouped or not */
+#define PM_NEAR_SEED 0xFFFFFFFEu /* origin: the seed try_form_new_groups would take for the configuration now (mod.rs:526-530) */
+#define PM_NEAR_MAX_K 256u
+#define PM_NEAR_MAX_QUERIES 65535u /* the grid's y extent */
+typedef struct pm_near_query {
+  uint32_t origin, config; /* worker index or PM_NEAR_SEED; pm_set_configs row */
+} pm_near_query;
+typedef struct pm_near_row {
+  uint32_t origin;     /* the worker the list is measured from; PM_NONE: PM_NEAR_SEED found no candidate */
+  uint32_t n;          /* entries written for this query: min(k, candidates) */
+  uint32_t candidates; /* workers of the pool that meet the configuration, the origin excluded */
+  uint32_t located;    /* of them with PM_W_HAS_LOC */
+} pm_near_row;
+int32_t pm_nearest_workers(pm_engine*, const pm_near_query* q, uint32_t n_q, uint32_t pool, uint32_t k, pm_near_row* rows,
+                           uint32_t* workers /* n_q * k */, double* km /* n_q * k, may be NULL */);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

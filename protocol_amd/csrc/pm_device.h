@@ -140,6 +140,19 @@ struct SpreadCfgAcc {
   unsigned long long v[4];
 };
 
+// pm_nearest_workers (pm_near.inc): one workgroup per query.  Output of query q: rows[q], workers[q * k + j], km[q * k + j].
+static constexpr uint32_t PM_NEAR_CAP = 2u * PM_NEAR_MAX_K;  // a wave's selection buffer: max(2 k, k + 64) entries
+struct NearArgs {
+  CompatArgs c;                 // worker columns (flags: the current host column), configurations, alternatives, model rule
+  const int32_t* group_of;      // current (host truth): -1 = in no group
+  const double *lat, *lon, *coslat;
+  const pm_near_query* q;
+  uint32_t n_q, pool, k;
+  pm_near_row* rows;
+  uint32_t* workers;
+  double* km;
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -375,6 +388,8 @@ void launch_task_report(const ReportArgs& a, uint32_t max_blocks, hipStream_t s)
 void launch_group_spread(const SpreadArgs& a, hipStream_t s);
 void launch_config_spread(const pm_group_spread_row* rows, const uint32_t* row_cfg, uint32_t n_rows, uint32_t n_cfgs,
                           SpreadCfgAcc* out, uint32_t max_blocks, hipStream_t s);
+// nearest candidates (pm_near.inc)
+void launch_nearest(const NearArgs& a, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -218,6 +218,7 @@ void pm_engine_destroy(pm_engine* e) {
   e->d_rep_rows.release(); e->d_rep_why.release(); e->d_rep_flags.release(); e->d_rep_live.release(); e->d_rep_g.release();
   e->d_rep_tprefix.release(); e->d_rep_cnt.release(); e->d_rep_task.release(); e->d_rep_gof.release();
   e->d_spr_idx.release(); e->d_spr_rows.release(); e->d_spr_acc.release();
+  e->d_near_q.release(); e->d_near_out.release();
   delete e->form;
   delete e;
 }
@@ -281,6 +282,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_adopt.inc"
 #include "pm_engine_report.inc"
 #include "pm_engine_spread.inc"
+#include "pm_engine_near.inc"
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

@@ -196,6 +196,10 @@ struct pm_engine {
   DevBuf<uint32_t> d_spr_idx;
   DevBuf<pm_group_spread_row> d_spr_rows;
   DevBuf<SpreadCfgAcc> d_spr_acc;
+  // ... of pm_nearest_workers (pm_engine_near.inc): the queries; km, rows and workers of every query, packed
+  DevBuf<pm_near_query> d_near_q;
+  DevBuf<double> d_near_out;
+  std::vector<double> h_near_out;
 
   // ---- multi-GPU (pm_dist_*): this engine is rank `dist_rank` of `dist_world`, every rank holds the whole swarm
   uint32_t dist_rank = 0, dist_world = 1;

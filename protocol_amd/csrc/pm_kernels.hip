@@ -10,6 +10,8 @@
 //   *_report_kernel      (pm_report.inc)
 //   group_spread_*,      mod.rs:218-231 (calculate_distance) over the members of every live group: diameter and
 //   config_spread_kernel the NEXT_P2P_ADDRESS ring (scheduler_impl.rs:115-116) (pm_spread.inc)
+//   nearest_kernel       mod.rs:234-255 (sort_nodes_by_proximity) over the carve's candidate set (:492-497, :511-515,
+//                        :526-551), the first k per query (pm_near.inc)
 //   carve_kernel         orchestrator/src/plugins/node_groups/mod.rs:478-628 (try_form_new_groups)
 //                        with :218-255 (Haversine proximity) and, in MERGE mode, the selection half
 //                        of :752-860 (attempt_group_merge)
@@ -783,5 +785,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 
 #include "pm_report.inc"        // diagnostics: reason codes, the config and task reports, their launchers
 #include "pm_spread.inc"        // group geography: per-group and per-configuration spread, their launchers
+#include "pm_near.inc"          // nearest candidates: the per-query top-k selection, its launcher
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

@@ -51,6 +51,12 @@ config_spread_dt = np.dtype([("groups", "<u4"), ("measured", "<u4"), ("hist", "<
                              ("sum_ring_m", "<u8")])
 assert group_spread_dt.itemsize == 48 and config_spread_dt.itemsize == 64
 REGROUP_ALL, REGROUP_DIAMETER, REGROUP_LONGEST_HOP = 0, 1, 2
+# pm_near_query / pm_near_row (include/pm_engine.h): nearest candidates
+near_query_dt = np.dtype([("origin", "<u4"), ("config", "<u4")])
+near_row_dt = np.dtype([("origin", "<u4"), ("n", "<u4"), ("candidates", "<u4"), ("located", "<u4")])
+NEAR_IDLE, NEAR_ELIGIBLE = 0, 1
+NEAR_SEED = 0xFFFFFFFE
+NEAR_MAX_K, NEAR_MAX_QUERIES = 256, 65535
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -118,6 +124,7 @@ EXPORTS = [
     "pm_adopt_groups", "pm_group_id_state",
     "pm_explain_workers", "pm_config_report", "pm_task_report",
     "pm_group_spread", "pm_config_spread", "pm_force_regroup",
+    "pm_nearest_workers",
 ]
 
 _lib = None
@@ -189,6 +196,7 @@ def lib() -> C.CDLL:
         L.pm_group_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_config_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_force_regroup.argtypes = [vp, u32, u32, C.c_double, C.POINTER(u32), C.POINTER(u32)]
+        L.pm_nearest_workers.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -498,6 +506,26 @@ class Engine:
         g, w = C.c_uint32(0), C.c_uint32(0)
         check(lib().pm_force_regroup(self._h, int(config), int(metric), float(threshold_km), C.byref(g), C.byref(w)))
         return g.value, w.value
+
+    # ---- nearest candidates (read-only)
+    def nearest_workers(self, queries, pool=NEAR_IDLE, k=16, want_km=True):
+        """pm_nearest_workers -> (rows: near_row_dt [n_q], workers: uint32 [n_q, k], km: float64 [n_q, k] or None).
+        `queries`: (origin, config) pairs (or near_query_dt records); origin a worker index or NEAR_SEED.  Entries behind
+        rows[i]["n"] read PM_NONE / DBL_MAX."""
+        if isinstance(queries, np.ndarray) and queries.dtype == near_query_dt:
+            q = np.ascontiguousarray(queries)
+        else:
+            q = np.zeros(len(queries), dtype=near_query_dt)
+            for i, (o, c) in enumerate(queries):
+                q[i] = (int(o), int(c))
+        n, kk = len(q), max(int(k), 0)
+        rows = np.zeros(n, dtype=near_row_dt)
+        workers = np.full((n, kk), PM_NONE, dtype=np.uint32)
+        km = np.full((n, kk), np.finfo(np.float64).max, dtype=np.float64) if want_km else None
+        check(lib().pm_nearest_workers(self._h, q.ctypes.data if n else None, n, int(pool), int(k),
+                                       rows.ctypes.data if n else None, workers.ctypes.data if n else None,
+                                       km.ctypes.data if (want_km and n) else None))
+        return rows, workers, km
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

@@ -335,6 +335,21 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::optional<ForceRegroupResult> force_regroup(const std::string& configuration_name, uint32_t metric = PM_REGROUP_ALL,
                                                   double threshold_km = 0.0);
 
+  // ---- nearest candidates (INTEGRATION.md "Diagnostics: nearest candidates"; gpu_match_near.cpp): pm_nearest_workers by
+  // address and configuration name.
+  struct NearestNodes {
+    std::string origin;       // the node the list is measured from; empty: the seed rule found no candidate
+    uint32_t candidates = 0;  // nodes of the pool that meet the configuration, the origin excluded
+    uint32_t located = 0;     // of them with a location
+    std::vector<std::pair<std::string, double>> nodes;  // (address, km), nearest first; km = DBL_MAX: not measured
+  };
+  // address nullopt: from the seed try_form_new_groups would take for the configuration now (PM_NEAR_SEED).  pool:
+  // PM_NEAR_IDLE (the next carve's candidates) or PM_NEAR_ELIGIBLE (Healthy with a p2p id, grouped or not); k in
+  // [1, PM_NEAR_MAX_K].  nullopt: the node table does not hold the address.  std::invalid_argument: no configuration has
+  // this name.
+  std::optional<NearestNodes> nearest_nodes(const std::optional<std::string>& address, const std::string& configuration_name,
+                                            uint32_t pool = PM_NEAR_IDLE, uint32_t k = 16) const;
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());

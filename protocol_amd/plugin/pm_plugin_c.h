@@ -133,6 +133,13 @@ int32_t pmx_configuration_spread(pmx_plugin*, char* out, size_t cap, size_t* nee
 int32_t pmx_force_regroup(pmx_plugin*, const char* configuration_name, uint32_t metric, double threshold_km, int32_t* found,
                           uint32_t* dissolved_groups, uint32_t* affected_nodes);
 
+/* ---- nearest candidates (pm_plugin_near_c.cpp): GpuMatchPlugin::nearest_nodes.  address NULL: from the seed the next carve
+ * would take for the configuration.  *found = 0: the node table does not hold the address (empty text).  Else the first line
+ * is "origin\t<address, "-" = the seed rule found no candidate>\t<candidates>\t<located>", then one line "<address>\t<km>"
+ * per node, nearest first (%.17g; "-" = not measured).  An unknown configuration name is an error (-1). */
+int32_t pmx_nearest_nodes(pmx_plugin*, const char* address, const char* configuration_name, uint32_t pool, uint32_t k,
+                          int32_t* found, char* out, size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -196,6 +196,29 @@ pub struct pm_config_spread_row {
     pub sum_ring_m: u64,
 }
 
+/// pm_near_query / pm_near_row (include/pm_engine.h)
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_near_query {
+    pub origin: u32,
+    pub config: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_near_row {
+    pub origin: u32,
+    pub n: u32,
+    pub candidates: u32,
+    pub located: u32,
+}
+
+/// pm_nearest_workers' pools (PM_NEAR_*), the seed origin and the largest k
+pub const NEAR_IDLE: u32 = 0;
+pub const NEAR_ELIGIBLE: u32 = 1;
+pub const NEAR_SEED: u32 = 0xFFFF_FFFE;
+pub const NEAR_MAX_K: u32 = 256;
+
 /// pm_force_regroup's metrics (PM_REGROUP_*)
 pub const REGROUP_ALL: u32 = 0;
 pub const REGROUP_DIAMETER: u32 = 1;
@@ -275,6 +298,8 @@ extern "C" {
     fn pm_config_spread(e: *mut c_void, out: *mut pm_config_spread_row, cap: u32, n_cfgs: *mut u32) -> i32;
     fn pm_force_regroup(e: *mut c_void, config: u32, metric: u32, threshold_km: f64, dissolved_groups: *mut u32,
                         affected_workers: *mut u32) -> i32;
+    fn pm_nearest_workers(e: *mut c_void, q: *const pm_near_query, n_q: u32, pool: u32, k: u32, rows: *mut pm_near_row,
+                          workers: *mut u32, km: *mut f64) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -489,6 +514,15 @@ pub struct ConfigurationSpread {
 pub struct ForceRegroupResult {
     pub dissolved_groups: u32,
     pub affected_nodes: u32,
+}
+
+/// nearest_nodes' answer (gpu_match_near.cpp's NearestNodes)
+#[derive(Default, Debug, Clone)]
+pub struct NearestNodes {
+    pub origin: String,                       // the node the list is measured from; empty: the seed rule found no candidate
+    pub candidates: u32,                      // nodes of the pool that meet the configuration, the origin excluded
+    pub located: u32,                         // of them with a location
+    pub nodes: Vec<(String, f64)>,            // (address, km), nearest first; km = f64::MAX: not measured
 }
 
 /// reason names in PM_WHY_* order
@@ -1342,6 +1376,33 @@ impl GpuMatchPlugin {
                                         &mut out.affected_nodes) })?;
         if out.dissolved_groups != 0 { self.emit_group_webhooks()?; }                    // send_group_destroyed, mod.rs:1469-1481
         Ok(Some(out))
+    }
+
+    // ---- nearest candidates (INTEGRATION.md "Diagnostics: nearest candidates"): pm_nearest_workers by address and name
+
+    /// address None: from the seed try_form_new_groups would take for the configuration now (NEAR_SEED).  pool: NEAR_IDLE
+    /// (the next carve's candidates) or NEAR_ELIGIBLE; k in [1, NEAR_MAX_K].  Ok(None): the node table does not hold the
+    /// address.  Err: no configuration has this name.
+    pub fn nearest_nodes(&self, address: Option<&str>, configuration_name: &str, pool: u32, k: u32) -> Result<Option<NearestNodes>> {
+        let Some(config) = self.config_names.iter().position(|n| n == configuration_name) else {
+            return Err(anyhow!("nearest_nodes: no configuration is named '{configuration_name}'"));
+        };
+        let t = self.nodes.read();           // (LOCK ORDER: nodes, the engine)
+        let mut q = pm_near_query { origin: NEAR_SEED, config: config as u32 };
+        if let Some(a) = address {
+            let Some(row) = Self::row_of_address_text(&t, a) else { return Ok(None) };
+            q.origin = row;
+        }
+        let mut r = pm_near_row::default();
+        let mut workers = vec![0u32; k.max(1) as usize];     // (k == 0 is the engine's to refuse)
+        let mut km = vec![0f64; workers.len()];
+        check(unsafe { pm_nearest_workers(self.engine, &q, 1, pool, k, &mut r, workers.as_mut_ptr(), km.as_mut_ptr()) })?;
+        Ok(Some(NearestNodes {
+            origin: if r.origin == PM_NONE { String::new() } else { t.address_strings[r.origin as usize].clone() },
+            candidates: r.candidates,
+            located: r.located,
+            nodes: workers.iter().zip(km.iter()).take(r.n as usize).map(|(&w, &d)| (t.address_strings[w as usize].clone(), d)).collect(),
+        }))
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).

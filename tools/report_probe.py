@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""What the diagnostics reports cost (pm_explain_workers over every row, pm_config_report, pm_task_report, and the group
-geography reports pm_group_spread / pm_config_spread) at BASELINE
+"""What the diagnostics reports cost (pm_explain_workers over every row, pm_config_report, pm_task_report, the group
+geography reports pm_group_spread / pm_config_spread, and the nearest-candidates query pm_nearest_workers for 1 and 256
+queries at k = 64 and 256, with the bytes one query reads: 56 a worker row) at BASELINE
 configs[1] and configs[2] after a cold match, and beside them a churn tick's ms_compat (BASELINE configs[4], the stream of
 bench.py's `churn` sub-object).  Host wall clock per call, median of `reps` calls after one warm-up; prints one JSON line.
 usage: python tools/report_probe.py [reps]"""
@@ -29,6 +30,21 @@ def timed(fn):
     return round(float(np.median(ts)), 3)
 
 
+def nearest(eng, sw):
+    """pm_nearest_workers: one query from the seed, one and 256 by index (origins and configurations spread over the table)"""
+    C = len(sw.configs)
+    q256 = [(i * sw.W // 256, i % C) for i in range(256)]
+    q256 = np.array(q256, dtype=E.near_query_dt)
+    seed = np.array([(E.NEAR_SEED, 0)], dtype=E.near_query_dt)
+    r = dict(mb_read_per_query=round(56 * sw.W / 1e6, 2))
+    for k in (64, 256):
+        r[f"ms_seed_k{k}"] = timed(lambda: eng.nearest_workers(seed, E.NEAR_IDLE, k))
+        for pool, tag in ((E.NEAR_IDLE, "idle"), (E.NEAR_ELIGIBLE, "eligible")):
+            r[f"ms_q1_k{k}_{tag}"] = timed(lambda: eng.nearest_workers(q256[128:129], pool, k))
+            r[f"ms_q256_k{k}_{tag}"] = timed(lambda: eng.nearest_workers(q256, pool, k))
+    return r
+
+
 out = {}
 for cfg in (1, 2):
     sw = baseline_config(cfg, seed=1)
@@ -38,7 +54,8 @@ for cfg in (1, 2):
     out[f"cfg{cfg}"] = dict(W=sw.W, T=sw.T, C=len(sw.configs), n_groups=s["n_groups"], ms_tick=round(s["ms_total"], 3),
                             ms_explain_all=timed(eng.explain_workers), ms_explain_one=timed(lambda: eng.explain_workers([0])),
                             ms_config_report=timed(eng.config_report), ms_task_report=timed(eng.task_report),
-                            ms_group_spread=timed(eng.group_spread), ms_config_spread=timed(eng.config_spread))
+                            ms_group_spread=timed(eng.group_spread), ms_config_spread=timed(eng.config_spread),
+                            nearest=nearest(eng, sw))
     eng.close()
 
 # a churn tick's ms_compat, and the reports in the middle of the stream (status changes pending, the group list carrying
