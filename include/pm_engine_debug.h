@@ -21,8 +21,9 @@ extern "C" {
  * incremental state a long-running engine keeps, not the last carve's (engine.py debug_task_space;
  * tests/test_gpu_soak.py bounds it) — t_lo, t_cap (the task index space: the swept range is [t_lo, t_cap)), T (live
  * tasks), t_dead (tombstones inside the range), regrowths and compactions of the index space since creation, entries
- * of the host group list, its tombstones (dissolved, not yet compacted), retired snapshot buffers.  Copies
- * min(cap, 97) words. */
+ * of the host group list, its tombstones (dissolved, not yet compacted), retired snapshot buffers.  out[97]: the last
+ * carve's again — times the streaming carve dropped a configuration's outstanding tickets and issued them afresh
+ * (debug_carve_counters: stream_refreshes).  Copies min(cap, 98) words. */
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap);
 
 /* Timeline of the last streaming carve launch (PM_CARVE_PROF builds; otherwise *n = 0): up to cap events of two words

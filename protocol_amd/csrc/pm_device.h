@@ -38,7 +38,10 @@ static constexpr uint32_t PM_ROW_SAFE = 1u << 27;        // no listed Haversine 
 static constexpr uint32_t PM_ROW_TAIL_CLEAR = 1u << 28;  // the first unlisted candidate is beyond the band of the last entry
 static constexpr uint32_t PM_ROW_CLEAN = 1u << 29;       // no two entries within the band of each other at different sites
 static constexpr uint32_t PM_ROW_TAIL_OK = 1u << 30;     // everything unlisted within the band of the last entry sits at its site
-static constexpr uint32_t PM_ROW_COMPLETE = 1u << 31;    // the row lists every live candidate
+static constexpr uint32_t PM_ROW_COMPLETE = 1u << 31;    // the row lists every candidate that can be alive at its seed's turn: every live
+                                                         // one but (FORM) the located ones in front of the seed, which are in a group by
+                                                         // then — read at the seed's turn only (carve_fast_steps, carve_chain's second
+                                                         // look, the parkers' digest for it), never for another seed or another moment
 static constexpr uint32_t PM_PROP_RESERVE = 64;        // entries beyond max_group_size - 1: the proposer's register holds 64 sorted
                                                        // keys whatever K is, so every row is as long as a row can be (K = 63)
 static constexpr uint32_t PM_PROP_MAX_SEEDS = 16384;   // located slots that get a proposal per configuration

@@ -664,6 +664,7 @@ static int32_t form_finish(pm_engine* e, FormRun* r, uint32_t* n_formed, bool de
   e->carve_why[21] = st.slow_steps;
   e->carve_why[22] = st.stream_pre_used;
   e->carve_why[23] = st.stream_pre_lost;
+  e->carve_why[24] = st.stream_refreshes;
 #ifdef PM_BATCH_LOG
   e->blog.assign(st.blog, st.blog + 3 * std::min<uint32_t>(st.blog_n, 512u));
 #endif

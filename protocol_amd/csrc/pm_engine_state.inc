@@ -15,7 +15,7 @@ struct pm_engine {
   bool end_event_queued = false;  // this tick's ev[5] stands behind the claim already (the claim publishes: there is no copy phase behind it, and no ev[4])
   uint64_t tick_cand_sum = 0;
   unsigned long long carve_prof[64]{};
-  unsigned long long carve_why[24]{};  // CarveStatus::why of the last carve, its batches and void launches, the spatial
+  unsigned long long carve_why[25]{};  // CarveStatus::why of the last carve, its batches and void launches, the spatial
                                        // index, the streaming carve's counters
   uint32_t debug_mem_above = 0;  // pm_debug_mem_lists_above
   uint32_t debug_abort_after = 0;  // pm_debug_stream_abort_after

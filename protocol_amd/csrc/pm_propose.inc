@@ -361,6 +361,7 @@ __device__ __forceinline__ void tile_store(TileBuf& tb, uint32_t tid, const Tile
 __device__ __forceinline__ void tile_keys(const CarveArgs& p, const TileBuf& tb, uint32_t tile, uint32_t lane, uint32_t s,
                                           bool shared, uint32_t ssite, const SeedGeo& sg, uint32_t SB, uint64_t ulps,
                                           NearRow& q, uint32_t& n_mine) {
+  const bool form = UNI(p.mode) != CARVE_MODE_MERGE;
 #pragma unroll 1
   for (uint32_t h = 0; h < PROP_TILE / 256u; ++h) {
     double x[4], y[4], z[4];
@@ -380,10 +381,13 @@ __device__ __forceinline__ void tile_keys(const CarveArgs& p, const TileBuf& tb,
     for (uint32_t v = 0; v < 4u; ++v) {
       const uint32_t u = h * 4u + v, t = tile * PROP_TILE + u * 64u + lane;
       const bool located = (lwd[v] >> lane) & 1ull;
-      // candidates at the seed's own (shared) site are at distance 0 (key = their slot): the ones behind the seed
-      // head its row in slot order; the ones in front of it are dead by the time it is a seed (a live located slot
-      // in front of it would be the seed instead) and would only fill the row
-      const bool counts = ((aw[v] >> lane) & 1ull) && t != s && !(shared && located && si[v] == ssite && t < s);
+      // FORM: a located candidate in front of the seed is dead by the time it is a seed (a live located slot in front
+      // of it would be the seed instead, mod.rs:526-530) and would only fill the row — wherever it sits.  Location-less
+      // ones in front stay in: they sort behind every located one and may well be alive at the seed's turn.  MERGE
+      // keeps the rule for the seed's own (shared) site only, where candidates are at distance 0 (key = their slot)
+      // and the ones behind the seed head its row in slot order: a merge batch can be refused with its seed still in
+      // the list.
+      const bool counts = ((aw[v] >> lane) & 1ull) && t != s && !(located && t < s && (form || (shared && si[v] == ssite)));
       const double dx = x[v] - sg.ux, dy = y[v] - sg.uy, dz = z[v] - sg.uz;
       double a = 0.25 * fma(dx, dx, fma(dy, dy, dz * dz));
       // (see prox_a: the sine form below ~14.5 km.  A candidate at the seed's own site — identical coordinates — has the
@@ -532,7 +536,11 @@ __device__ __forceinline__ void cell_drain(const CarveArgs& p, uint32_t* wl, uin
 #pragma unroll
       for (uint32_t v = 0; v < NV; ++v) {
         if (!__ballot(in[v])) continue;
-        // (every indexed position has a location; the slots in front of the seed at its own shared site: see tile_keys)
+        // (every indexed position has a location; the slots in front of the seed at its own shared site: see tile_keys.
+        // The walk leaves out no other candidate in front of the seed, though none of them can be alive at its turn:
+        // a walk stops where its row's window closes, and with the few hundred candidates of the look-ahead window
+        // gone from around a late seed the rings go further out and give up twice as often — measured at 1M x 100k,
+        // 6.5 - 7.0 ms a match with this rule as it stands against 6.9 - 7.4 with the general one, DESIGN.md 4.2)
         const bool counts = in[v] && t[v] != s && !(shared && si[v] == ssite && t[v] < s);
         offer_candidate(p, sg, ssite, x[v], y[v], z[v], si[v], in[v] ? t[v] : 0u, true, counts, SB, ulps, q, n_mine);
       }
@@ -691,6 +699,7 @@ __device__ __forceinline__ void list_sweep_solo(const CarveArgs& p, uint32_t n_l
                                              const uint64_t* cfg64 = nullptr) {
   const auto alive = G((const uint64_t*)p.bits_scratch);
   const auto loc = G((const uint64_t*)p.bits_scratch) + p.bits_stride;
+  const bool form = UNI(p.mode) != CARVE_MODE_MERGE;  // (see tile_keys)
   for (uint32_t t0 = 0; t0 < n_list; t0 += 256u) {
     double x[4], y[4], z[4];
     uint32_t si[4];
@@ -711,7 +720,7 @@ __device__ __forceinline__ void list_sweep_solo(const CarveArgs& p, uint32_t n_l
     for (uint32_t v = 0; v < 4u; ++v) {
       const uint32_t t = t0 + v * 64u + lane;
       const bool located = (lw[v] >> lane) & 1ull;
-      const bool counts = ((aw[v] >> lane) & 1ull) && t != s && !(shared && located && si[v] == ssite && t < s);
+      const bool counts = ((aw[v] >> lane) & 1ull) && t != s && !(located && t < s && (form || (shared && si[v] == ssite)));
       offer_candidate(p, sg, ssite, x[v], y[v], z[v], si[v], counts ? t : 0u, located, counts, SB, ulps, q, n_mine);
     }
   }

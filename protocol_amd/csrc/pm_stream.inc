@@ -11,7 +11,9 @@
 //     ONE bitmap for the whole carve — `free`, p.bits_scratch: the positions no group holds yet — which its collector
 //     wave keeps a few commits behind the truth.  A copy that only ever lags is a superset of the truth at any later
 //     moment, and that is all a neighbour row needs (rows are validated against the live bitmap; a row made from a
-//     superset minus its dead entries is the reference's sorted remaining list, see carve_chain).
+//     superset minus its dead entries is the reference's sorted remaining list, see carve_chain).  The superset need
+//     not hold what is certainly dead at the seed's turn: the located candidates in front of the seed (a live one would
+//     be the seed instead) are masked out of a swept row before anything is fetched — stream_bitmap_sweep.
 //   * workgroup 0 is the validator (the same three-wave chain as the batch pipeline).  Its producer wave walks the
 //     candidate bitmap in front of the chain and hands every live located candidate a TICKET — an 8-byte granule
 //     {tag, position | configuration | how to make the row} in a ring — at most a look-ahead of `la` tickets in front
@@ -2144,6 +2146,7 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
   // columns were five, and a row is a chain of exactly these gathers
   const double* const pack = p.c_pack;
   const bool located_only = UNI(p.mode) == CARVE_MODE_MERGE;  // (read here, once: not inside the strides)
+  const bool form = !located_only;  // (FORM: no located candidate in front of the seed can be alive at its turn, see tile_keys)
   // The next batch's gathers are in flight while this one is evaluated; the evaluation stands in ONE place (it has the
   // sorting networks inline) and the batches change places in registers.
   struct Batch {
@@ -2179,7 +2182,7 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
       const bool located = pack_located(bt.rec[v]);
       ss[v] = pack_site(bt.rec[v]);
       // (merge pass: the neighbours of a seed are the LOCATED candidates only, mod.rs:792-804)
-      const bool counts = in && tv != s && !(shared && located && ss[v] == ssite && tv < s) && (located || !located_only);
+      const bool counts = in && tv != s && !(located && tv < s && (form || (shared && ss[v] == ssite))) && (located || !located_only);
 #ifdef PM_ROW_BENCH  // (2 — no key arithmetic: a key out of the position)
       if (g_rowb_mode & 2u) kk[v] = counts ? (((uint64_t)(tv * 2654435761u) << SB) | tv) : ~0ull;
       else
@@ -2254,11 +2257,23 @@ __device__ __forceinline__ bool stream_bitmap_sweep(const CarveArgs& p, const ui
   uint64_t bp_t = __builtin_amdgcn_s_memtime(), bp_pass = 0, bp_drain = 0;
   uint32_t bp_np = 0, bp_nd = 0;
 #endif
-  unsigned long long a_n = lane < lw ? (ld_ag(&freeg[lane]) & cfgb[lane]) : 0ull;  // (the next pass's words, one pass early)
+  // FORM: the located candidates in front of the seed are masked out right here — every one of them is in a group by
+  // the seed's turn (a live one would be the seed instead, mod.rs:526-530), so they take no place in the buffer, no
+  // gather and no key.  One more load per word up to the seed's; the words behind it are untouched.  (The merge pass
+  // keeps its candidates: a merge batch can be refused with its seed still in the list.)
+  const auto locg = G((const unsigned long long*)p.loc_g);
+  const uint32_t sw = UNI(p.mode) != CARVE_MODE_MERGE ? s >> 6 : 0u;  // words up to here have located positions in front of the seed
+  const unsigned long long s_below = UNI(p.mode) != CARVE_MODE_MERGE ? (1ull << (s & 63u)) - 1ull : 0ull;
+  auto word = [&](uint32_t j) -> unsigned long long {
+    if (j >= lw) return 0ull;
+    unsigned long long a = ld_ag(&freeg[j]) & cfgb[j];
+    if (j <= sw) a &= ~(locg[j] & (j < sw ? ~0ull : s_below));
+    return a;
+  };
+  unsigned long long a_n = word(lane);  // (the next pass's words, one pass early)
   for (uint32_t j0 = 0; j0 < lw; j0 += 64u) {
     unsigned long long a = a_n;
-    const uint32_t jn = j0 + 64u + lane;
-    a_n = jn < lw ? (ld_ag(&freeg[jn]) & cfgb[jn]) : 0ull;
+    a_n = word(j0 + 64u + lane);
     const uint32_t cw = (uint32_t)__popcll(a);
     const uint32_t incl = wave_incl_scan_u32(cw);
     uint32_t o = nb + incl - cw;

@@ -435,8 +435,10 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
     if (dbg_every && ((steps_before + c.steps + 1u) % dbg_every) == 0u) SLOW_RETURN(21);
 
     // ---- the seed's neighbour row: one packed key per lane, ascending.  Candidates with the seed's exact
-    // coordinates are at distance 0 and head the row in slot order (only those behind the seed are listed: a live one
-    // in front of it would have been the seed).
+    // coordinates are at distance 0 and head the row in slot order.  Of the located candidates only those behind the
+    // seed are listed (FORM; a swept row — a walk's leaves out the ones at the seed's own site only): a live one in front
+    // of it would have been the seed, so at this moment — the only one a row is read at — nothing is missing, and a
+    // row flagged complete lists everything that is alive.
     const size_t rbase = STREAM ? (size_t)(cur & (PM_STREAM_RQ - 1u)) * 64u : (size_t)prop_row_of(cur, world, rows_pr) * PM_PROP_ROW;
     uint32_t nk_word;
     if (STREAM) {  // (granule 0: the flags word under the ticket's tag — a row that never arrived does not carry it)
