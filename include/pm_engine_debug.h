@@ -27,7 +27,7 @@ extern "C" {
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap);
 
 /* Timeline of the last streaming carve launch (PM_CARVE_PROF builds; otherwise *n = 0): up to cap events of two words
- * {s_memtime, type | a << 8 | b << 32}; tools/stream_trace.py decodes them. */
+ * {s_memtime, type | a << 8 | b << 32} (STREAM_TRACE, csrc/pm_measure.inc, lists the types); tools/stream_trace.py decodes them. */
 int32_t pm_debug_stream_trace(pm_engine* e, unsigned long long* out, uint32_t cap, uint32_t* n);
 
 /* Test hook: candidate lists longer than n slots take the all-in-HBM carve path (carve_step_mem), which otherwise
@@ -63,7 +63,7 @@ int32_t pm_debug_hbm_triad(pm_engine* e, uint64_t n_doubles, uint32_t reps, doub
 /* A measuring build's (-DPM_ROW_REC) record of the last streaming launch's rows: eight words per ticket — the real-time
  * counter (100 MHz, one clock for all CUs; the validator's events of such a build carry the same) when the ticket was seen, when the first pass of the sweep was packed, when the first batch's keys were there, when the candidates
  * were through, when the row was finished, when it was stored; candidates evaluated | mode << 32; hardware id.  n_rows = 0 from
- * a product build. */
+ * a product build.  (These three records are written by PROP_REC_ROW, CHAIN_REC_* and PARK_REC_* of csrc/pm_measure.inc.) */
 int32_t pm_debug_row_records(pm_engine* e, unsigned long long* out, uint32_t cap_rows, uint32_t* n_rows);
 /* ... and the batches of steps its chain took up: four words each — the clock at the top of the chain's loop; first entry |
  * entries << 24 | live ones << 32 | commits so far << 40; the clock when the entries had been looked at; the clock behind the steps.

@@ -156,9 +156,7 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
         PROF_MARK(29);  // loop overhead
         c.n_list = carve_compact_count(p, red, n, cbit, p.alive_g);
         PROF_MARK(26);
-#ifdef PM_CARVE_PROF
-        if (tid == 0) G(p.status)->prof[30] += 1;
-#endif
+        PM_PROF(if (tid == 0) G(p.status)->prof[30] += 1;)
         if (c.n_list < c.min_s || c.n_list == 0) continue;  // mod.rs:517-519
         carve_compact_place(p, red, n, cbit, c.n_list, p.alive_g);
         PROF_MARK(27);

@@ -777,6 +777,7 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
   (void)best_key;
 }
 
+#include "pm_measure.inc"       // what the measuring builds add to the kernels below; nothing in the product build
 #include "pm_validate.inc"      // the validator's building blocks: LDS layout, the three-wave chain, exact steps
 #include "pm_propose.inc"       // neighbour rows: NearRow, the walk over the spatial index, carve_propose_kernel
 #include "pm_prep.inc"          // list preparation on the whole chip: candidate lists, the eligible list, the spatial index

@@ -42,9 +42,7 @@ __global__ __launch_bounds__(256) void carve_prep_count_kernel(const CarveArgs* 
     if (blockIdx.x == 0 && tid == 0) p.desc->planned = 0u;
     return;
   }
-#ifdef PM_BATCH_LOG
-  if (blockIdx.x == 0 && tid == 0) p.status->prof[5] = ~0ull;  // (earliest block start of the placement behind this)
-#endif
+  PM_BLOG(if (blockIdx.x == 0 && tid == 0) p.status->prof[5] = ~0ull;)  // (earliest block start of the placement behind this)
   // (one batch at a time: the plan is the carve's own state, the same in every block)
   const uint32_t ci0 = st->cur_ci;
   if (blockIdx.x == 0 && tid == 0) plan_batch(p);
@@ -85,10 +83,7 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   __shared__ uint32_t s_red[PREP_WAVES + 4];
   __shared__ uint32_t s_bits[PREP_WAVES][64];
-#ifdef PM_BATCH_LOG
-  const uint64_t pl_t0 = __builtin_amdgcn_s_memtime();
-  if (tid == 0) atomicMin((unsigned long long*)&p.status->prof[5], (unsigned long long)pl_t0);
-#endif
+  PM_BLOG(const uint64_t pl_t0 = PM_TICKS(); if (tid == 0) atomicMin((unsigned long long*)&p.status->prof[5], (unsigned long long)pl_t0);)
   const uint32_t n = st->n_eligible, n_words = (n + 63u) >> 6;
   const uint32_t total_available = D->total_available;
   // ---- the next configuration whose loop would be entered (mod.rs:505-519), the same in every block.  (Counts and
@@ -134,9 +129,7 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
     const uint32_t cnt = (uint32_t)__popcll(bal);
     if (lane == 0) s_red[PREP_WAVES + wave] = cnt;
     __syncthreads();
-#ifdef PM_BATCH_LOG
-    if (tid == 0) atomicAdd((unsigned long long*)&p.status->prof[14], (unsigned long long)(__builtin_amdgcn_s_memtime() - pl_t0));  // loads in
-#endif
+    PM_BLOG(if (tid == 0) atomicAdd((unsigned long long*)&p.status->prof[14], (unsigned long long)(PM_TICKS() - pl_t0));)  // loads in
     uint32_t off = 0;
 #pragma unroll
     for (uint32_t w = 0; w < PREP_WAVES; ++w) off += s_red[w];
@@ -169,9 +162,7 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
     }
   }
   // ---- the block that finishes last completes the list and publishes it
-#ifdef PM_BATCH_LOG
-  if (tid == 0) atomicAdd((unsigned long long*)&p.status->prof[15], (unsigned long long)(__builtin_amdgcn_s_memtime() - pl_t0));  // stores issued
-#endif
+  PM_BLOG(if (tid == 0) atomicAdd((unsigned long long*)&p.status->prof[15], (unsigned long long)(PM_TICKS() - pl_t0));)  // stores issued
   // What the last block reads of the others is the slot loc bitmap, and that is written with device-scope atomics
   // only: they need no release, just to have been performed before this block's ticket is taken — which a wait for
   // the wave's outstanding memory operations gives (workgroup-scope fence: s_waitcnt, no cache maintenance).  The
@@ -179,29 +170,17 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
   // here writes the XCD's L2 back once per BLOCK: 25 of the 42 us this kernel took at 100 k positions.)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __syncthreads();
-#ifdef PM_BATCH_LOG
-  if (tid == 0) {  // this block, start to ticket: sum, max, count
-    const uint64_t dt = __builtin_amdgcn_s_memtime() - pl_t0;
-    atomicAdd((unsigned long long*)&p.status->prof[8], (unsigned long long)dt);
-    atomicMax((unsigned long long*)&p.status->prof[9], (unsigned long long)dt);
-    atomicAdd((unsigned long long*)&p.status->prof[10], 1ull);
-  }
-#endif
+  BLOG_BLOCK_TICKET(pl_t0);  // this block, start to ticket
   if (tid == 0) s_red[0] = atomicAdd(&p.prep_counts[PM_MAX_CONFIGS], 1u);
   __syncthreads();
   if (s_red[0] != gridDim.x - 1u) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (see what the other blocks' atomics wrote: invalidate, nothing to write back)
-#ifdef PM_BATCH_LOG
-  const uint64_t pl_t1 = __builtin_amdgcn_s_memtime();  // every block is through: the tail begins
-#endif
+  PM_BLOG(const uint64_t pl_t1 = PM_TICKS();)  // every block is through: the tail begins
   if (none) {
     if (tid == 0) {
       p.desc->ci = p.n_avail;
       p.desc->none = 1u;
-#ifdef PM_BATCH_LOG
-      const uint32_t k = p.status->blog_n++;
-      if (k < 512u) p.status->blog[3u * k] = p.status->blog[3u * k + 1u] = p.status->blog[3u * k + 2u] = 0u;
-#endif
+      BLOG_LINE_NONE();
     }
     return;
   }
@@ -238,20 +217,8 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
     d->cell_g = cell_g;
     d->valid = 1u;
     if (cell_g) p.status->pruned_batches += 1u;
-#ifdef PM_BATCH_LOG
-    {
-      const uint64_t pl_t2 = __builtin_amdgcn_s_memtime();
-      p.status->prof[11] += pl_t1 - p.status->prof[5];  // first block start -> last block through
-      p.status->prof[12] += pl_t2 - pl_t1;              // the tail
-      p.status->prof[13] += 1ull;
-    }
-    const uint32_t k = p.status->blog_n++;
-    if (k < 512u) {
-      p.status->blog[3u * k] = n_list;
-      p.status->blog[3u * k + 1u] = n_seeds;
-      p.status->blog[3u * k + 2u] = cell_g;
-    }
-#endif
+    BLOG_PLACED(pl_t1);
+    BLOG_LINE(n_list, n_seeds, cell_g);
   }
 }
 

@@ -16,26 +16,8 @@ struct NearRow {
   // there an unlisted candidate within the band of the last entry that does not sit at that entry's site?"
   uint64_t m1, m2;
   uint32_t s1;
-#ifdef PM_CARVE_PROF  // the row's anatomy: ticks and counts of the sorted insertions, the near-miss tracker, the exact
-  // (sine form) keys, evictions that needed a site looked up
-  uint64_t p_ins_t = 0, p_trk_t = 0, p_hav_t = 0, p_wait_t = 0, p_eval_t = 0, p_key_t = 0, p_off_t = 0;
-  uint32_t p_ins_n = 0, p_trk_n = 0, p_hav_n = 0, p_ev_n = 0, p_strides = 0;
-  uint64_t p_seg[6] = {0, 0, 0, 0, 0, 0};  // near_row_bulk4: count + pack, networks, threshold + evictions, near misses; calls; whole calls
-#endif
+  NEAR_ROW_PROF_FIELDS  // (a measuring build: the row's anatomy — NR_T0 / NR_ADD / NR_CNT / NR_SEG below book into these)
 };
-#ifdef PM_CARVE_PROF
-#define NR_SEG(r, i, t0) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); (r).p_seg[i] += t_ - (t0); (t0) = t_; } while (0)
-#define NR_SEG0(var) uint64_t var = __builtin_amdgcn_s_memtime()
-#define NR_T0 const uint64_t nr_t0_ = __builtin_amdgcn_s_memtime()
-#define NR_ADD(field) (field) += __builtin_amdgcn_s_memtime() - nr_t0_
-#define NR_CNT(field, n) (field) += (n)
-#else
-#define NR_SEG(r, i, t0)
-#define NR_SEG0(var)
-#define NR_T0
-#define NR_ADD(field)
-#define NR_CNT(field, n)
-#endif
 __device__ __forceinline__ uint64_t wave_shr1_u64(uint64_t v) {  // lane i <- lane i - 1, lane 0 <- 0
   const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0x138, 0xF, 0xF, false);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x138, 0xF, 0xF, false);
@@ -474,9 +456,7 @@ __device__ __forceinline__ void offer_candidate(const CarveArgs& p, const SeedGe
 struct BulkCtx {  // the streaming carve's rows: how many candidates the row has seen, the lane's network constants
   uint32_t seen;
   LaneNet ln;
-#ifdef PM_ROW_REC  // (a measuring build: when the sweep's first pass was packed, when the first batch's keys were there)
-  uint64_t rec_pass = 0, rec_keys = 0;
-#endif
+  BULK_REC_FIELDS  // (a measuring build: when the sweep's first pass was packed, when the first batch's keys were there)
 };
 template <bool STREAM = false>
 __device__ __forceinline__ void cell_drain(const CarveArgs& p, uint32_t* wl, uint32_t& nb, uint32_t lane, uint32_t s, bool shared,
@@ -847,13 +827,6 @@ __global__ __launch_bounds__(256) void carve_propose_kernel(const CarveArgs* __r
     const bool valid = out_row < n_my;
     const uint32_t s = valid ? seed_slots[world > 1u ? my_rank + world * out_row : out_row] : 0u;
     const uint32_t ssite = G(p.cc_site)[s];
-#ifdef PM_PROP_PROF
-    uint64_t pt = __builtin_amdgcn_s_memtime(), pt_same = 0, pt_sweep = 0, pt_pop = 0, pt_flags = 0;
-    (void)pt_same; (void)pt_sweep; (void)pt_pop; (void)pt_flags;
-#define PP_MARK(var) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); var += t_ - pt; pt = t_; } while (0)
-#else
-#define PP_MARK(var)
-#endif
     const SeedGeo sg = {G(p.cc_lat)[s], G(p.cc_lon)[s], G(p.cc_cos)[s], G(p.cc_ux)[s], G(p.cc_uy)[s], G(p.cc_uz)[s]};
     const bool shared = (ssite & 0x80000000u) != 0u;
     NearRow q = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
@@ -863,21 +836,9 @@ __global__ __launch_bounds__(256) void carve_propose_kernel(const CarveArgs* __r
         // (the tiles' LDS is free on this side: a candidate buffer per wave)
         static_assert(4u * 2u * CELL_BUF * sizeof(uint32_t) <= sizeof(tiles), "four candidate buffers in the tiles' LDS");
         uint32_t* wl = reinterpret_cast<uint32_t*>(tiles) + wave * (2u * CELL_BUF);
-#ifdef PM_BATCH_LOG
-        const uint64_t wt0 = __builtin_amdgcn_s_memtime();
-#endif
+        PM_BLOG(const uint64_t wt0 = PM_TICKS();)
         const uint32_t stop_r = p.prune_mode != 3u ? cell_walk(p, wl, cell_g, PM_CELL_RMAX, lane, s, shared, ssite, sg, SB, WINDOW_ULPS, q, n_mine) : 0u;
-#ifdef PM_BATCH_LOG
-        if (lane == 0) {  // (experiment builds: where the walks stopped, what they cost)
-          const uint64_t dt = __builtin_amdgcn_s_memtime() - wt0;
-          unsigned long long* pr = (unsigned long long*)p.status->prof;
-          atomicAdd(&pr[0], (unsigned long long)dt);
-          atomicMax(&pr[1], (unsigned long long)dt);
-          atomicAdd(&pr[2], 1ull);
-          atomicAdd(&pr[3], (unsigned long long)n_mine);
-          atomicAdd(&pr[16u + (stop_r < 15u ? stop_r : 15u)], 1ull);
-        }
-#endif
+        BLOG_WALK(wt0, n_mine, stop_r);  // where the walk stopped, what it cost
         if (!stop_r) {
           q = NearRow{~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
           n_mine = 0;
@@ -898,27 +859,9 @@ __global__ __launch_bounds__(256) void carve_propose_kernel(const CarveArgs* __r
         __syncthreads();
       }
     }
-    PP_MARK(pt_sweep);
     uint64_t mine;
     const uint32_t meta = near_row_finish(p, q, valid, K, SB, TIE_BAND, lane, &mine);
     if (!valid) continue;  // (the workgroup's last seeds may be fewer than four)
-    PP_MARK(pt_flags);
-#ifdef PM_PROP_PROF
-    {
-      if (lane == 0) {
-        unsigned long long* pr = (unsigned long long*)p.status->prof;
-#ifndef PM_CARVE_PROF_FINE  // (the fine build uses these slots for the validator's round phases)
-        atomicAdd(&pr[5], (unsigned long long)pt_same);
-        atomicAdd(&pr[6], (unsigned long long)pt_sweep);
-        atomicAdd(&pr[7], (unsigned long long)pt_pop);
-        atomicAdd(&pr[8], (unsigned long long)pt_flags);
-        atomicMax(&pr[23], (unsigned long long)(pt_same + pt_sweep + pt_pop + pt_flags));
-#endif
-        atomicAdd(&pr[24], 1ull);
-        atomicAdd(&pr[25], (q.m1 != ~0ull) ? 1ull : 0ull);
-      }
-    }
-#endif
     if (p.count_keys) {  // bookkeeping for the roofline of this kernel (bench only): keys this sweep evaluated
       const uint32_t swept = wave_sum(n_mine);
       if (lane == 0) {

@@ -104,8 +104,23 @@ static_assert(STREAM_SMALL_START >= STREAM_SMALL_AT && STREAM_SMALL_START <= STR
 #else
 #define STREAM_LA_SMALL(n) ((n) / 4u * STREAM_LA_SMALL_NUM)
 #endif
+// STREAM_NO_DROP is 0 or 1 — a variant build's switch, not a tuning knob.  1 (what a bare -DSTREAM_NO_DROP gives): no ticket is
+// ever dropped, STREAM_DROPPED is false.  0, the product: the tickets a configuration has no use for any more are let be.
+#ifndef STREAM_NO_DROP
+#define STREAM_NO_DROP 0
+#endif
+static_assert(STREAM_NO_DROP == 0 || STREAM_NO_DROP == 1, "STREAM_NO_DROP is 0 or 1");
 #ifndef STREAM_LA_ALL
 #define STREAM_LA_ALL 1536u  // candidates up to which a configuration's seeds all get their tickets at once
+#endif
+#ifndef PM_STREAM_ROW_SPINS
+#define PM_STREAM_ROW_SPINS 4096u       // polls (about 0.5 us each) before the validator gives a row up
+#endif
+#ifndef PM_STREAM_IDLE_SPINS
+#define PM_STREAM_IDLE_SPINS (1u << 21) // polls (about 1 us each) before an unasked proposer wave leaves
+#endif
+#ifndef STREAM_SMALL_WINDOW  // live candidates in front of a candidate of stream_small_rows whose row is being made (settable in a variant build)
+#define STREAM_SMALL_WINDOW 8u
 #endif
 // located candidates alive (cand & loc), counted by one wave from the LDS bitmaps
 __device__ __forceinline__ uint32_t stream_count_located(const uint64_t* l_alive, const uint64_t* l_loc, uint32_t lw, uint32_t lane) {
@@ -114,54 +129,10 @@ __device__ __forceinline__ uint32_t stream_count_located(const uint64_t* l_alive
   return wave_sum(cnt);
 }
 
-#ifndef PM_STREAM_ROW_SPINS
-#define PM_STREAM_ROW_SPINS 4096u       // polls (about 0.5 us each) before the validator gives a row up
-#endif
-#ifndef PM_STREAM_IDLE_SPINS
-#define PM_STREAM_IDLE_SPINS (1u << 21) // polls (about 1 us each) before an unasked proposer wave leaves
-#endif
-
-#if defined(PM_CARVE_PROF) || defined(PM_ROW_REC)  // timeline events (one lane calls): 1 configuration entered (ci, candidates), 2 chain waits (entry), 3 chain
-// goes on (entry), 4 tickets issued (count), 5 block parked (block, first entry), 6 run starts (ticket), 7 run ends (action,
-// commits), 8 row written (ticket, ticks it took), 9 exact step
-#ifdef PM_ROW_REC  // (a measuring build: the row makers' records fill the first half of the buffer, the validator's events the second;
-// every stamp of it is the REAL-TIME counter — 100 MHz, one clock for all CUs — so that a ticket's way from the ticketer
-// through a row maker and a parker to the chain can be laid on one axis: tools/pipeline_probe.py)
-#define STREAM_TRACE_AT size_t(PM_STREAM_TRACE_CAP)
-#define STREAM_TRACE_MAX (PM_STREAM_TRACE_CAP / 8u)
-#define STREAM_PARK_AT (size_t(PM_STREAM_TRACE_CAP) + PM_STREAM_TRACE_CAP / 4u)  // the parkers' blocks: eight words each, plain stores, by ticket / 16
-#define STREAM_PARK_MAX (PM_STREAM_TRACE_CAP / 32u)
-#define STREAM_BATCH_AT (size_t(PM_STREAM_TRACE_CAP) + PM_STREAM_TRACE_CAP / 2u)  // the chain's batches: {clock, what it took up}, plain stores
-#define STREAM_BATCH_MAX (PM_STREAM_TRACE_CAP / 8u)  // (four words each)
-#define STREAM_CLOCK() __builtin_amdgcn_s_memrealtime()
-#else
-#define STREAM_TRACE_AT size_t(0)
-#define STREAM_TRACE_MAX PM_STREAM_TRACE_CAP
-#define STREAM_CLOCK() __builtin_amdgcn_s_memtime()
-#endif
-#define STREAM_TRACE(type, a, b)                                                                                   \
-  do {                                                                                                             \
-    if (p.stream_trace) {                                                                                          \
-      const uint32_t ti_ = atomicAdd(&p.stream_ctl[SC_TRACE], 1u);                                                 \
-      if (ti_ < STREAM_TRACE_MAX) {                                                                                \
-        p.stream_trace[STREAM_TRACE_AT + 2u * ti_] = STREAM_CLOCK();                                           \
-        p.stream_trace[STREAM_TRACE_AT + 2u * ti_ + 1u] = (unsigned long long)(type) | ((unsigned long long)((a) & 0xFFFFFFu) << 8) | \
-                                        ((unsigned long long)(b) << 32);                                           \
-      }                                                                                                            \
-    }                                                                                                              \
-  } while (0)
-#else
-#define STREAM_TRACE(type, a, b)
-#endif
-
 // SC_DROP: what the validator publishes when a configuration's outstanding tickets lose their purpose, and what a row maker
 // asks of it (ticket numbers count from zero in every launch and stay far below 2^25)
 #define STREAM_DROP_WORD(ci, t) (((uint32_t)(ci) << 26) | ((uint32_t)(t) & 0x03FFFFFFu))
-#ifdef STREAM_NO_DROP  // (a variant build's switch: tools/build_variants.py)
-#define STREAM_DROPPED(word, ci, t) (false && (word) == (ci) + (t))
-#else
-#define STREAM_DROPPED(word, ci, t) (((word) >> 26) == (uint32_t)(ci) && ((((uint32_t)(t) - (word)) & 0x03FFFFFFu) >= 0x02000000u))
-#endif
+#define STREAM_DROPPED(word, ci, t) (!STREAM_NO_DROP && ((word) >> 26) == (uint32_t)(ci) && ((((uint32_t)(t) - (word)) & 0x03FFFFFFu) >= 0x02000000u))
 typedef __attribute__((address_space(1))) unsigned long long stream_gu64;
 typedef __attribute__((address_space(1))) uint32_t stream_gu32;
 __device__ __forceinline__ unsigned long long ld_ag(const stream_gu64* q) {
@@ -435,15 +406,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
                              : UNI(p.stream_row_spins) ? UNI(p.stream_row_spins) : PM_STREAM_ROW_SPINS;
   uint32_t timeouts = 0u;
   uint32_t seen = 0u;
-#ifdef PM_CARVE_PROF  // parker anatomy: ticks waiting for tickets, for room, for rows, digesting
-  uint64_t pt = __builtin_amdgcn_s_memtime(), pt_tick = 0, pt_room = 0, pt_rows = 0, pt_write = 0, pt_idle = 0;
-  uint32_t pn_polls = 0, pn_late = 0, pn_rows = 0;
-#define SP_MARK(var) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); var += t_ - pt; pt = t_; } while (0)
-#define SP_COUNT(var, n) (var += (n))
-#else
-#define SP_MARK(var)
-#define SP_COUNT(var, n)
-#endif
+  SP_DECL;
   for (;;) {
     uint32_t cmd = chain_wait_cmd(L, seen);
     SP_MARK(pt_idle);
@@ -484,9 +447,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
       }
       if (stopped) break;
       SP_MARK(pt_tick);
-#ifdef PM_CARVE_PROF
-      const uint64_t rw0 = __builtin_amdgcn_s_memtime();
-#endif
+      PM_PROF(const uint64_t rw0 = PM_TICKS();)
       // ---- the seeds (lane k: ticket t0 + k) and the rows of the ones that are alive (lane = granule of the row)
       // (a ticket of another configuration, issued ahead of its turn, is not this run's business)
       const uint32_t tp_k = lane < n_real ? cc_ld(&SL[(t0 + lane) & (PM_STREAM_TP - 1u)]) : 0u;
@@ -500,14 +461,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
       for (uint32_t k = 0; k < NB; ++k)
         prow[k] = (need_rows && ((live_m >> k) & 1u)) ? ld_ag(&row_lo[(size_t)((t0 + k) & (PM_STREAM_RQ - 1u)) * 64u + lane]) : 0ull;
       SP_COUNT(pn_rows, n_live);
-#ifdef PM_ROW_REC  // (a record per block, plain stores: which tickets' rows were asked for and when; when they were all there; when the
-      // block had its turn; when it had room; when it was parked, where and which)
-      unsigned long long* const prec = p.stream_trace ? p.stream_trace + STREAM_PARK_AT + size_t((t0 >> 4) & (STREAM_PARK_MAX - 1u)) * 8u : nullptr;
-      if (lane == 0u && prec) {
-        prec[0] = (unsigned long long)t0 | ((unsigned long long)live_m << 32) | ((unsigned long long)n_real << 48) | (1ull << 63);
-        prec[1] = STREAM_CLOCK();
-      }
-#endif
+      PARK_REC_OPEN(t0, live_m, n_real);  // the block's record: which tickets' rows were asked for, and when
       // one row -> its ring entry q (digested: per lane the LDS address of the entry's bitmap word and its bit), stamped
       auto park_one = [&](uint32_t k, unsigned long long row, uint32_t q) {
         const uint32_t v = (uint32_t)row;  // granule 0: the flags word; granule g: the low half of entry g - 1's key
@@ -556,27 +510,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
 #pragma unroll
             for (uint32_t k = 0; k < NB; ++k)
               if ((not_ready >> k) & 1u) {
-#ifdef PM_TIMEOUT_DIAG  // what was there instead (first time-outs of the launch): status->prof[8 n .. 8 n + 7]
-                {
-                  const unsigned long long sqv2 = ld_ag(&G((const unsigned long long*)p.stream_sq)[(t0 + k) & (PM_STREAM_SQ - 1u)]);
-                  const uint32_t claim2 = ld_ag32(&G(p.stream_ctl)[SC_CLAIM]);
-                  const uint32_t rtag2 = UNI((uint32_t)(prow[k] >> 32));
-                  if (lane == 0u) {
-                    unsigned long long* pr = (unsigned long long*)p.status->prof;
-                    const unsigned long long slot = atomicAdd(&pr[47], 1ull);
-                    if (slot < 5ull) {
-                      pr[8 * slot + 0] = t0 + k;
-                      pr[8 * slot + 1] = rtag2 - tag0;
-                      pr[8 * slot + 2] = (uint32_t)(sqv2 >> 32) - tag0;
-                      pr[8 * slot + 3] = (uint32_t)sqv2;
-                      pr[8 * slot + 4] = claim2;
-                      pr[8 * slot + 5] = UNI(cc_ld(&SL[SLW_TREQ]));
-                      pr[8 * slot + 6] = t0_run;
-                      pr[8 * slot + 7] = UNI(cc_ld(&SL[SLW_TISSUED]));
-                    }
-                  }
-                }
-#endif
+                STREAM_TIMEOUT_DUMP(t0 + k, prow[k]);  // what was there instead
                 prow[k] = 0ull;
                 ++timeouts;
               }
@@ -586,12 +520,8 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
         if (stopped) break;
       }
       SP_MARK(pt_rows);
-#ifdef PM_ROW_REC
-      if (lane == 0u && prec) prec[2] = STREAM_CLOCK();
-#endif
-#ifdef PM_CARVE_PROF
-      if (lane == 0u) STREAM_TRACE(16, b, (uint32_t)(__builtin_amdgcn_s_memtime() - rw0));  // (the block's rows: asked for -> all there)
-#endif
+      PARK_REC_STAMP(2);  // the rows are all there
+      PM_PROF(if (lane == 0u) STREAM_TRACE(16, b, (uint32_t)(PM_TICKS() - rw0));)  // (the block's rows: asked for -> all there)
       // ---- who is still alive now that the rows are there (a dead seed takes no ring entry: the later this is looked
       // at, the fewer entries the chain finds dead at their turn)
       {
@@ -618,12 +548,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
         }
       }
       if (stopped) break;
-#ifdef PM_ROW_REC
-      if (lane == 0u && prec) prec[3] = STREAM_CLOCK();
-#endif
-#ifdef STREAM_PARK_SLOWER  // (a measuring build: are the parkers on the carve's critical path?)
-      __builtin_amdgcn_s_sleep(STREAM_PARK_SLOWER);
-#endif
+      PARK_REC_STAMP(3);  // the block has its turn
       if (lane == 0u) {
         cc_st(&L.CC[CC_CUM], q_b + n_live);
         if (n_real < NB) cc_st(&L.CC[CC_DONE], q_b + n_live + 1u);  // (the run's last block: its last entry is known)
@@ -644,24 +569,15 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
         }
       }
       if (stopped) break;
-#ifdef PM_ROW_REC
-      if (lane == 0u && prec) prec[4] = STREAM_CLOCK();
-#endif
+      PARK_REC_STAMP(4);  // it has room
       SP_MARK(pt_room);
       // ---- park the live ones
 #pragma unroll
       for (uint32_t k = 0; k < NB; ++k)
         if ((live_m >> k) & 1u) park_one(k, prow[k], q_b + (uint32_t)__builtin_popcount(live_m & ((1u << k) - 1u)));
       SP_MARK(pt_write);
-#ifndef PM_ROW_REC  // (an atomic with its return value in the parkers' path: the measuring build has the record below instead)
-      if (lane == 0u) STREAM_TRACE(5, b, q_b | (n_live << 24));
-#endif
-#ifdef PM_ROW_REC
-      if (lane == 0u && prec) {
-        prec[5] = STREAM_CLOCK();
-        prec[6] = (unsigned long long)q_b | ((unsigned long long)live_m << 32) | ((unsigned long long)b << 48);
-      }
-#endif
+      if (lane == 0u) STREAM_TRACE_NOT_REC(5, b, q_b | (n_live << 24));  // (the PM_ROW_REC build has the record's last words instead)
+      PARK_REC_CLOSE(q_b, live_m, b);  // it is parked: when, where and which
       if (n_real < NB) break;  // the run's last block
     }
     cmd = chain_wait_cmd(L, seen);
@@ -672,19 +588,7 @@ __device__ __noinline__ void stream_park(const CarveArgs& p, const StepCtx& c, u
     cc_st(&SL[SLW_ACKP0 + pi], cmd);  // STOP
   }
   if (lane == 0u && timeouts) __hip_atomic_fetch_add(&SL[SLW_TIMEOUTS], timeouts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#if defined(PM_CARVE_PROF) && !defined(PM_CHAIN_FINE)
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    atomicAdd(&pr[5], (unsigned long long)pt_tick);
-    atomicAdd(&pr[6], (unsigned long long)pt_room);
-    atomicAdd(&pr[7], (unsigned long long)pt_rows);
-    atomicAdd(&pr[8], (unsigned long long)pt_write);
-    atomicAdd(&pr[9], (unsigned long long)pt_idle);
-    atomicAdd(&pr[26], (unsigned long long)pn_polls);
-    atomicAdd(&pr[27], (unsigned long long)pn_late);
-    atomicAdd(&pr[28], (unsigned long long)pn_rows);
-  }
-#endif
+  SP_BOOK();
 }
 
 // ---- the chain (wave 0 of the validator).  carve_chain's loop, with the ring fed by the parkers: entry q of a run is
@@ -737,15 +641,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
     const uint32_t t = n_loc > STREAM_SMALL_AT ? (n_loc - STREAM_SMALL_AT + group_n - 1u) / group_n : 0u;
     return b < t ? b : t;
   };
-#ifdef PM_CARVE_PROF
-  uint64_t ct = __builtin_amdgcn_s_memtime(), ct_wait = 0, ct_steps = 0, ct_stop = 0, ct_head = 0, ct_plain = 0, ct_att = 0;
-  uint32_t cn_outer = 0, cn_dead = 0, cn_wait = 0, cn_att = 0;
-#define CH_MARK(var) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); var += t_ - ct; ct = t_; } while (0)
-#define CH_COUNT(var) (++var)
-#else
-#define CH_MARK(var)
-#define CH_COUNT(var)
-#endif
+  CH_DECL_FINE;
 
   // ---- start the ticketer, the parkers and the collector: the run begins at ticket T0 — the one to resume at, or
   // behind the last one issued for this configuration when nothing issued so far is of use any more
@@ -771,12 +667,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
   if (lane == 0u) STREAM_TRACE(6, t0_run, base_cand);
   uint32_t tail = 0u, budget = 0u;
   bool aborted = false;
-#ifdef PM_ROW_REC
-  uint32_t rec_batches = UNI(p.stream_ctl[SC_BATCHES]);  // (the runs of a launch share the region)
-#endif
-#ifdef PM_CHAIN_PRIO
-  __builtin_amdgcn_s_setprio(3);  // (the chain is the critical path; the waves beside it only feed it)
-#endif
+  PM_REC(uint32_t rec_batches = UNI(p.stream_ctl[SC_BATCHES]);)  // (the runs of a launch share the region)
   // entries parked from `tail` on, as far as their stamps say (at most the next 16 matter): one LDS read, one ballot
   auto head_now = [&](uint32_t tl) -> uint32_t {
     const uint32_t q = tl + lane;
@@ -786,9 +677,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
   {
     for (;;) {
       CH_COUNT(cn_outer);
-#ifdef PM_ROW_REC
-      const uint64_t rec_top = STREAM_CLOCK();
-#endif
+      PM_REC(const uint64_t rec_top = STREAM_CLOCK();)
       tail = UNI(tail);
       // ---- rows parked and not yet looked at
       uint32_t head = head_now(tail);
@@ -839,18 +728,8 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
         const bool al = lane < n_steps && sab != 0ull && (sw & ~(uint32_t)(sab >> 32)) != 0u;
         lm = (uint32_t)__ballot(al);
         if (lane < n_steps && !al) L.RAB[qe * 64u] = 0ull;
-#ifdef PM_CARVE_PROF
-        cn_dead += n_steps - (uint32_t)__builtin_popcount(lm);
-#endif
-#ifdef PM_ROW_REC  // (one record per batch, plain stores: clock at the loop's top; first entry | entries << 24 | live ones << 32 |
-        // commits so far << 40; clock here — the entries seen and looked at; clock behind the steps)
-        if (lane == 0u && p.stream_trace && rec_batches < STREAM_BATCH_MAX) {
-          p.stream_trace[STREAM_BATCH_AT + 4u * rec_batches] = rec_top;
-          p.stream_trace[STREAM_BATCH_AT + 4u * rec_batches + 1u] = (unsigned long long)(tail0 & 0xFFFFFFu) | ((unsigned long long)n_steps << 24) |
-                                                                    ((unsigned long long)__builtin_popcount(lm) << 32) | ((unsigned long long)(step0 + commits) << 40);
-          p.stream_trace[STREAM_BATCH_AT + 4u * rec_batches + 2u] = STREAM_CLOCK();
-        }
-#endif
+        PM_PROF(cn_dead += n_steps - (uint32_t)__builtin_popcount(lm);)
+        CHAIN_REC_BATCH(rec_top, tail0, n_steps, __builtin_popcount(lm), step0 + commits);  // the batch's record: its entries seen and looked at
       }
       // ---- the budget, looked at in FRONT of a batch (the steps below do not test it: a batch takes no more entries than
       // the budget has commits left)
@@ -1015,9 +894,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
             // (here: lm — the live entries behind the NEXT one; sn — the next one's offset, -1: none)
             r = (tail0 + s) & (R - 1u);
             if ((a & 1ull) == 0ull) {  // the seed is dead at its turn: a step that selects nothing (its word stays 0)
-#ifdef PM_CARVE_PROF
-              cn_dead += 1u;
-#endif
+              PM_PROF(cn_dead += 1u;)
             } else {
               // ---- a live seed that needs a second look
               m2 = UNI(L.RM[r]);
@@ -1073,13 +950,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
         budget -= commits - commits0;
         n_cand = base_cand - commits * group_n;
       }
-#ifdef PM_ROW_REC
-      if (lane == 0u && p.stream_trace && rec_batches < STREAM_BATCH_MAX) p.stream_trace[STREAM_BATCH_AT + 4u * rec_batches + 3u] = STREAM_CLOCK();
-      rec_batches += 1u;
-#endif
-#ifdef STREAM_CHAIN_SLOWER  // (a measuring build: is the chain on the carve's critical path?)
-      __builtin_amdgcn_s_sleep(STREAM_CHAIN_SLOWER);
-#endif
+      CHAIN_REC_BATCH_END();  // ... and the clock behind its steps
       if (lane == 0u) {
         cc_st(&L.CC[CC_CRIT], tail);  // for the collector
         cc_st(&SL[SLW_NCAND], n_cand);  // for the ticketer: its window follows what is left
@@ -1088,34 +959,10 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
       if (stop) break;
     }
   }
-#ifdef PM_CHAIN_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
   // ---- stop the other two (they must be off the key array before it is used again; the collector writes out first)
   cmd_seq += 4u;
   if (lane == 0u) cc_st(&L.CC[CC_CMD], cmd_seq | CH_STOP);
-#if defined(PM_CARVE_PROF) || defined(PM_ROW_REC)  // (measuring builds: when each of the seven acknowledges — event 26: who, ticks)
-  {
-    const uint64_t st0 = __builtin_amdgcn_s_memtime();
-    const uint32_t want_ack = cmd_seq | CH_STOP;
-    uint32_t got = 0u, sp_n = 0u;
-    uint32_t dt[7] = {0, 0, 0, 0, 0, 0, 0};
-    while (got != 0x7Fu && ++sp_n < (1u << 16)) {
-#pragma unroll
-      for (uint32_t i = 0; i < 7u; ++i) {
-        const uint32_t v = i == 0u ? UNI(cc_ld(&L.CC[CC_ACK2])) : i == 1u ? UNI(cc_ld(&SL[SLW_ACKT])) : UNI(cc_ld(&SL[SLW_ACKP0 + (i - 2u)]));
-        if (!((got >> i) & 1u) && v == want_ack) {
-          got |= 1u << i;
-          dt[i] = (uint32_t)(__builtin_amdgcn_s_memtime() - st0);
-        }
-      }
-    }
-    if (lane == 0u) {
-#pragma unroll
-      for (uint32_t i = 0; i < 7u; ++i) STREAM_TRACE(26, i, dt[i]);
-    }
-  }
-#endif
+  STREAM_TRACE_ACKS(L, SL, cmd_seq | CH_STOP);  // when each of the seven acknowledges
   {
     uint32_t sp_n = 0u;
     const uint32_t want_ack = cmd_seq | CH_STOP;
@@ -1144,29 +991,8 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
   // sum over the commits of the live candidates before each: base, base - g, base - 2g, ...
   c.cand_sum += (unsigned long long)commits * base_cand -
                 (unsigned long long)group_n * ((unsigned long long)commits * (commits ? commits - 1u : 0u) / 2ull);
-#ifdef PM_CARVE_PROF
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    pr[1] += 1u;        // calls
-    pr[2] += commits;
-    pr[4] += action == FAST_SLOW ? 1u : 0u;
-    pr[16] += ct_wait;
-    pr[17] += ct_stop;
-    pr[18] += ct_steps;
-    pr[19] += cn_outer;
-    pr[23] += cn_dead;
-    pr[24] += cn_wait;
-#ifdef PM_CHAIN_FINE  // (with -DPM_CARVE_PROF: the steps' time taken apart, in the parkers' slots — every prof word has an owner)
-    pr[5] += ct_head;   // of the steps' time: the batches' heads,
-    pr[6] += ct_plain;  // the plain runs,
-    pr[7] += ct_att;    // the steps that needed attention (a dead seed, a second look),
-    pr[8] += cn_att;    // how many of those (ct_steps, pr[18]: what is left — the batch's tail: counters, the hand-over words)
-#endif
-  }
-#endif
-#ifdef PM_ROW_REC
-  if (lane == 0u) p.stream_ctl[SC_BATCHES] = rec_batches;
-#endif
+  CH_BOOK(CH_FINE_WORDS);
+  PM_REC(if (lane == 0u) p.stream_ctl[SC_BATCHES] = rec_batches;)
   if (lane == 0u) STREAM_TRACE(7, action, commits);
   c_ref = c;
   seed_cur = exit_cur;
@@ -1380,13 +1206,7 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
   uint32_t uw = 0u;       // first bitmap word that may still hold a live location-less candidate
   int rc = STEP_BREAK;
   if (lane == 0u) STREAM_TRACE(15, n_cl, c.n_cand);
-#ifdef PM_CARVE_PROF
-  uint64_t sm_t = __builtin_amdgcn_s_memtime(), sm_a[5] = {0, 0, 0, 0, 0};
-  uint32_t sm_n = 0;
-#define SM_MARK(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); sm_a[k] += t_ - sm_t; sm_t = t_; } while (0)
-#else
-#define SM_MARK(k)
-#endif
+  SM_DECL;
   for (;;) {
     if (!(c.total_available >= c.min_s && c.n_cand >= c.min_s && c.n_cand > 0u)) break;  // mod.rs:507, 517-519
     if (!(prox && n_loc > 0u)) {  // first-come from here on (mod.rs:553-561): the whole workgroup's business
@@ -1547,17 +1367,9 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
     c.steps += 1u;
     c.fast_steps += 1u;  // (not an exact sweep of the workgroup: counted with the steps that came from rows)
     SM_MARK(4);
-#ifdef PM_CARVE_PROF
-    ++sm_n;
-#endif
+    PM_PROF(++sm_n;)
   }
-#ifdef PM_CARVE_PROF
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    for (int q = 0; q < 5; ++q) pr[42 + q] += sm_a[q];
-    pr[47] += sm_n;
-  }
-#endif
+  SM_BOOK();
   c_ref = c;
   return rc;
 }
@@ -1576,9 +1388,6 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
 //   l_stage words [0, 128): the candidates' positions (stream_compact_candidates); [192, 198): control words;
 //   [ROWS_AT, + 8192): 64 rows of 64 keys; behind them 64 x 64 bytes: the inverses.
 #define STREAM_ROWS_AT 256u
-#ifndef STREAM_SMALL_WINDOW  // live candidates in front of one whose row is being made (settable in a variant build)
-#define STREAM_SMALL_WINDOW 8u
-#endif
 #define STREAM_ROWS_INV_AT (STREAM_ROWS_AT + 64u * 64u * 2u)
 static_assert(STREAM_ROWS_INV_AT + 64u * 64u / 4u <= 3u * CHAIN_RING * 64u, "the rows end in front of the chain's control block");
 // control words of the phase (u32 index into l_stage): the next candidate a helper takes, the end of the phase, the rows
@@ -1708,10 +1517,7 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
   uint32_t uw = 0u;
   int rc = STEP_BREAK;
   if (lane == 0u) STREAM_TRACE(15, n_cl, c.n_cand);
-#ifdef PM_CARVE_PROF  // (the anatomy's stream_small line: the steps on rows are booked as selection time)
-  const uint64_t sr_t0 = __builtin_amdgcn_s_memtime();
-  const uint32_t sr_g0 = c.n_groups;
-#endif
+  PM_PROF(const uint64_t sr_t0 = PM_TICKS(); const uint32_t sr_g0 = c.n_groups;)  // (the steps on rows are booked as selection time)
   for (;;) {
     if (!(c.total_available >= c.min_s && c.n_cand >= c.min_s && c.n_cand > 0u)) break;  // mod.rs:507, 517-519
     if (!(prox && n_loc > 0u)) {  // first-come from here on (mod.rs:553-561): the whole workgroup's business
@@ -1838,13 +1644,7 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
     c.fast_steps += 1u;  // (not an exact sweep of the workgroup: counted with the steps that came from rows)
   }
   if (lane == 0u) cc_st(&ctl[SRW_QUIT], 1u);  // (the helpers leave: on to the caller's barrier)
-#ifdef PM_CARVE_PROF
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    pr[44] += __builtin_amdgcn_s_memtime() - sr_t0;
-    pr[47] += c.n_groups - sr_g0;
-  }
-#endif
+  SR_BOOK(sr_t0, c.n_groups - sr_g0);
   c_ref = c;
   return rc;
 }
@@ -2135,9 +1935,9 @@ __device__ __noinline__ int stream_run_config(const CarveArgs& p, BlockRed& red,
 #define STREAM_WL_WORDS 4608u  // a pass adds up to 4096 positions to at most 511 left over
 // (returns true when the ticket was dropped in the meantime — SC_DROP, asked once per batch, the answer read behind the
 // batch's evaluation: the row is let be)
-#ifdef PM_ROW_BENCH
-__device__ uint32_t g_rowb_mode = 0u;  // measuring modes: set by pm_debug_row_bench around its launch only
-#endif
+// (PM_ROWB: what carve_row_bench_kernel leaves out of a row — 1 the row: the keys are made, the row is not; 2 the key
+// arithmetic: a key out of the position; 4 the gathers: every candidate the record of position `lane`; 8 everything but the
+// passes over the bitmap.  false in every build but the row bench's.)
 __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t* wl, uint32_t nb, uint32_t lane, uint32_t s, bool shared,
                                              uint32_t ssite, const SeedGeo& sg, uint32_t SB, uint64_t ulps, NearRow& q, uint32_t& n_mine,
                                              BulkCtx& bulk, uint32_t ci, uint32_t ticket) {
@@ -2159,11 +1959,7 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
       const uint32_t k = k0 + v * 64u + lane;
       const uint32_t tc = wl[k < nb ? k : 0u];
       bt.t[v] = k < nb ? tc : 0xFFFFFFFFu;
-#ifdef PM_ROW_BENCH  // (4 — no gathers: every candidate the record of position `lane`)
-      bt.rec[v] = pack_load(pack, (g_rowb_mode & 4u) ? lane : tc);
-#else
-      bt.rec[v] = pack_load(pack, tc);
-#endif
+      bt.rec[v] = pack_load(pack, PM_ROWB(4u) ? lane : tc);
     }
   };
   auto eval = [&](const Batch& bt, uint32_t n_in_batch) {
@@ -2172,9 +1968,7 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
     uint64_t kk[4];
     uint32_t ss[4];
     const uint32_t n_in = n_in_batch;  // (how many of the batch's 256 places hold a candidate: the caller's arithmetic, not four ballots)
-#ifdef PM_CARVE_PROF
-    const uint64_t ek0 = __builtin_amdgcn_s_memtime();
-#endif
+    PM_PROF(const uint64_t ek0 = PM_TICKS();)
 #pragma unroll
     for (uint32_t v = 0; v < 4u; ++v) {
       const bool in = bt.t[v] != 0xFFFFFFFFu;
@@ -2183,26 +1977,15 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
       ss[v] = pack_site(bt.rec[v]);
       // (merge pass: the neighbours of a seed are the LOCATED candidates only, mod.rs:792-804)
       const bool counts = in && tv != s && !(located && tv < s && (form || (shared && ss[v] == ssite))) && (located || !located_only);
-#ifdef PM_ROW_BENCH  // (2 — no key arithmetic: a key out of the position)
-      if (g_rowb_mode & 2u) kk[v] = counts ? (((uint64_t)(tv * 2654435761u) << SB) | tv) : ~0ull;
-      else
-#endif
-      kk[v] = candidate_key(p, sg, ssite, bt.rec[v].x, bt.rec[v].y, bt.rec[v].z, ss[v], counts ? tv : 0u, located, counts, SB, q);
+      kk[v] = PM_ROWB(2u) ? (counts ? (((uint64_t)(tv * 2654435761u) << SB) | tv) : ~0ull)
+                          : candidate_key(p, sg, ssite, bt.rec[v].x, bt.rec[v].y, bt.rec[v].z, ss[v], counts ? tv : 0u, located, counts, SB, q);
       n_mine += counts ? 1u : 0u;
     }
-#ifdef PM_CARVE_PROF
-    const uint64_t ek1 = __builtin_amdgcn_s_memtime();
-    q.p_key_t += ek1 - ek0;
-#endif
-#ifdef PM_ROW_REC
-    if (bulk.rec_keys == 0) bulk.rec_keys = STREAM_CLOCK();
-#endif
-#ifdef PM_ROW_BENCH  // (measuring modes of carve_row_bench_kernel: 1 — the keys are made, the row is not)
-    if (g_rowb_mode & 1u) {
+    PM_PROF(const uint64_t ek1 = PM_TICKS(); q.p_key_t += ek1 - ek0;)
+    PM_REC(if (bulk.rec_keys == 0) bulk.rec_keys = STREAM_CLOCK();)
+    if (PM_ROWB(1u)) {
       q.m1 ^= kk[0] ^ kk[1] ^ kk[2] ^ kk[3];
-    } else
-#endif
-    if (UNI(bulk.seen) < STREAM_BULK_UPTO) {
+    } else if (UNI(bulk.seen) < STREAM_BULK_UPTO) {
       near_row_offer_bulk<4u, true>(q, kk, ss, p.cc_site, SB, ulps, bulk.ln);
     } else {
 #pragma unroll
@@ -2211,18 +1994,14 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
         near_row_offer(q, kk[v], ss[v], G(p.cc_site), SB, ulps);
       }
     }
-#ifdef PM_CARVE_PROF
-    q.p_off_t += __builtin_amdgcn_s_memtime() - ek1;
-#endif
+    PM_PROF(q.p_off_t += PM_TICKS() - ek1;)
     bulk.seen += n_in;
   };
   if (nb == 0u) return false;
-#ifdef PM_ROW_BENCH  // (8 — the passes over the bitmap alone)
-  if (g_rowb_mode & 8u) {
+  if (PM_ROWB(8u)) {
     n_mine += nb / 64u;
     return false;
   }
-#endif
   const auto drop_w = G(p.stream_ctl) + SC_DROP;
   Batch cur, nxt;
   fetch(cur, 0u);
@@ -2230,17 +2009,9 @@ __device__ __forceinline__ bool stream_drain(const CarveArgs& p, const uint32_t*
     const bool more = k0 + 256u < nb;
     const uint32_t dropw = ld_ag32(drop_w);
     if (more) fetch(nxt, k0 + 256u);
-#ifdef PM_CARVE_PROF  // this batch's gathers waited for (the next batch's eight loads may stay in flight), then its evaluation
-    const uint64_t t0_ = __builtin_amdgcn_s_memtime();
-    if (more) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t t1_ = __builtin_amdgcn_s_memtime();
+    DRAIN_PROF_WAIT(more);  // (a measuring build waits for this batch's gathers HERE, to tell the wait from the evaluation)
     eval(cur, nb - k0 < 256u ? nb - k0 : 256u);
-    q.p_wait_t += t1_ - t0_;
-    q.p_eval_t += __builtin_amdgcn_s_memtime() - t1_;
-#else
-    eval(cur, nb - k0 < 256u ? nb - k0 : 256u);
-#endif
+    DRAIN_PROF_BOOK(q);
     if (STREAM_DROPPED(UNI(dropw), ci, ticket)) return true;
     if (more) cur = nxt;
   }
@@ -2253,10 +2024,7 @@ __device__ __forceinline__ bool stream_bitmap_sweep(const CarveArgs& p, const ui
   const auto cfgb = G(cfg64);
   const uint32_t lw = (n + 63u) >> 6;
   uint32_t nb = 0u;
-#ifdef PM_CARVE_PROF
-  uint64_t bp_t = __builtin_amdgcn_s_memtime(), bp_pass = 0, bp_drain = 0;
-  uint32_t bp_np = 0, bp_nd = 0;
-#endif
+  SWEEP_PROF_DECL;
   // FORM: the located candidates in front of the seed are masked out right here — every one of them is in a group by
   // the seed's turn (a live one would be the seed instead, mod.rs:526-530), so they take no place in the buffer, no
   // gather and no key.  One more load per word up to the seed's; the words behind it are untouched.  (The merge pass
@@ -2280,19 +2048,13 @@ __device__ __forceinline__ bool stream_bitmap_sweep(const CarveArgs& p, const ui
     const uint32_t base = (j0 + lane) * 64u;
     for (; a; a &= a - 1ull) wl[o++] = base + (uint32_t)__builtin_ctzll(a);
     nb += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-#ifdef PM_ROW_REC
-    if (bulk.rec_pass == 0) bulk.rec_pass = STREAM_CLOCK();
-#endif
-#ifdef PM_CARVE_PROF
-    { const uint64_t t_ = __builtin_amdgcn_s_memtime(); bp_pass += t_ - bp_t; bp_t = t_; ++bp_np; }
-#endif
+    PM_REC(if (bulk.rec_pass == 0) bulk.rec_pass = STREAM_CLOCK();)
+    SWEEP_PROF_MARK(bp_pass, bp_np, 1u);
     if (nb >= 512u || j0 + 64u >= lw) {  // whole batches of 256 while the sweep goes on, everything at its end
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // (the lanes read what other lanes of the wave packed)
       const uint32_t take = j0 + 64u >= lw ? nb : (nb & ~255u);
       if (stream_drain(p, wl, take, lane, s, shared, ssite, sg, SB, ulps, q, n_mine, bulk, ci, ticket)) return true;
-#ifdef PM_CARVE_PROF
-      { const uint64_t t_ = __builtin_amdgcn_s_memtime(); bp_drain += t_ - bp_t; bp_t = t_; bp_nd += (take + 255u) >> 8; }
-#endif
+      SWEEP_PROF_MARK(bp_drain, bp_nd, (take + 255u) >> 8);
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       const uint32_t left = nb - take;  // (< 256: moved to the front)
       uint32_t mv[4];
@@ -2305,17 +2067,7 @@ __device__ __forceinline__ bool stream_bitmap_sweep(const CarveArgs& p, const ui
       nb = left;
     }
   }
-#ifdef PM_CARVE_PROF
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    atomicAdd(&pr[38], (unsigned long long)bp_pass);
-    atomicAdd(&pr[39], (unsigned long long)bp_drain);
-    atomicAdd(&pr[40], (unsigned long long)bp_np);
-    atomicAdd(&pr[41], (unsigned long long)bp_nd);
-  }
-  q.p_seg[4] = bp_pass;   // (for the row's own trace events)
-  q.p_seg[5] = bp_drain;
-#endif
+  SWEEP_PROF_BOOK(q);
   return false;
 }
 
@@ -2345,9 +2097,6 @@ __device__ __forceinline__ void stream_proposer(const CarveArgs& p, unsigned cha
                 "a packing list per wave behind the buffers");
   BulkCtx bulk = {0u, lane_net(lane, reinterpret_cast<uint64_t*>(s_raw + size_t(CARVE_WAVES) * STREAM_WL_WORDS * 4u) + wave * NET_PACK_KEYS)};
   for (;;) {
-#ifdef PM_CARVE_PROF
-    const uint64_t ct0 = __builtin_amdgcn_s_memtime();
-#endif
     uint32_t t = 0u;
     if (lane == 0u) t = atomicAdd(&p.stream_ctl[SC_CLAIM], 1u);
     t = UNI(t);
@@ -2371,9 +2120,7 @@ __device__ __forceinline__ void stream_proposer(const CarveArgs& p, unsigned cha
     }
     if (UNI((uint32_t)g) == 0xFFFFFFFFu) return;  // the carve is over
     const uint64_t t_seen = __builtin_amdgcn_s_memtime();
-#ifdef PM_CARVE_PROF
-    const uint64_t bt0 = t_seen;
-#endif
+    PM_PROF(const uint64_t bt0 = t_seen;)
     const uint32_t pay = UNI((uint32_t)g);
     const uint32_t s = pay & 0x3FFFFu, mode = (pay >> 24) & 3u, ci = (pay >> 18) & 63u;
     if (s >= n) continue;  // (never: a ticket names a position)
@@ -2385,14 +2132,8 @@ __device__ __forceinline__ void stream_proposer(const CarveArgs& p, unsigned cha
     NearRow q = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
     uint32_t n_mine = 0;
     bulk.seen = 0u;
-#ifdef PM_ROW_REC
-    bulk.rec_pass = bulk.rec_keys = 0;
-    const uint64_t rec_seen = STREAM_CLOCK();
-#endif
-#ifdef PM_CARVE_PROF  // (the seed's own columns are there)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t bt_geo = __builtin_amdgcn_s_memtime();
-#endif
+    PM_REC(bulk.rec_pass = bulk.rec_keys = 0; const uint64_t rec_seen = STREAM_CLOCK();)
+    PM_PROF(asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const uint64_t bt_geo = PM_TICKS();)  // (the seed's own columns are there)
     bool sweep = true;  // (the bitmap sweep stands in one place: it has the sorting networks inline)
     if (mode == SROW_WALK && cell_g) {
       const uint32_t stop_r = p.prune_mode != 3u ? cell_walk<true>(p, wl, cell_g, PM_CELL_RMAX, lane, s, shared, ssite, sg, SB, WINDOW_ULPS, q, n_mine, (const uint32_t*)cfg64, &bulk) : 0u;
@@ -2411,17 +2152,11 @@ __device__ __forceinline__ void stream_proposer(const CarveArgs& p, unsigned cha
       if (lane == 0u) atomicAdd(&p.stream_ctl[SC_LET_BE], 1u);
       continue;
     }
-#ifdef PM_CARVE_PROF
-    const uint64_t bt1 = __builtin_amdgcn_s_memtime();
-#endif
-#ifdef PM_ROW_REC
-    const uint64_t rec_swept = STREAM_CLOCK();
-#endif
+    PM_PROF(const uint64_t bt1 = PM_TICKS();)
+    PM_REC(const uint64_t rec_swept = STREAM_CLOCK();)
     uint64_t mine;
     const uint32_t meta = near_row_finish(p, q, true, PM_PROP_KMAX, SB, TIE_BAND, lane, &mine);
-#ifdef PM_ROW_REC
-    const uint64_t rec_fin = STREAM_CLOCK() + (meta & 0u);  // (behind the flags word)
-#endif
+    PM_REC(const uint64_t rec_fin = STREAM_CLOCK() + (meta & 0u);)  // (behind the flags word)
     if (p.count_keys) {  // bookkeeping for the bench: keys this row evaluated
       const uint32_t swept = wave_sum(n_mine);
       if (lane == 0) {
@@ -2447,113 +2182,10 @@ __device__ __forceinline__ void stream_proposer(const CarveArgs& p, unsigned cha
     st_ag(&row_hi[rb], tagw | (lane == 63u ? 0ull : (unsigned long long)(uint32_t)(mine >> 32)));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     st_ag(&row_lo[rb], tagw | (lane == 63u ? (unsigned long long)meta : (unsigned long long)(uint32_t)mine));
-#ifdef PM_ROW_REC
-    if (t < PM_STREAM_TRACE_CAP / 8u) {
-      const uint64_t rec_end = STREAM_CLOCK();
-      const uint32_t hw = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-      const uint32_t swept_r = wave_sum(n_mine);
-      const uint64_t w = lane == 0u ? rec_seen : lane == 1u ? bulk.rec_pass : lane == 2u ? bulk.rec_keys : lane == 3u ? rec_swept
-                         : lane == 4u ? rec_fin : lane == 5u ? rec_end : lane == 6u ? ((uint64_t)mode << 32 | swept_r) : (uint64_t)hw;
-      if (lane < 8u) p.stream_trace[(size_t)t * 8u + lane] = w;
-    }
-#endif
-#ifdef PM_CARVE_PROF  // what a row costs its wave, by the way it was made (ticks, rows): list 10/12, walk 13/14, sweep 15/29
-    const uint32_t swept_p = wave_sum(n_mine);
-    if (lane == 0u) {
-      unsigned long long* pr = (unsigned long long*)p.status->prof;
-      const uint64_t dt = __builtin_amdgcn_s_memtime() - bt0;
-      const uint32_t a = mode == SROW_BITMAP ? 10u : mode == SROW_WALK ? 13u : 15u, b = mode == SROW_BITMAP ? 12u : mode == SROW_WALK ? 14u : 29u;
-      atomicAdd(&pr[a], (unsigned long long)dt);
-      atomicAdd(&pr[b], 1ull);
-      atomicMax(&pr[30], (unsigned long long)dt);
-      atomicAdd(&pr[35], (unsigned long long)(bt1 - bt0));                      // ticket seen -> candidates swept
-      atomicAdd(&pr[36], (unsigned long long)(__builtin_amdgcn_s_memtime() - bt1));  // row finished and written
-      atomicAdd(&pr[37], (unsigned long long)swept_p);
-      atomicAdd(&pr[48], (unsigned long long)q.p_ins_t);
-      atomicAdd(&pr[49], (unsigned long long)q.p_ins_n);
-      atomicAdd(&pr[50], (unsigned long long)q.p_trk_t);
-      atomicAdd(&pr[51], (unsigned long long)q.p_trk_n);
-      atomicAdd(&pr[52], (unsigned long long)q.p_hav_t);
-      atomicAdd(&pr[53], (unsigned long long)q.p_hav_n);
-      atomicAdd(&pr[54], (unsigned long long)q.p_ev_n);
-      atomicAdd(&pr[55], (unsigned long long)q.p_strides);
-      atomicAdd(&pr[56], (unsigned long long)q.p_wait_t);
-      atomicAdd(&pr[57], (unsigned long long)q.p_eval_t);
-      atomicAdd(&pr[58], (unsigned long long)q.p_key_t);
-      atomicAdd(&pr[59], (unsigned long long)q.p_off_t);
-      for (uint32_t i = 0; i < 4u; ++i) atomicAdd(&pr[60u + i], (unsigned long long)(i < 3u ? q.p_seg[i == 0u ? 0u : i == 1u ? 2u : 3u] : q.p_seg[5]));
-      STREAM_TRACE(8, t, (uint32_t)dt);
-      if (mode == SROW_BITMAP) {  // where a swept row's time went: ticket seen -> sweep begins; the passes; the batches: waiting, evaluating, the rest; finish + write
-        STREAM_TRACE(20, t, (uint32_t)(bt_geo - bt0));
-        STREAM_TRACE(21, t, (uint32_t)q.p_seg[4]);
-        STREAM_TRACE(22, t, (uint32_t)q.p_wait_t);
-        STREAM_TRACE(23, t, (uint32_t)q.p_eval_t);
-        STREAM_TRACE(24, t, (uint32_t)(q.p_seg[5] - q.p_wait_t - q.p_eval_t));
-        STREAM_TRACE(25, t, (uint32_t)(__builtin_amdgcn_s_memtime() - bt1));
-      }
-    }
-#endif
+    PROP_REC_ROW(t, mode, n_mine, rec_seen, bulk, rec_swept, rec_fin);  // the row's record: its stamps, how it was made, where
+    PROP_PROF_ROW(t, mode, q, n_mine, bt0, bt_geo, bt1);  // what the row cost, by the way it was made
   }
 }
-
-#ifdef PM_ROW_BENCH
-// A measuring build's kernel (tools/row_bench.py): ONE wave alone on a CU makes the row of seed `s` in configuration `ci` `reps`
-// times over — the bitmap sweep exactly as a row maker runs it (every position of free & compatible; the caller hands in a free
-// bitmap of all ones) — and reports s_memtime ticks: out[0] ticks in all, [1] rows, [2] candidates evaluated in the last one,
-// [3] a checksum of the last row (so that what is taken out of the row maker in a variant build shows), [4..7] ticks of the
-// seed's columns, the sweep, the finish.
-__global__ __launch_bounds__(CARVE_THREADS) void carve_row_bench_kernel(const CarveArgs* __restrict__ pa, uint32_t s, uint32_t ci, uint32_t reps,
-                                                                        unsigned long long* __restrict__ out) {
-  const CarveArgs& p = *pa;
-  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  if (wave != 0u) return;
-  const auto st = G((const CarveStatus*)p.status);
-  const uint32_t n = st->n_eligible;
-  if (n == 0u || n > PM_CARVE_BIG_SLOTS || s >= n) return;
-  const uint32_t SB = n > PM_CARVE_SLOTS ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS;
-  const double TIE_BAND = n > PM_CARVE_SLOTS ? PM_TIE_BAND_BIG : PM_TIE_BAND;
-  const uint64_t WINDOW_ULPS = n > PM_CARVE_SLOTS ? (1ull << 25) : (1ull << 20);
-  uint32_t* wl = reinterpret_cast<uint32_t*>(s_raw);
-  BulkCtx bulk = {0u, lane_net(lane, reinterpret_cast<uint64_t*>(s_raw + size_t(CARVE_WAVES) * STREAM_WL_WORDS * 4u))};
-  const uint64_t* cfg64 = p.cfgbits + (size_t)ci * p.bits_stride;
-  unsigned long long t_all = 0, t_geo = 0, t_sweep = 0, t_fin = 0, check = 0;
-  uint32_t swept = 0;
-  for (uint32_t rep = 0; rep < reps; ++rep) {
-    const uint64_t t0 = __builtin_amdgcn_s_memtime();
-    const uint32_t ssite = G(p.cc_site)[s];
-    const SeedGeo sg = {G(p.cc_lat)[s], G(p.cc_lon)[s], G(p.cc_cos)[s], G(p.cc_ux)[s], G(p.cc_uy)[s], G(p.cc_uz)[s]};
-    const bool shared = (ssite & 0x80000000u) != 0u;
-    NearRow q = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
-    uint32_t n_mine = 0;
-    bulk.seen = 0u;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint64_t t1 = __builtin_amdgcn_s_memtime();
-    (void)stream_bitmap_sweep(p, cfg64, n, wl, lane, s, shared, ssite, sg, SB, WINDOW_ULPS, q, n_mine, bulk, ci, 0x01FFFFF0u);
-    const uint64_t t2 = __builtin_amdgcn_s_memtime();
-    uint64_t mine = q.m1;
-    const uint32_t meta = (g_rowb_mode & 1u) ? 0u : near_row_finish(p, q, true, PM_PROP_KMAX, SB, TIE_BAND, lane, &mine);
-    const uint64_t t3 = __builtin_amdgcn_s_memtime() + (meta & 0u);
-    t_all += t3 - t0;
-    t_geo += t1 - t0;
-    t_sweep += t2 - t1;
-    t_fin += t3 - t2;
-    swept = wave_sum(n_mine);
-    check = mine * (lane + 1u) + meta;
-  }
-  unsigned long long cs = check;
-  for (uint32_t o = 32u; o; o >>= 1) cs += __shfl_xor(cs, o, 64);
-  if (lane == 0u) {
-    out[0] = t_all;
-    out[1] = reps;
-    out[2] = swept;
-    out[3] = cs;
-    out[4] = t_geo;
-    out[5] = t_sweep;
-    out[6] = t_fin;
-  }
-}
-#endif
 
 // ---- the kernel: workgroup 0 validates, the others propose
 __global__ __launch_bounds__(CARVE_THREADS) void carve_stream_kernel(const CarveArgs* __restrict__ pa, uint32_t start_ci) {
@@ -2904,3 +2536,63 @@ hipError_t launch_carve_stream(const CarveArgs* d_args, uint32_t start_ci, uint3
   hipLaunchKernelGGL(carve_finish_kernel, dim3(128), dim3(256), 0, s, d_args);
   return hipGetLastError();
 }
+
+// ---- measuring builds only (-DPM_ROW_BENCH; everything else that measures lives in pm_measure.inc, this calls the row maker)
+#ifdef PM_ROW_BENCH
+// A measuring build's kernel (tools/row_bench.py): ONE wave alone on a CU makes the row of seed `s` in configuration `ci` `reps`
+// times over — the bitmap sweep exactly as a row maker runs it (every position of free & compatible; the caller hands in a free
+// bitmap of all ones) — and reports s_memtime ticks: out[0] ticks in all, [1] rows, [2] candidates evaluated in the last one,
+// [3] a checksum of the last row (so that what is taken out of the row maker in a variant build shows), [4..7] ticks of the
+// seed's columns, the sweep, the finish.
+__global__ __launch_bounds__(CARVE_THREADS) void carve_row_bench_kernel(const CarveArgs* __restrict__ pa, uint32_t s, uint32_t ci, uint32_t reps,
+                                                                        unsigned long long* __restrict__ out) {
+  const CarveArgs& p = *pa;
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (wave != 0u) return;
+  const auto st = G((const CarveStatus*)p.status);
+  const uint32_t n = st->n_eligible;
+  if (n == 0u || n > PM_CARVE_BIG_SLOTS || s >= n) return;
+  const uint32_t SB = n > PM_CARVE_SLOTS ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS;
+  const double TIE_BAND = n > PM_CARVE_SLOTS ? PM_TIE_BAND_BIG : PM_TIE_BAND;
+  const uint64_t WINDOW_ULPS = n > PM_CARVE_SLOTS ? (1ull << 25) : (1ull << 20);
+  uint32_t* wl = reinterpret_cast<uint32_t*>(s_raw);
+  BulkCtx bulk = {0u, lane_net(lane, reinterpret_cast<uint64_t*>(s_raw + size_t(CARVE_WAVES) * STREAM_WL_WORDS * 4u))};
+  const uint64_t* cfg64 = p.cfgbits + (size_t)ci * p.bits_stride;
+  unsigned long long t_all = 0, t_geo = 0, t_sweep = 0, t_fin = 0, check = 0;
+  uint32_t swept = 0;
+  for (uint32_t rep = 0; rep < reps; ++rep) {
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+    const uint32_t ssite = G(p.cc_site)[s];
+    const SeedGeo sg = {G(p.cc_lat)[s], G(p.cc_lon)[s], G(p.cc_cos)[s], G(p.cc_ux)[s], G(p.cc_uy)[s], G(p.cc_uz)[s]};
+    const bool shared = (ssite & 0x80000000u) != 0u;
+    NearRow q = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
+    uint32_t n_mine = 0;
+    bulk.seen = 0u;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint64_t t1 = __builtin_amdgcn_s_memtime();
+    (void)stream_bitmap_sweep(p, cfg64, n, wl, lane, s, shared, ssite, sg, SB, WINDOW_ULPS, q, n_mine, bulk, ci, 0x01FFFFF0u);
+    const uint64_t t2 = __builtin_amdgcn_s_memtime();
+    uint64_t mine = q.m1;
+    const uint32_t meta = PM_ROWB(1u) ? 0u : near_row_finish(p, q, true, PM_PROP_KMAX, SB, TIE_BAND, lane, &mine);
+    const uint64_t t3 = __builtin_amdgcn_s_memtime() + (meta & 0u);
+    t_all += t3 - t0;
+    t_geo += t1 - t0;
+    t_sweep += t2 - t1;
+    t_fin += t3 - t2;
+    swept = wave_sum(n_mine);
+    check = mine * (lane + 1u) + meta;
+  }
+  unsigned long long cs = check;
+  for (uint32_t o = 32u; o; o >>= 1) cs += __shfl_xor(cs, o, 64);
+  if (lane == 0u) {
+    out[0] = t_all;
+    out[1] = reps;
+    out[2] = swept;
+    out[3] = cs;
+    out[4] = t_geo;
+    out[5] = t_sweep;
+    out[6] = t_fin;
+  }
+}
+#endif

@@ -171,19 +171,6 @@ __device__ __forceinline__ uint64_t pack_key(uint64_t key_bits, uint32_t slot, u
 
 enum { STEP_CONTINUE = 0, STEP_BREAK = 1, STEP_UNCERTAIN = 2, STEP_OVERFLOW = 3, STEP_ABORT = 4 };
 
-#ifdef PM_CARVE_PROF
-#define PROF_DECL uint64_t prof_t0 = __builtin_amdgcn_s_memtime()
-#define PROF_MARK(slot)                                                     \
-  do {                                                                      \
-    const uint64_t t_ = __builtin_amdgcn_s_memtime();                       \
-    if (threadIdx.x == 0) G(p.status)->prof[slot] += t_ - prof_t0;  \
-    prof_t0 = t_;                                                           \
-  } while (0)
-#else
-#define PROF_DECL
-#define PROF_MARK(slot)
-#endif
-
 struct StepCtx {
   uint32_t mode, proximity, min_s, max_s, cfg;
   uint32_t n_list;       // slots of the current list
@@ -213,17 +200,7 @@ __device__ __forceinline__ void ctx_set_geometry(StepCtx& c) {
 enum { FAST_DONE = 0, FAST_SLOW = 1, FAST_OVERFLOW = 2, FAST_AGAIN = 3, FAST_REPROPOSE = 4, FAST_SEQ = 5, FAST_WIDEN = 6,
        FAST_ABORT = 7, FAST_TAIL = 8, FAST_TINY = 9, FAST_RANOUT = 10 };
 
-#ifdef PM_CARVE_PROF_FINE
-#define PROF_COUNT(slot) do { if (lane == 0) G(p.status)->prof[slot] += 1; } while (0)
-#else
-#define PROF_COUNT(slot)
-#endif
-#define FAST_RETURN(code) do { c_ref = c; seed_cur = cur; return (code); } while (0)
-#ifdef PM_CARVE_PROF  // why a step went to the exact sweep: 20 no proposal, 21 debug hook, 25 row exhausted, 31 certificate
-#define SLOW_RETURN(why) do { if (lane == 0) G(p.status)->prof[why] += 1; FAST_RETURN(FAST_SLOW); } while (0)
-#else
-#define SLOW_RETURN(why) FAST_RETURN(FAST_SLOW)
-#endif
+#define FAST_RETURN(code) do { c_ref = c; seed_cur = cur; return (code); } while (0)  // (SLOW_RETURN(why): FAST_SLOW, counted — pm_measure.inc)
 
 // The proposals of a batch as the validating wave sees them: seed number i (rank among the live located slots below
 // prop_limit at preparation time, ascending slot order) -> its slot (seed_slots, dense) and its row.
@@ -470,21 +447,11 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
     const bool alive = lane < n_k && alive_at(slot);
     const uint64_t am = __ballot(alive);
     const uint32_t rank = __popcll(am & ((1ull << lane) - 1ull));
-#ifdef PM_CARVE_PROF  // (timeline of the streaming carve: a row that ran out — entries, live ones, wanted, flags)
-    if (STREAM && (uint32_t)__popcll(am) < want && lane == 0 && p.stream_trace) {
-      const uint32_t ti_ = atomicAdd(&p.stream_ctl[SC_TRACE], 1u);
-      if (ti_ < PM_STREAM_TRACE_CAP) {
-        p.stream_trace[2u * ti_] = __builtin_amdgcn_s_memtime();
-        p.stream_trace[2u * ti_ + 1u] = 14ull | ((unsigned long long)((n_k | ((uint32_t)__popcll(am) << 8) | (want << 16)) & 0xFFFFFFu) << 8) |
-                                        ((unsigned long long)(nk_word >> 16) << 32);
-      }
-    }
-#endif
+    // (timeline of the streaming carve: a row that ran out — entries, live ones, wanted, flags)
+    PM_PROF(if (STREAM && (uint32_t)__popcll(am) < want && lane == 0) STREAM_TRACE(14, n_k | ((uint32_t)__popcll(am) << 8) | (want << 16), nk_word >> 16);)
     if ((uint32_t)__popcll(am) < want) {  // row exhausted by earlier groups
       if (STREAM) {  // (the streaming carve wants to know: the rows requested along with this one are as old)
-#ifdef PM_CARVE_PROF
-        if (lane == 0) G(p.status)->prof[25] += 1;
-#endif
+        PM_PROF(if (lane == 0) G(p.status)->prof[25] += 1;)
         FAST_RETURN(FAST_RANOUT);
       }
       SLOW_RETURN(25);
@@ -843,9 +810,6 @@ __device__ __noinline__ void carve_chain_collect(const CarveArgs& p, const StepC
             staged += 1u;
             k = kn;
             re = re_n;
-#ifdef CHAIN_COLLECT_SLOWER  // (a measuring build: is the collector on the carve's critical path?  tools/gpu_run.sh ... variants:)
-            __builtin_amdgcn_s_sleep(CHAIN_COLLECT_SLOWER);
-#endif
           }
           t2 += n;
           cc_st(&L.CC[CC_TAIL], t2);  // room for the producer
@@ -909,15 +873,7 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
     }
     return b;
   };
-#ifdef PM_CARVE_PROF
-  uint64_t ct = __builtin_amdgcn_s_memtime(), ct_wait = 0, ct_steps = 0, ct_stop = 0;
-  uint32_t cn_outer = 0, cn_dead = 0, cn_wait = 0;
-#define CH_MARK(var) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); var += t_ - ct; ct = t_; } while (0)
-#define CH_COUNT(var) (++var)
-#else
-#define CH_MARK(var)
-#define CH_COUNT(var)
-#endif
+  CH_DECL;
 
   // ---- start the producer and the collector
   if (lane == 0u) {
@@ -933,9 +889,6 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
   if (lane == 0u) cc_st(&L.CC[CC_CMD], cmd_seq | CH_RUN);
   uint32_t tail = 0u, budget = 0u;
   bool aborted = false;
-#ifdef PM_CHAIN_PRIO
-  __builtin_amdgcn_s_setprio(3);  // (the chain is the critical path; the waves beside it only feed it)
-#endif
   if (n_seeds > 0u) {
     for (;;) {
       CH_COUNT(cn_outer);
@@ -1006,9 +959,7 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
           n_cand -= live ? group_n : 0u;
           commits += live ? 1u : 0u;
           budget -= live ? 1u : 0u;
-#ifdef PM_CARVE_PROF
-          cn_dead += live ? 0u : 1u;
-#endif
+          PM_PROF(cn_dead += live ? 0u : 1u;)
         } while (s < n_steps);
         if (good) break;
         // ---- a live seed that needs a second look (its row is loaded: ra, rb, m2, a)
@@ -1071,9 +1022,6 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
       if (stop) break;
     }
   }
-#ifdef PM_CHAIN_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
   // ---- stop the other two (they must be off the key array before it is used again; the collector writes out first)
   cmd_seq += 4u;
   if (lane == 0u) cc_st(&L.CC[CC_CMD], cmd_seq | CH_STOP);
@@ -1101,20 +1049,7 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
   // sum over the commits of the live candidates before each: base, base - g, base - 2g, ...
   c.cand_sum += (unsigned long long)commits * base_cand -
                 (unsigned long long)group_n * ((unsigned long long)commits * (commits ? commits - 1u : 0u) / 2ull);
-#ifdef PM_CARVE_PROF
-  if (lane == 0u) {
-    unsigned long long* pr = (unsigned long long*)p.status->prof;
-    pr[1] += 1u;        // calls
-    pr[2] += commits;
-    pr[4] += action == FAST_SLOW ? 1u : 0u;
-    pr[16] += ct_wait;
-    pr[17] += ct_stop;
-    pr[18] += ct_steps;
-    pr[19] += cn_outer;
-    pr[23] += cn_dead;
-    pr[24] += cn_wait;
-  }
-#endif
+  CH_BOOK();
   c_ref = c;
   seed_cur = exit_cur;
   return action;

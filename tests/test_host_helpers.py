@@ -435,3 +435,32 @@ def test_tuning_flags_compile_together(tmp_path):
     assert "PM_EXP_" not in srcs.replace("PM_EXP_DEFINES", "")
     out = B.build(force=True, defines=flags, out=str(tmp_path / "libpm_engine_exp.so"))
     assert os.path.getsize(out) > 500_000
+
+
+def test_measuring_code_stays_out_of_the_kernel_bodies():
+    """The carve kernels read straight: what the measuring builds add (PM_CARVE_PROF, PM_ROW_REC, PM_ROW_BENCH,
+    PM_BATCH_LOG, PM_TIMEOUT_DIAG) lives in pm_measure.inc, and a kernel body names it in one line.  So the five kernel
+    files hold no preprocessor conditional but a tuning knob's default (#ifndef X / #define X ...), the choice that hangs
+    on STREAM_LA_SMALL_NUM, and the row bench's kernel — one marked block, the last thing in pm_stream.inc.  Text only:
+    nothing is compiled."""
+    from protocol_amd import build as B
+    assert "pm_measure.inc" in B.HEADERS
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")
+    bad = []
+    for name in ("pm_stream.inc", "pm_validate.inc", "pm_propose.inc", "pm_prep.inc", "pm_carve_kernel.inc"):
+        lines = open(os.path.join(B.CSRC, name)).read().split("\n")
+        for i, line in enumerate(lines):
+            m = cond.match(line)
+            if not m:
+                continue
+            kind, rest = m.group(1), m.group(2).split("//")[0].strip()
+            if kind == "ifndef" and re.match(r"\s*#\s*define\s+" + re.escape(rest) + r"\b", lines[i + 1]):
+                continue  # a knob's default
+            if kind == "if" and re.match(r"STREAM_LA_SMALL_NUM\s*==", rest):
+                continue
+            if name == "pm_stream.inc" and kind == "ifdef" and rest == "PM_ROW_BENCH" and "measuring builds only" in lines[i - 1]:
+                end = next(j for j in range(i + 1, len(lines)) if re.match(r"\s*#\s*endif\b", lines[j]))
+                assert not "".join(lines[end + 1:]).strip(), "the row bench's block is the last thing in pm_stream.inc"
+                continue
+            bad.append(f"{name}:{i + 1}: {line.strip()}")
+    assert not bad, bad

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Phase breakdown of the carve kernel: builds a PM_CARVE_PROF variant of the library (s_memtime ticks
-accumulated per phase by thread 0) and runs cold full-swarm matches on BASELINE configs[1]."""
+accumulated per phase by thread 0: PROF_MARK, protocol_amd/csrc/pm_measure.inc) and runs cold full-swarm matches on BASELINE
+configs[1]."""
 import ctypes as C
 import os
 import sys

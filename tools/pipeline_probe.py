@@ -3,6 +3,7 @@
 issued by the ticketer -> seen by a row maker -> row stored -> its block's rows all there (parker) -> parked in the chain's ring ->
 taken up by a batch of the chain.  Per configuration: the latencies of the stages, what stands between the chain and its next
 entry, and a time-sliced view of the window (tickets issued / taken up / rows stored / entries parked / consumed / commits).
+The records are PROP_REC_ROW, PARK_REC_* and CHAIN_REC_* in protocol_amd/csrc/pm_measure.inc.
 
     PM_EXP_LIB=protocol_amd/variants/libpm_engine_rowrec.so python tools/pipeline_probe.py [T W] [--slice US] [--configs 0,2]
 """

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""A neighbour row made by ONE wave alone on a CU (a -DPM_ROW_BENCH build: carve_row_bench_kernel), after a match of configs[1]:
+"""A neighbour row made by ONE wave alone on a CU (a -DPM_ROW_BENCH build: carve_row_bench_kernel at the end of
+pm_stream.inc, its modes PM_ROWB in pm_measure.inc), after a match of configs[1]:
     PM_EXP_LIB=protocol_amd/variants/libpm_engine_rowbench.so python tools/row_bench.py [config index ...]
 cycles per row and per candidate, the split seed columns / sweep / finish, a checksum of the row (variant builds that take pieces out
 of the row maker show in it)."""

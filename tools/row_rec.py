@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the rows of a streaming carve cost their waves, from a measuring build (-DPM_ROW_REC: eight time stamps per ticket,
 plain stores, nothing shared between the waves — the PM_CARVE_PROF build's counters are atomics on a handful of words and
-slow the rows they count):  PM_EXP_LIB=protocol_amd/variants/libpm_engine_rowrec.so python tools/row_rec.py [T W]"""
+slow the rows they count; the record is PROP_REC_ROW in protocol_amd/csrc/pm_measure.inc):  PM_EXP_LIB=protocol_amd/variants/libpm_engine_rowrec.so python tools/row_rec.py [T W]"""
 import ctypes as C
 import os
 import sys

@@ -5,7 +5,8 @@ accumulated per phase) and runs cold full-swarm matches.
     python tools/stream_prof.py [T W]          default 100000 10000 (BASELINE configs[1]); 1000000 100000 = configs[2]
 
 What the validator's workgroup did (chain wave / producer wave), what a row cost the proposer waves by the way it was
-made, and what the configuration boundaries cost.  Environment: PM_STREAM_WGS, PM_STREAM_LA, PM_STREAM_LA_DIV.
+made, and what the configuration boundaries cost (the marks and who owns which prof word: protocol_amd/csrc/pm_measure.inc).
+Environment: PM_STREAM_WGS, PM_STREAM_LA, PM_STREAM_LA_DIV.
 """
 import ctypes as C
 import os

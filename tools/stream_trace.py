@@ -5,7 +5,8 @@
 
 Per configuration: when it was entered, when its run started, when the first row was parked, the chain's waits (start,
 length, entry), how the rows arrived.  Times in microseconds from the first event (s_memtime ticks / ticks-per-us, the
-latter calibrated against the carve's hipEvent time).
+latter calibrated against the carve's hipEvent time).  The events and their numbers: STREAM_TRACE in
+protocol_amd/csrc/pm_measure.inc.
 """
 import ctypes as C
 import os
