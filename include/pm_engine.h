@@ -582,6 +582,8 @@ int32_t pm_device_task_column(pm_engine*, uint64_t* device_ptr, uint32_t* n);
  *   - the pair sweep + chooser + claim run for the OWNED workers only; the published rows are all-gathered once
  *     per tick and scattered into every rank's full table (the "cross-shard conflict-resolution all-gather");
  *   - pm_match_per_task bids with the owned workers only; the caller folds the per-task bests (min index / sum).
+ * The carve has no notion of rank: pm_form_groups on an engine configured with world > 1 runs the same replicated
+ * carve as the stepwise tick and forms the reference's groups.
  * The collectives are the caller's (RCCL ncclAllGather, or torch.distributed): the engine hands out device
  * pointers.  recv = [world][bytes_per_rank]; send = this rank's contribution (bytes_per_rank bytes); issue
  * all-gather(send -> recv) on the engine's stream (pm_set_stream) and call the next step.  bytes_per_rank == 0:

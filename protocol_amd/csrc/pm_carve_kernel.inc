@@ -100,7 +100,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
         st->n_eligible = n;
         st->total_available = n;
         st->cur_ci = start_ci;
-        st->need_prep = 1u;
         st->g_lo = st->g_hi = st->n_groups;
       }
       return;
@@ -146,7 +145,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
       c.n_list = 0;
       c.prop_k = 0;
       c.prop_limit = 0;
-      c.rows_pr = 0;
       c.n_seeds = 0;
       for (; ci < p.n_avail; ++ci) {
         c.min_s = p.min_size[ci];
@@ -174,7 +172,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
         // PM_PROP_MAX_SEEDS-th located one (a later round covers the rest)
         uint32_t n_seeds = 0;
         c.prop_limit = carve_prop_limit(p, red, c.n_list, &n_seeds);
-        c.rows_pr = (n_seeds + p.dist_world - 1u) / p.dist_world;
         c.n_seeds = n_seeds;
       }
       prepared = true;
@@ -185,7 +182,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
       c.n_list = d.n_list;
       c.prop_k = d.prop_k;
       c.prop_limit = d.prop_limit;
-      c.rows_pr = d.rows_pr;
       c.n_seeds = d.n_seeds;
       c.min_s = p.min_size[ci];
       c.max_s = p.max_size[ci];
@@ -193,7 +189,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
       c.n_list = st->n_list;
       c.prop_k = st->prop_k;
       c.prop_limit = st->prop_limit;
-      c.rows_pr = st->rows_pr;
       c.n_seeds = st->n_seeds;
       c.min_s = p.min_size[ci];
       c.max_s = p.max_size[ci];
@@ -308,11 +303,9 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_kernel(const CarveArgs* _
     st->n_list = c.n_list;
     st->prop_k = c.prop_k;
     st->prop_limit = c.prop_limit;
-    st->rows_pr = c.rows_pr;
     st->n_seeds = c.n_seeds;
     st->total_available = c.total_available;
     if (ext) {
-      st->need_prep = exit_state == CARVE_STATE_RUNNING ? 1u : 0u;
       st->g_lo = groups_at_entry;
       st->g_hi = c.n_groups;
     }

@@ -220,21 +220,18 @@ struct CarveStatus {
   uint32_t n_groups;     // records written so far (in/out)
   uint32_t n_members;    // member slots used so far (in/out)
   uint32_t steps_total;  // committed steps over all launches of this tick
-  uint32_t stop_seed;    // worker index of the seed of the uncertain step (diagnostic)
   uint32_t n_eligible;   // length of the eligible list
   uint32_t cur_ci;       // prepared configuration (position in the carve order); n_avail = none left
-  unsigned long long cand_sum;  // sum over committed steps of the candidates scanned
   uint32_t n_list;       // slots of the prepared candidate list
+  unsigned long long cand_sum;  // sum over committed steps of the candidates scanned
   uint32_t prop_k;       // entries per proposal for the prepared configuration (0 = no proposals)
   uint32_t prop_limit;   // proposals exist for located slots below this slot number
-  uint32_t rows_pr;      // rows per rank of this batch in the proposal buffer: ceil(seeds / world)
   uint32_t n_seeds;      // seeds of the batch
   uint32_t total_available;
   uint32_t fast_steps;   // steps committed from proposals
   uint32_t slow_steps;   // steps that needed the full key sweep
   uint32_t n_solo;       // single-node groups carved (the merge pass only runs when there are two or more)
   uint32_t n_props;      // neighbour lists computed by this rank's proposer
-  uint32_t need_prep;    // (external preparation) the next candidate list has not been prepared yet
   uint32_t g_lo, g_hi;   // groups appended by the last validation launch (their group_of is written by the prep kernels)
   uint32_t n_batches;    // validation launches that had a prepared list to run (the host sizes its next queue by it)
   uint32_t n_void;       // validation launches whose batch had been prepared for another configuration, or for nothing
@@ -261,28 +258,26 @@ struct CarveStatus {
   unsigned long long prof[64];  // PM_CARVE_PROF builds: accumulated s_memtime ticks per phase
 };
 
-// A proposal batch as its preparation describes it (carve_plan_kernel + carve_prep_*_kernel write it, the proposer
-// and the validator read it).  A batch may be prepared while the batch in front of it is still being validated —
-// from a snapshot of the position bitmap, for the configuration the carve is expected to be at — so the validator
-// accepts it only if it started from the configuration the carve really is at (ci0), and treats what has been
-// removed since the snapshot as dead slots.
-struct BatchDesc {
+// The proposal batch as its preparation describes it: carve_prep_count_kernel plans it from the carve's own state
+// (plan_batch) and carve_prep_place_kernel fills it in; the proposer and the validator read it.  There is one batch
+// at a time, prepared behind the validation launch in front of it on the same stream.  The host queues these
+// launches without looking, so the validator takes a batch only if it started from the configuration the carve is
+// at (ci0); a launch that finds another is void (CarveStatus::n_void).
+struct alignas(16) BatchDesc {  // (48 bytes, not 44: the host clears it with ONE fill, a size off 8 bytes takes two)
   uint32_t planned;          // the plan ran (the carve was RUNNING)
   uint32_t ci0;              // configuration (position in the carve order) the preparation started from
   uint32_t total_available;  // as of the plan (an upper bound of what the validator will find)
   uint32_t valid;            // a candidate list was prepared: configuration `ci`, the first from ci0 on that can be entered
   uint32_t none;             // no configuration from ci0 on can be entered any more
-  uint32_t ci, n_list, prop_k, prop_limit, rows_pr, n_seeds;
+  uint32_t ci, n_list, prop_k, prop_limit, n_seeds;
   uint32_t cell_g;           // the proposals of this batch walk the spatial index (grid size; 0 = sweep the whole list)
 };
 
 struct CarveArgs {
   uint32_t mode;   // CARVE_MODE_*
-  uint32_t _flags_unused;
   uint32_t W;
   uint32_t proximity;
   uint32_t debug_uncertain_every;
-  uint32_t _pad_re;
   // worker columns
   const uint32_t* wflags;
   const double *lat, *lon, *coslat;
@@ -313,15 +308,12 @@ struct CarveArgs {
   uint32_t _pad0;
   // proposals (carve_propose_kernel): one row of PM_PROP_ROW u64 per seed of the batch — the flags word (PM_ROW_*)
   // in word 0, then the packed keys sorted ascending.  Seed i of a batch (rank among the live located slots
-  // below prop_limit) belongs to rank i % world and is row i / world of that rank's segment; `prop` holds all
-  // segments back to back ([world][rows_pr] rows — what the all-gather delivers), `prop_send` is this rank's
-  // segment (the same memory as `prop` when world == 1).
+  // below prop_limit) has row i.  Every engine makes all rows of its own carve: a multi-GPU engine carves the
+  // whole pool like a single one, and the carve knows no rank.
   uint64_t* prop;
-  uint64_t* prop_send;
   uint64_t* seed_map;      // per bitmap word below prop_limit: the batch's seeds (live & located at preparation)
   uint32_t* seed_prefix;   // per bitmap word: seeds in front of the word
   uint32_t* seed_slots;    // seed number -> slot (PM_PROP_MAX_SEEDS + 64 entries)
-  uint32_t dist_rank, dist_world;
   uint32_t count_keys, _pad_ck;  // proposer: count the keys it sweeps (bench bookkeeping)
   uint32_t* prep_block_counts;   // [blocks][PM_MAX_CONFIGS] live compatible positions per block and configuration
   uint32_t* prep_counts;         // [PM_MAX_CONFIGS] totals, [PM_MAX_CONFIGS] = finished-blocks ticket

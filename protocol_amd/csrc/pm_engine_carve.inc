@@ -96,11 +96,8 @@ static int32_t fill_carve_args(pm_engine* e, CarveArgs* a, uint32_t mode, uint32
   HIPCHK(e->d_slot_wid.ensure(cap));
   HIPCHK(e->d_c_site.ensure(cap));
   HIPCHK(e->d_cc_site.ensure(cap));
-  {  // proposal rows: at most PM_PROP_MAX_SEEDS + 63 seeds per batch, dealt round-robin over the ranks
-    const size_t world = e->dist_world;
-    const size_t rows_pr = (size_t(PM_PROP_MAX_SEEDS) + 64 + world - 1) / world;
-    HIPCHK(e->d_prop.ensure(rows_pr * world * PM_PROP_ROW));
-    if (world > 1) HIPCHK(e->d_prop_send.ensure(rows_pr * PM_PROP_ROW));
+  {  // proposal rows: at most PM_PROP_MAX_SEEDS + 63 seeds per batch
+    HIPCHK(e->d_prop.ensure((size_t(PM_PROP_MAX_SEEDS) + 64) * PM_PROP_ROW));
     HIPCHK(e->d_seed_map.ensure((cap + 63) / 64 + 64));
     HIPCHK(e->d_seed_prefix.ensure((cap + 63) / 64 + 64));
     HIPCHK(e->d_seed_slots.ensure(size_t(PM_PROP_MAX_SEEDS) + 128));
@@ -108,11 +105,11 @@ static int32_t fill_carve_args(pm_engine* e, CarveArgs* a, uint32_t mode, uint32
     HIPCHK(e->d_prep_counts.ensure(PM_MAX_CONFIGS + 8));
   }
   HIPCHK(e->d_status.ensure(1));
-  HIPCHK(e->d_carve_args.ensure(2));
-  HIPCHK(e->d_desc.ensure(2));
+  HIPCHK(e->d_carve_args.ensure(1));
+  HIPCHK(e->d_desc.ensure(1));
   const uint32_t stride = uint32_t((cap + 63) / 64);
   HIPCHK(e->d_bits.ensure(size_t(stride) * 4));
-  HIPCHK(e->d_snap.ensure(size_t(stride) * 2));
+  HIPCHK(e->d_snap.ensure(stride));
   if (stream) {
     HIPCHK(e->d_c_pack.ensure(cap * 4));
     HIPCHK(e->d_cs_pack.ensure(cap * 4));
@@ -179,12 +176,9 @@ static int32_t fill_carve_args(pm_engine* e, CarveArgs* a, uint32_t mode, uint32
   a->c_site = e->d_c_site.p;
   a->cc_site = e->d_cc_site.p;
   a->prop = e->d_prop.p;
-  a->prop_send = e->dist_world > 1 ? e->d_prop_send.p : e->d_prop.p;
   a->seed_map = e->d_seed_map.p;
   a->seed_prefix = e->d_seed_prefix.p;
   a->seed_slots = e->d_seed_slots.p;
-  a->dist_rank = e->dist_rank;
-  a->dist_world = e->dist_world;
   a->count_keys = e->cfg.time_proposer ? 1u : 0u;
   a->prep_block_counts = e->d_prep_block_counts.p;
   a->prep_counts = e->d_prep_counts.p;
@@ -349,11 +343,10 @@ static void host_mark(const char* what) {
 }
 
 // One try_form_new_groups run (mod.rs:478-628) as a resumable sequence, so the same code serves the
-// single-GPU tick (launches queued blindly, status read when they are done) and the stepwise multi-GPU tick
-// (one status read per proposal batch, the all-gather of the batch's rows issued by the caller in between).
+// single-GPU tick and the stepwise multi-GPU tick, whose ranks each run the whole carve (launches queued blindly,
+// status read when they are done).
 struct FormRun {
   CarveArgs a;
-  BatchDesc desc[2] = {};   // the batch descriptors as of the last poll
   CarveStatus st;
   std::vector<uint32_t> avail;
   uint32_t g0 = 0, m0 = 0, start_ci = 0;
@@ -363,9 +356,7 @@ struct FormRun {
   uint32_t n_bound = 0;  // rows outside any group when the carve starts (>= the eligible list): sizes the prep grids
   uint32_t n_elig_hint = 0;  // the eligible ones among them, by the host mirror
   bool stream = false;       // one streaming launch (carve_stream_kernel) instead of the batch pipeline
-  bool single_call = true;   // run_form drives the whole carve (the stepwise multi-GPU tick exchanges rows per batch)
   uint32_t stream_wgs = 0;   // proposer workgroups of the streaming launch
-  bool local_carve = false;  // the multi-GPU tick: this rank carves the whole pool itself (every rank does, and ends with the same groups)
   bool rearmed = false;      // the carve took more than its first launch sequence (host-resolved step, aborted streaming launch)
   uint32_t stage_cap = 0;    // streaming carve: entries of each staging array carve_finish_kernel fills in pinned host memory
   bool args_pending = false; // `a` is not on the device yet: the first kernel of the launch sequence takes it up as its own argument
@@ -381,7 +372,7 @@ static int32_t form_queue_init(pm_engine* e, FormRun* r, bool fresh = false) {
   fresh = fresh && r->use_props;  // (the proposal-free carve's one launch reads the status it is handed)
   if (!fresh) HIPCHK(hipMemcpyAsync(e->d_status.p, &r->st, sizeof(r->st), hipMemcpyHostToDevice, e->stream));
   if (r->use_props) {
-    if (!r->stream) HIPCHK(hipMemsetAsync(e->d_desc.p, 0, 2 * sizeof(BatchDesc), e->stream));  // (the batch pipeline's descriptors)
+    if (!r->stream) HIPCHK(hipMemsetAsync(e->d_desc.p, 0, sizeof(BatchDesc), e->stream));  // (the batch pipeline's descriptor)
     // the ordered eligible list, and the spatial index of its positions when there are enough of them to matter
     const uint32_t index_min = !r->a.prune_mode ? 0u : r->a.prune_mode >= 2u ? 1u : PM_CELL_AUTO_N;
     if (r->stream) {
@@ -419,11 +410,9 @@ static int32_t form_queue_init(pm_engine* e, FormRun* r, bool fresh = false) {
   return PM_OK;
 }
 
-// local_carve: a rank of the multi-GPU tick — the carve is replicated, not exchanged (see pm_dist_tick_begin): the launches
-// are those of one GPU whatever dist_world says
 // begin_ev: an event the caller has recorded behind everything in front of the carve (nothing is queued between it and the
 // carve's first kernel here): it brackets the carve's kernels instead of a record of its own — a record is a barrier packet
-static int32_t form_begin(pm_engine* e, FormRun* r, bool allow_pipeline, bool local_carve = false, hipEvent_t begin_ev = nullptr) {
+static int32_t form_begin(pm_engine* e, FormRun* r, hipEvent_t begin_ev = nullptr) {
   int32_t rc = absorb_groups(e);  // a match that failed half-way may have left the last carve unabsorbed
   if (rc) return rc;
   rc = ensure_compat(e);
@@ -465,13 +454,10 @@ static int32_t form_begin(pm_engine* e, FormRun* r, bool allow_pipeline, bool lo
   r->st.state = CARVE_STATE_RUNNING;
   r->st.n_groups = r->g0;
   r->st.n_members = r->m0;
-  r->single_call = allow_pipeline;
-  r->local_carve = local_carve;
   r->use_props = e->cfg.carve_variant != 1 && e->cfg.proximity_enabled;
-  // The streaming carve: one engine, one call, positions that fit the validator's LDS bitmaps.  Everything else (the
-  // stepwise multi-GPU tick, swarms beyond 262,144 unassigned rows) goes through the batch pipeline.
-  r->stream = r->single_call && r->use_props && e->cfg.carve_variant == 0 && (e->dist_world == 1 || r->local_carve) &&
-              r->n_bound <= PM_CARVE_BIG_SLOTS &&
+  // The streaming carve: positions that fit the validator's LDS bitmaps.  Everything else (swarms beyond 262,144
+  // unassigned rows) goes through the batch pipeline.
+  r->stream = r->use_props && e->cfg.carve_variant == 0 && r->n_bound <= PM_CARVE_BIG_SLOTS &&
               !e->debug_mem_above;  // (the test hook for the all-in-HBM lists is the batch pipeline's)
   host_mark("form: begin (host mirrors counted)");
   rc = form_setup_args(e, r);
@@ -524,11 +510,6 @@ static int32_t form_setup_args(pm_engine* e, FormRun* r) {
     a.stage_mem = e->h_gstage + size_t(3) * r->stage_cap;
     a.h_status = e->h_status;
     e->h_status->state = 0xFFFFFFFFu;  // (not yet written by this carve)
-  }
-  if (r->local_carve) {  // (rows are made here for every seed: no segment of another rank's to wait for)
-    a.dist_rank = 0;
-    a.dist_world = 1;
-    a.prop_send = a.prop;
   }
   a.n_avail = uint32_t(r->avail.size());
   for (size_t i = 0; i < r->avail.size(); ++i) {
@@ -586,10 +567,6 @@ static int32_t form_poll(pm_engine* e, FormRun* r) {
   for (;;) {
     HIPCHK(hipEventRecord(e->kev[3], e->stream));
     HIPCHK(hipMemcpyAsync(&r->st, e->d_status.p, sizeof(r->st), hipMemcpyDeviceToHost, e->stream));
-    // (the batch descriptors: on the engine's stream with the status — a blocking copy on the null stream was a second
-    // driver round trip per poll; the streaming carve has none)
-    const bool want_desc = r->use_props && !r->stream;
-    if (want_desc) HIPCHK(hipMemcpyAsync(r->desc, e->d_desc.p, sizeof(r->desc), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     {
       float ms = 0;
@@ -630,7 +607,7 @@ static int32_t form_poll(pm_engine* e, FormRun* r) {
     rc = form_queue_init(e, r);
     if (rc) return rc;
     // read the status again: the INIT launch prepares the next list (and, without proposals, runs on to the end
-    // or the next stop) — the caller sizes the batch's exchange from what it reports
+    // or the next stop)
   }
 }
 
@@ -764,7 +741,7 @@ static int32_t run_form_rest(pm_engine* e, FormRun& r, uint32_t* n_formed, bool 
 
 static int32_t run_form(pm_engine* e, uint32_t* n_formed, bool defer_absorb = false) {
   FormRun r;
-  int32_t rc = form_begin(e, &r, /*allow_pipeline=*/true);
+  int32_t rc = form_begin(e, &r);
   if (rc) return rc;
   return run_form_rest(e, r, n_formed, defer_absorb);
 }

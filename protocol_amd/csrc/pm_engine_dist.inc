@@ -93,7 +93,7 @@ int32_t pm_dist_tick_begin(pm_engine* e) {
   // The carve is REPLICATED: every rank runs the whole of it — the streaming launch, as on one GPU — and ends with the
   // identical groups and ids, because the result does not depend on how the launch went (which rows arrived when), only
   // on the reference's rule: nothing is exchanged until the published table (DESIGN.md section 7).
-  rc = form_begin(e, e->form, /*allow_pipeline=*/true, /*local_carve=*/true);
+  rc = form_begin(e, e->form);
   if (rc) {
     dist_abort(e);
     return rc;

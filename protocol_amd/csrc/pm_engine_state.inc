@@ -50,7 +50,7 @@ struct pm_engine {
   std::vector<double> h_lat, h_lon;
   std::vector<uint32_t> h_site;  // equal (lat, lon) bit patterns <=> equal site id
   DevBuf<uint32_t> d_site, d_c_site, d_cc_site, d_seed_prefix, d_seed_slots, d_prep_block_counts, d_prep_counts;
-  DevBuf<uint64_t> d_prop, d_prop_send, d_seed_map;
+  DevBuf<uint64_t> d_prop, d_seed_map;
   uint32_t tick_fast_steps = 0;
   DevBuf<uint32_t> d_flags, d_gpu_count, d_gpu_mem, d_gpu_cls, d_cpu_cores, d_ram, d_storage, d_addr_rank;
   DevBuf<double> d_lat, d_lon, d_coslat, d_ux, d_uy, d_uz;
@@ -137,10 +137,9 @@ struct pm_engine {
   DevBuf<uint64_t> d_c_compat, d_keys, d_bits;
   DevBuf<uint32_t> d_slot_pos, d_slot_wid;
   DevBuf<CarveStatus> d_status;
-  DevBuf<CarveArgs> d_carve_args;   // [2]: one argument block per proposal batch in flight (the second one only
-                                    // differs in the per-batch scratch, see CarveSet)
-  DevBuf<BatchDesc> d_desc;         // [2]
-  DevBuf<uint64_t> d_snap;          // [2][stride] position-bitmap snapshots of the preparations
+  DevBuf<CarveArgs> d_carve_args;   // the carve's argument block
+  DevBuf<BatchDesc> d_desc;         // the proposal batch in preparation or under validation
+  DevBuf<uint64_t> d_snap;          // [stride] the position bitmap as the preparation saw it
   // spatial index of a carve's located positions (cell_*_kernel)
   DevBuf<uint32_t> d_cell_cnt, d_cell_start, d_pos_cell, d_pos_rank, d_cs_of_pos, d_cs_slot, d_cs_site;
   DevBuf<double> d_cs_u[3];

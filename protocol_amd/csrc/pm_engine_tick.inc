@@ -91,7 +91,7 @@ int32_t pm_tick(pm_engine* e, pm_stats* stats) {
   // The host copy of the new groups is built while the pair sweep runs, unless the merge pass needs it.
   host_mark("tick: compat queued");
   FormRun r;
-  rc = form_begin(e, &r, /*allow_pipeline=*/true, /*local_carve=*/false, /*begin_ev=*/e->ev[1]);  // (the end of the compat phase IS the carve's begin)
+  rc = form_begin(e, &r, /*begin_ev=*/e->ev[1]);  // (the end of the compat phase IS the carve's begin)
   if (rc) return rc;
   // ---- the streaming carve: everything behind it is queued BEFORE the host waits for any of it.  The carve's last
   // kernel has completed the group records on the device (ids, empty task words) and written their host copy and the
@@ -264,7 +264,7 @@ int32_t pm_tick_many(pm_engine* const* engines, uint32_t n, pm_stats* stats, uin
       HIPCHK(hipEventRecord(e->ev[1], e->stream));
       runs[i].reset(new (std::nothrow) FormRun());
       if (!runs[i]) return set_error(PM_ENOMEM, "out of host memory");
-      return form_begin(e, runs[i].get(), /*allow_pipeline=*/true);
+      return form_begin(e, runs[i].get());
     };
     const int32_t rc = stage();
     if (rc) failed(i, rc);

@@ -212,7 +212,6 @@ __global__ __launch_bounds__(256) void carve_prep_place_kernel(const CarveArgs* 
     d->n_list = n_list;
     d->prop_k = prop_k;
     d->prop_limit = limit;
-    d->rows_pr = (n_seeds + p.dist_world - 1u) / p.dist_world;
     d->n_seeds = n_seeds;
     d->cell_g = cell_g;
     d->valid = 1u;
@@ -382,7 +381,6 @@ __global__ __launch_bounds__(256) void carve_elig_place_kernel(const CarveArgs* 
     st->n_eligible = n;
     st->total_available = n;  // mod.rs:503
     st->cur_ci = start_ci;
-    st->need_prep = 1u;
     st->g_lo = st->g_hi = st->n_groups;
   }
 }

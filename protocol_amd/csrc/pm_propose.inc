@@ -803,8 +803,7 @@ __global__ __launch_bounds__(256) void carve_propose_kernel(const CarveArgs* __r
   const auto D = G((const BatchDesc*)p.desc);
   if (!D->planned || !D->valid) return;
   const uint32_t K = D->prop_k, n_list = D->n_list;
-  const uint32_t world = p.dist_world, my_rank = p.dist_rank;
-  const auto prop_out = G(p.prop_send);
+  const auto prop_out = G(p.prop);
   if (K == 0 || n_list > PM_CARVE_BIG_SLOTS) return;
   const uint32_t SB = n_list > PM_CARVE_SLOTS ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS;
   const double TIE_BAND = n_list > PM_CARVE_SLOTS ? PM_TIE_BAND_BIG : PM_TIE_BAND;
@@ -814,18 +813,16 @@ __global__ __launch_bounds__(256) void carve_propose_kernel(const CarveArgs* __r
   const auto loc = G((const uint64_t*)p.bits_scratch) + p.bits_stride;
   const uint32_t lw = (n_list + 63u) >> 6;
   // ---- the neighbour rows.  Four seeds per workgroup (one per wave) sweep the candidate list together,
-  // tile by tile through LDS.  The seeds of the batch are dealt round-robin over the ranks: this rank computes
-  // seed numbers my_rank, my_rank + world, ...
+  // tile by tile through LDS.
   __shared__ TileBuf tiles[2];
   const uint32_t tid = threadIdx.x, wave = tid >> 6;
   const uint32_t n_seeds = D->n_seeds, cell_g = D->cell_g;
-  const uint32_t n_my = world > 1u ? (n_seeds > my_rank ? (n_seeds - my_rank + world - 1u) / world : 0u) : n_seeds;
   const uint32_t n_tiles = (n_list + PROP_TILE - 1u) / PROP_TILE;
   const auto seed_slots = G((const uint32_t*)p.seed_slots);
-  for (uint32_t k0 = blockIdx.x * 4u; k0 < n_my; k0 += gridDim.x * 4u) {
-    const uint32_t out_row = k0 + wave;  // row in this rank's send segment
-    const bool valid = out_row < n_my;
-    const uint32_t s = valid ? seed_slots[world > 1u ? my_rank + world * out_row : out_row] : 0u;
+  for (uint32_t k0 = blockIdx.x * 4u; k0 < n_seeds; k0 += gridDim.x * 4u) {
+    const uint32_t out_row = k0 + wave;  // seed number = row
+    const bool valid = out_row < n_seeds;
+    const uint32_t s = valid ? seed_slots[out_row] : 0u;
     const uint32_t ssite = G(p.cc_site)[s];
     const SeedGeo sg = {G(p.cc_lat)[s], G(p.cc_lon)[s], G(p.cc_cos)[s], G(p.cc_ux)[s], G(p.cc_uy)[s], G(p.cc_uz)[s]};
     const bool shared = (ssite & 0x80000000u) != 0u;

@@ -1306,7 +1306,6 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
       if (__ballot(bad)) uncertain = true;
     }
     if (uncertain) {
-      if (lane == 0u) G(p.status)->stop_seed = G(p.slot_wid)[seed];
       rc = STEP_UNCERTAIN;
       break;
     }
@@ -1584,7 +1583,6 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
       }
     }
     if (uncertain) {
-      if (lane == 0u) G(p.status)->stop_seed = G(p.slot_wid)[seed];
       rc = STEP_UNCERTAIN;
       break;
     }
@@ -2333,7 +2331,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_stream_kernel(const Carve
       c.n_cand = n_cand;
       c.prop_k = (p.proximity && c.max_s - 1u < PM_PROP_KMAX) ? PM_PROP_KMAX : 0u;
       c.prop_limit = n;
-      c.rows_pr = 0;
       c.n_seeds = PM_NONE;  // (carve_chain: "the list is used up" = no ticket)
       uint32_t switch_at = 0u;
       const uint32_t mode = c.prop_k ? row_mode(n_cand, &switch_at) : SROW_BITMAP;
@@ -2462,7 +2459,6 @@ __global__ __launch_bounds__(CARVE_THREADS) void carve_stream_kernel(const Carve
     st->cur_ci = exit_state == CARVE_STATE_DONE ? p.n_avail : ci;
     st->n_list = n;
     st->total_available = c.total_available;
-    st->need_prep = 0u;
     st->g_lo = groups_at_entry;
     st->g_hi = c.n_groups;
     st->fast_steps += c.fast_steps;

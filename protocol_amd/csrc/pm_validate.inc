@@ -182,7 +182,6 @@ struct StepCtx {
   unsigned long long cand_sum;
   // proposals (0 = none)
   uint32_t prop_k, prop_limit;
-  uint32_t rows_pr;  // rows per rank in the proposal buffer for this batch: ceil(seeds / world)
   uint32_t n_seeds;  // seeds of the batch
   bool use_props;
   // packed-key geometry of the current list: low slot_bits of a key hold the slot; certificate band
@@ -203,10 +202,7 @@ enum { FAST_DONE = 0, FAST_SLOW = 1, FAST_OVERFLOW = 2, FAST_AGAIN = 3, FAST_REP
 #define FAST_RETURN(code) do { c_ref = c; seed_cur = cur; return (code); } while (0)  // (SLOW_RETURN(why): FAST_SLOW, counted — pm_measure.inc)
 
 // The proposals of a batch as the validating wave sees them: seed number i (rank among the live located slots below
-// prop_limit at preparation time, ascending slot order) -> its slot (seed_slots, dense) and its row.
-__device__ __forceinline__ uint32_t prop_row_of(uint32_t i, uint32_t world, uint32_t rows_pr) {
-  return world > 1u ? (i % world) * rows_pr + i / world : i;
-}
+// prop_limit at preparation time, ascending slot order) -> its slot (seed_slots, dense); its row is row i of `prop`.
 
 // Fast steps one at a time, executed by wave 0 alone while the other waves are parked at a barrier: the expensive
 // part of a step (keys for every live candidate + top-k) was done for every possible seed by
@@ -236,7 +232,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
   const auto seed_slots = G((const uint32_t*)p.seed_slots);
   const uint32_t cap_groups = p.cap_groups, cap_members = p.cap_members;
   const uint32_t dbg_every = p.debug_uncertain_every;
-  const uint32_t world = UNI(p.dist_world), rows_pr = UNI(c.rows_pr), n_seeds = UNI(c.n_seeds);
+  const uint32_t n_seeds = UNI(c.n_seeds);
   constexpr uint32_t SB = BIG ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS;
   constexpr uint64_t SLOT_MASK = (1ull << SB) - 1ull;
   constexpr uint64_t noloc_key = (PM_KEY_NOLOC >> SB) << SB;
@@ -416,7 +412,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
     // seed are listed (FORM; a swept row — a walk's leaves out the ones at the seed's own site only): a live one in front
     // of it would have been the seed, so at this moment — the only one a row is read at — nothing is missing, and a
     // row flagged complete lists everything that is alive.
-    const size_t rbase = STREAM ? (size_t)(cur & (PM_STREAM_RQ - 1u)) * 64u : (size_t)prop_row_of(cur, world, rows_pr) * PM_PROP_ROW;
+    const size_t rbase = STREAM ? (size_t)(cur & (PM_STREAM_RQ - 1u)) * 64u : (size_t)cur * PM_PROP_ROW;
     uint32_t nk_word;
     if (STREAM) {  // (granule 0: the flags word under the ticket's tag — a row that never arrived does not carry it)
       const unsigned long long g0 = __hip_atomic_load(&G(p.stream_row_lo)[rbase], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -617,7 +613,7 @@ __device__ __noinline__ void carve_chain_produce(const CarveArgs& p, const StepC
   const auto rows32 = G((const uint32_t*)p.prop);  // row r: 2 * PM_PROP_ROW words; its compact slot list (flags word,
                                                    // slot of entry 0, 1, ...) starts at word 2 * PM_PROP_SLOTS
   const auto seed_slots = G((const uint32_t*)p.seed_slots);
-  const uint32_t world = UNI(p.dist_world), rows_pr = UNI(c.rows_pr), n_seeds = UNI(c.n_seeds);
+  const uint32_t n_seeds = UNI(c.n_seeds);
   uint32_t seen = 0u;  // last command word acted on
   for (;;) {
     uint32_t cmd = chain_wait_cmd(L, seen);
@@ -658,7 +654,7 @@ __device__ __noinline__ void carve_chain_produce(const CarveArgs& p, const StepC
             const uint32_t sp = (uint32_t)__builtin_amdgcn_readlane((int)q, (int)l);
             pidx_v = lane == k ? si : pidx_v;
             ppos_v = lane == k ? sp : ppos_v;
-            prow[k] = rows32[(size_t)prop_row_of(si, world, rows_pr) * (2u * PM_PROP_ROW) + 2u * PM_PROP_SLOTS + lane];
+            prow[k] = rows32[(size_t)si * (2u * PM_PROP_ROW) + 2u * PM_PROP_SLOTS + lane];
             cpos = si + 1u;
           }
         }
@@ -1257,10 +1253,7 @@ __device__ __noinline__ int carve_exact_step(const CarveArgs& p, BlockRed& red, 
   uint32_t any = 0;
 #pragma unroll
   for (uint32_t k = 0; k < CARVE_WAVES; ++k) any |= red.flag[k];
-  if (any) {
-    if (tid == 0) G(p.status)->stop_seed = l_wid[seed];
-    return STEP_UNCERTAIN;
-  }
+  if (any) return STEP_UNCERTAIN;
   if (c.n_groups >= p.cap_groups || c.mem_off + total > p.cap_members) return STEP_OVERFLOW;
 
   // ---- commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585): selected slots =
@@ -1513,10 +1506,7 @@ __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, St
       if (fabs(a - a_m) <= band && (G(p.cc_lat)[s] != mlat || G(p.cc_lon)[s] != mlon)) uncertain = 1;
     }
   }
-  if (__syncthreads_or(uncertain)) {
-    if (tid == 0) G(p.status)->stop_seed = wid[seed];
-    return STEP_UNCERTAIN;
-  }
+  if (__syncthreads_or(uncertain)) return STEP_UNCERTAIN;
   if (c.n_groups >= p.cap_groups || c.mem_off + total > p.cap_members) return STEP_OVERFLOW;
   for (uint32_t s = tid; s < c.n_list; s += CARVE_THREADS) {
     if (!bit_at(alive, s)) continue;

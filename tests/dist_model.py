@@ -47,7 +47,6 @@ class ModelLocal:
         self.proximity = proximity
         self.max_seeds, self.min_cap = max_seeds, min_cap
         self.rank, self.world = 0, 1
-        self.c_rank, self.c_world = 0, 1      # (who makes which row of a batch: this rank, all of them)
         self.batches = 0
 
     # ---------------------------------------------------------------- ownership
@@ -94,7 +93,7 @@ class ModelLocal:
         self.loc = sw.has_loc[self.lst].copy()
         self.n_cand = n
         self.prop_k = 0
-        self.seeds, self.seed_no, self.limit, self.rows_pr = [], {}, 0, 0
+        self.seeds, self.seed_no, self.limit = [], {}, 0
         if self.proximity and mx - 1 < ROW - 1:
             self.prop_k = min(mx - 1 + 48, ROW - 1)
             cap = max(self.min_cap, n // 10 if n > 8192 else n // 5)
@@ -104,7 +103,6 @@ class ModelLocal:
             self.limit = min(self.limit, n)
             self.seeds = [int(s) for s in located if s < self.limit]
             self.seed_no = {s: i for i, s in enumerate(self.seeds)}
-            self.rows_pr = (len(self.seeds) + self.c_world - 1) // self.c_world
 
     def _sorted_others(self, seed):
         """every live candidate but the seed, by (distance to the seed, slot) — sort_nodes_by_proximity
@@ -121,33 +119,25 @@ class ModelLocal:
 
     def carve_wait(self):
         while not self.done:   # every batch's rows made and used by this rank
-            _more, send, recv = self._carve_next_batch()
-            if send is not None:
-                recv.copy_(send)
+            self._make_rows()
             self.carve_validate()
 
-    def _carve_next_batch(self):
-        if self.done:
-            return False, None, None
+    def _make_rows(self):
+        """the neighbour rows of the batch's seeds: seed number i has row i"""
+        self.rows = None
         if not self.prop_k or not self.seeds:
-            return True, None, None
+            return
         self.batches += 1
-        send = torch.full((self.rows_pr * ROW,), -1, dtype=torch.int64)
+        self.rows = np.full((len(self.seeds), ROW), -7, dtype=np.int64)
         for i, s in enumerate(self.seeds):
-            if i % self.c_world != self.c_rank:
-                continue
             near = self._sorted_others(s)
             row = np.full(ROW, -1, dtype=np.int64)
             k = min(self.prop_k, len(near))
             row[:k] = near[:k]
             row[ROW - 1] = 1 if len(near) <= self.prop_k else 0     # the row holds every live candidate
-            j = i // self.c_world
-            send[j * ROW:(j + 1) * ROW] = torch.from_numpy(row)
-        self.recv = torch.full((self.c_world * self.rows_pr * ROW,), -7, dtype=torch.int64)
-        return True, send, self.recv
+            self.rows[i] = row
 
     def carve_validate(self):
-        recv = self.recv.numpy() if self.prop_k and self.seeds else None
         while True:
             if not (self.total_available >= self.mn and self.n_cand >= self.mn and self.n_cand > 0):
                 break                                                     # mod.rs:507, :517-519
@@ -161,9 +151,7 @@ class ModelLocal:
                     self._prepare()                                       # beyond the batch: next batch, same config
                     return
                 if self.prop_k:
-                    i = self.seed_no[seed]
-                    r0 = ((i % self.c_world) * self.rows_pr + i // self.c_world) * ROW
-                    row = recv[r0:r0 + ROW]
+                    row = self.rows[self.seed_no[seed]]
                     assert row[ROW - 1] in (0, 1), "the seed's row was never made"
                     ent = row[:ROW - 1]
                     ent = ent[ent >= 0]

@@ -1,7 +1,7 @@
 """The N>1 path on CPU: world_size 2 and 3 over gloo, real torch.distributed collectives.
 
-Under test is protocol_amd.dist.ShardedEngine — the stepwise multi-GPU tick with its two kinds of exchange (the
-all-gather of each carve batch's neighbour rows, the all-gather of the owned workers' published rows) and the
+Under test is protocol_amd.dist.ShardedEngine — the stepwise multi-GPU tick with its one exchange (the all-gather
+of the owned workers' published rows; the carve is replicated on every rank and exchanges nothing) and the
 device-side fold of the per-task best bids.  The local compute of each rank is tests/dist_model.ModelLocal, a
 numpy model of the engine's stepwise protocol (the engine itself needs an MI355X; -m gpu tests run the same
 driver over libpm_engine.so).  The bar: every rank ends with exactly the groups, tasks and table of the

@@ -19,7 +19,7 @@ import torch
 
 from protocol_amd import engine as E
 from protocol_amd import host
-from protocol_amd.dist import EngineLocal, ShardedEngine
+from protocol_amd.dist import EngineLocal, ShardedEngine, shard_of
 from protocol_amd.swarm import baseline_config, make_swarm
 from helpers import engine_groups, oracle_groups, oracle_state_for
 
@@ -202,6 +202,33 @@ def test_in_process_ranks_follow_churn():
     for (g, t, s, _pt, _n) in _run_in_process(sw, 2, ticks=3, between=between):
         assert sorted(g) == sorted(g1) and np.array_equal(t["task"], t1["task"])
         assert np.array_equal(t["group_id"], t1["group_id"])
+
+
+@pytest.mark.parametrize("carve_variant", [0, 3])
+def test_form_groups_on_a_configured_rank_is_the_whole_carve(carve_variant):
+    """pm_form_groups / pm_merge_solo_groups on an engine configured as rank 1 of 2: the carve knows no rank, so the call
+    forms the reference's groups — the oracle's, and those of an engine that was never configured.  The swarm is
+    test_dist_gloo.py's; its oracle groups span several configurations, so the batch pipeline (carve_variant 3) runs
+    more than one proposal batch."""
+    sw = make_swarm(5, 400, 900)
+    st = oracle_state_for(sw, reference_shaped=False, group_id_seed=9)
+    n_formed, n_merged = st.try_form_new_groups(), st.try_merge_solo_groups()
+    want = [g[:3] for g in oracle_groups(st)]
+    assert len({cfg for _gid, cfg, _mem in want}) > 1
+    got = []
+    for configured in (True, False):
+        eng = E.Engine(group_id_seed=9, carve_variant=carve_variant)
+        host.load_swarm(eng, sw)
+        if configured:
+            eng.dist_configure(1, 2, shard_of(sw.address, 2))
+        assert eng.form_groups() == n_formed
+        if carve_variant == 3:
+            assert eng.debug_carve_counters()["batches"] > 1
+        assert eng.merge_solo_groups() == n_merged
+        got.append(engine_groups(eng))
+        eng.close()
+    assert [g[:3] for g in got[0]] == want, "the configured engine's groups differ from the oracle"
+    assert got[0] == got[1], "the configured engine's groups differ from an engine that was never configured"
 
 
 def _free_port() -> int:
