@@ -603,35 +603,19 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
   typedef chain_lds_u32 lds_u32;
   const ChainLds L = chain_lds(l_buf);
   chain_lds_u32* const SL = lds_pin<chain_lds_u32*>(sl_words);
-  const uint32_t dbg_every = UNI(p.debug_uncertain_every);
   const uint32_t dbg_abort = UNI(p.debug_abort_after);  // (test hook: pm_debug_stream_abort_after)
   const uint32_t n_seeds = PM_NONE;
-  const uint32_t n_list_v = UNI(c.n_list), n_start = UNI(c.n_start);
-  const uint32_t group_n = UNI(c.max_s), want = group_n - 1u;
-  const uint32_t cap_g = UNI(p.cap_groups), cap_m = UNI(p.cap_members);
-  const uint32_t step0 = UNI(steps_before) + UNI(c.steps);
-  const uint32_t base_cand = UNI(c.n_cand), base_groups = UNI(c.n_groups), base_mem = UNI(c.mem_off);
+  const ChainRun run = chain_run(p, c, steps_before);
+  const uint32_t group_n = run.group_n, want = group_n - 1u;
+  const uint32_t step0 = run.step0, base_cand = run.base_cand;
   uint32_t n_cand = base_cand, commits = 0;
   int action = FAST_SEQ;
   uint32_t exit_cur = n_seeds;  // where carve_fast_steps resumes its search for the first live seed
-  const uint32_t lw_bits = (n_list_v + 63u) >> 6;
+  const uint32_t lw_bits = (run.n_list + 63u) >> 6;
   uint32_t n_loc = UNI(stream_count_located(l_alive, l_loc, lw_bits, lane));  // located candidates alive (as of the last count)
-  // Commits that can follow one another before any of the conditions that end the chain can come true (they are
-  // looked at again when the budget is used up): candidates for full groups, room in the output arrays, the
-  // re-proposal threshold, the debug hook.  >= 1 whenever none of those conditions holds.
+  // chain_budget, and what only this chain stops for: the abort hook and the hand-over to stream_small
   auto budget_now = [&]() -> uint32_t {
-    uint32_t b = n_cand / group_n;
-    const uint32_t room_g = cap_g - (base_groups + commits), room_m = (cap_m - base_mem) / group_n - commits;
-    b = b < room_g ? b : room_g;
-    b = b < room_m ? b : room_m;
-    if (n_list_v > 256u) {
-      const uint32_t t = n_cand * PM_THIN_DIV >= n_start ? (n_cand * PM_THIN_DIV - n_start) / (PM_THIN_DIV * group_n) + 1u : 1u;
-      b = b < t ? b : t;
-    }
-    if (dbg_every) {
-      const uint32_t r = (step0 + commits + 1u) % dbg_every;
-      b = b < dbg_every - r ? b : dbg_every - r;
-    }
+    uint32_t b = chain_budget(run, n_cand, commits);
     if (dbg_abort) {
       const uint32_t r = dbg_abort > step0 + commits ? dbg_abort - (step0 + commits) : 0u;
       b = b < r ? b : r;
@@ -659,8 +643,8 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
     cc_st(&L.CC[CC_CUMSEQ], 0u);
     cc_st(&L.CC[CC_CUM], 0u);
     cc_st(&L.CC[CC_START], t0_run);
-    cc_st(&L.CC[CC_G0], base_groups);
-    cc_st(&L.CC[CC_M0], base_mem);
+    cc_st(&L.CC[CC_G0], run.base_groups);
+    cc_st(&L.CC[CC_M0], run.base_mem);
   }
   cmd_seq += 4u;
   if (lane == 0u) cc_st(&L.CC[CC_CMD], cmd_seq | CH_RUN);
@@ -742,26 +726,11 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
           action = FAST_ABORT;
           stop = true;
         } else {
-          // `while total_available >= min` with `compatible < min => break` (mod.rs:507,517-519) hold while full
-          // groups fit (max_s >= min_s); the last, partial group is carve_fast_steps' business
           n_loc = UNI(stream_count_located(l_alive, l_loc, lw_bits, lane));
-          if (n_loc <= STREAM_SMALL_AT) {
-            action = FAST_TINY;
-            stop = true;
-          } else if (n_cand < group_n) {
-            action = FAST_SEQ;
-            stop = true;
-          } else if (base_groups + commits >= cap_g || base_mem + (commits + 1u) * group_n > cap_m) {
-            action = FAST_OVERFLOW;
-            stop = true;
-          } else if (n_cand * PM_THIN_DIV < n_start && n_list_v > 256u && commits > 0u) {
-            // A good part of what was alive when the batch started is gone: the neighbour rows are thinning out.
-            // Re-prepare (compact) and re-propose now, before rows start running out of live entries.
-            if (lane == 0u) p.status->why[0] += 1u;
-            action = FAST_REPROPOSE;
-            stop = true;
-          } else if (dbg_every && ((step0 + commits + 1u) % dbg_every) == 0u) {
-            action = FAST_SLOW;
+          const int why = n_loc <= STREAM_SMALL_AT ? FAST_TINY : chain_stop_reason(run, n_cand, commits);
+          if (why != FAST_AGAIN) {
+            if (why == FAST_REPROPOSE && lane == 0u) p.status->why[0] += 1u;
+            action = why;
             stop = true;
           } else {
             budget = budget_now();
@@ -982,15 +951,7 @@ __device__ __noinline__ int stream_chain(const CarveArgs& p, StepCtx& c_ref, uin
     if (lane == 0u) cc_st(&L.CC[CC_ABORT], 1u);
     action = FAST_ABORT;  // a hand-shake inside the workgroup timed out: reported as CARVE_STATE_ABORTED (never seen)
   }
-  c.n_groups = base_groups + commits;
-  c.mem_off = base_mem + commits * group_n;
-  c.n_cand = n_cand;
-  c.total_available -= commits * group_n;
-  c.steps += commits;
-  c.fast_steps += commits;
-  // sum over the commits of the live candidates before each: base, base - g, base - 2g, ...
-  c.cand_sum += (unsigned long long)commits * base_cand -
-                (unsigned long long)group_n * ((unsigned long long)commits * (commits ? commits - 1u : 0u) / 2ull);
+  chain_book(c, run, commits, n_cand);
   CH_BOOK(CH_FINE_WORDS);
   PM_REC(if (lane == 0u) p.stream_ctl[SC_BATCHES] = rec_batches;)
   if (lane == 0u) STREAM_TRACE(7, action, commits);
@@ -1161,24 +1122,14 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
   constexpr uint64_t SLOT_MASK = (1ull << SB) - 1ull;
   constexpr double band_rel = BIG ? PM_TIE_BAND_BIG : PM_TIE_BAND;
   // (everything the loop reads from the argument block is read HERE: behind a store the compiler re-reads whatever it
-  // cannot prove unaliased, and a read of the argument block is a round trip to L2 in the middle of a selection round;
-  // and what is the same in every lane is said to be: a divergent loop counter turns the loop into predicated code)
+  // cannot prove unaliased, and a read of the argument block is a round trip to L2 in the middle of a selection round)
   const auto freeg = G((unsigned long long*)p.bits_scratch);
   const auto mem_g = G(p.members);
   const auto gcfg_g = G(p.g_cfg);
   const auto gn_g = G(p.g_n);
   const auto goff_g = G(p.g_off);
   const uint32_t cap_g = UNI(p.cap_groups), cap_m = UNI(p.cap_members), dbg_every = UNI(p.debug_uncertain_every);
-  c.n_list = UNI(c.n_list);
-  c.n_cand = UNI(c.n_cand);
-  c.total_available = UNI(c.total_available);
-  c.min_s = UNI(c.min_s);
-  c.max_s = UNI(c.max_s);
-  c.n_groups = UNI(c.n_groups);
-  c.mem_off = UNI(c.mem_off);
-  c.steps = UNI(c.steps);
-  c.fast_steps = UNI(c.fast_steps);
-  c.cfg = UNI(c.cfg);
+  ctx_uniform(c);
   const bool prox = UNI(c.proximity) != 0u;
   n_cl = UNI(n_cl);
   steps_before = UNI(steps_before);
@@ -1208,8 +1159,8 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
   if (lane == 0u) STREAM_TRACE(15, n_cl, c.n_cand);
   SM_DECL;
   for (;;) {
-    if (!(c.total_available >= c.min_s && c.n_cand >= c.min_s && c.n_cand > 0u)) break;  // mod.rs:507, 517-519
-    if (!(prox && n_loc > 0u)) {  // first-come from here on (mod.rs:553-561): the whole workgroup's business
+    if (!step_open(c)) break;
+    if (!(prox && n_loc > 0u)) {  // first-come from here on: the whole workgroup's business
       rc = STEP_CONTINUE;
       break;
     }
@@ -1217,9 +1168,9 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
       rc = STEP_AGAIN;
       break;
     }
-    const uint32_t want = c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;  // fill to max (mod.rs:545-551)
-    const bool room = c.n_groups < cap_g && c.mem_off + want + 1u <= cap_m;
-    // ---- the seed: the first candidate WITH a location (mod.rs:526-530)
+    const uint32_t want = step_want(c);
+    const bool room = step_room(c, want + 1u, cap_g, cap_m);
+    // ---- the seed: the first candidate WITH a location
     uint32_t smin = 0xFFFFFFFFu;
 #pragma unroll
     for (uint32_t j = 0; j < CPL; ++j) smin = ((alive[j] >> lane) & 1ull) && s[j] < smin ? s[j] : smin;
@@ -1279,11 +1230,12 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
     if (total < c.min_s) break;  // mod.rs:564-566
     // ---- exactness certificate for the distance-ordered part (see carve_exact_step): only when the LAST selected
     // candidate has a location — otherwise every located one is in, and nothing is left to decide
-    bool uncertain = dbg_every && ((steps_before + c.steps + 1u) % dbg_every) == 0u;
+    bool uncertain = step_forced(dbg_every, steps_before + c.steps);
     if (n_sel > 0u && need_unl == 0u) {
       const uint64_t last_key = (last >> SB) << SB;
       const double a_m = __longlong_as_double((long long)last_key);
-      const double band = a_m * band_rel + 1e-300;
+      bool unsafe;
+      const double band = cert_band(a_m, band_rel, unsafe);
       const uint32_t last_s = (uint32_t)(last & SLOT_MASK);
       double mlat = 0.0, mlon = 0.0;
 #pragma unroll
@@ -1295,7 +1247,7 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
           mlon = __longlong_as_double((long long)readlane_u64((uint64_t)__double_as_longlong(lon[j]), l));
         }
       }
-      if (a_m > PM_A_MAX_SAFE) uncertain = true;
+      if (unsafe) uncertain = true;
       bool bad = false;
 #pragma unroll
       for (uint32_t j = 0; j < CPL; ++j) {
@@ -1314,7 +1266,7 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
       break;
     }
     SM_MARK(3);
-    // ---- commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585)
+    // ---- commit
 #pragma unroll
     for (uint32_t j = 0; j < CPL; ++j) {
       const uint64_t kill = selm[j] | __ballot(s[j] == seed);
@@ -1324,46 +1276,13 @@ __device__ __noinline__ int stream_small_n(const CarveArgs& p, StepCtx& c_ref, u
       }
       alive[j] &= ~kill;
     }
-    if (need_unl) {  // the lowest live location-less slots (every word below uw holds none for good)
-      uint32_t cnt = 0u;
-      bool first = true;
-      for (uint32_t jb = uw; jb < lw && cnt < need_unl; jb += 64u) {  // 64 words a look, a lane each
-        const uint32_t jl = jb + lane;
-        const uint64_t wl = jl < lw ? (l_alive[jl] & ~l_loc[jl]) : 0ull;
-        uint64_t nz = __ballot(wl != 0ull);
-        if (nz && first) {
-          uw = jb + (uint32_t)__builtin_ctzll(nz);
-          first = false;
-        }
-        for (; nz && cnt < need_unl; nz &= nz - 1ull) {
-          const uint32_t src = (uint32_t)__builtin_ctzll(nz), j = jb + src;
-          const uint64_t w = readlane_u64(wl, src);
-          const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
-          const bool take_me = ((w >> lane) & 1ull) && rk < need_unl - cnt;
-          const uint64_t take = __ballot(take_me);
-          if (take_me) mem_g[c.mem_off + 1u + n_sel + cnt + rk] = j * 64u + lane;
-          if (lane == 0u) {
-            __hip_atomic_fetch_and(&l_alive[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_and(&freeg[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          cnt += (uint32_t)__popcll(take);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the bitmap words are read again by the next step)
-    }
+    if (need_unl) fill_location_less(l_alive, l_loc, freeg, mem_g, c.mem_off + 1u + n_sel, need_unl, lw, lane, uw);
     if (lane == 0u) {
       mem_g[c.mem_off] = seed;
-      gcfg_g[c.n_groups] = c.cfg;
-      gn_g[c.n_groups] = total;
-      goff_g[c.n_groups] = c.mem_off;
+      step_record(gcfg_g, gn_g, goff_g, c.n_groups, c.cfg, total, c.mem_off);
     }
     n_loc -= 1u + n_sel;
-    c.n_groups += 1u;
-    c.mem_off += total;
-    c.cand_sum += c.n_cand;
-    c.n_cand -= total;
-    c.total_available -= total;  // mod.rs:586
-    c.steps += 1u;
+    step_book(c, total);
     c.fast_steps += 1u;  // (not an exact sweep of the workgroup: counted with the steps that came from rows)
     SM_MARK(4);
     PM_PROF(++sm_n;)
@@ -1484,16 +1403,7 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
   const auto gn_g = G(p.g_n);
   const auto goff_g = G(p.g_off);
   const uint32_t cap_g = UNI(p.cap_groups), cap_m = UNI(p.cap_members), dbg_every = UNI(p.debug_uncertain_every);
-  c.n_list = UNI(c.n_list);
-  c.n_cand = UNI(c.n_cand);
-  c.total_available = UNI(c.total_available);
-  c.min_s = UNI(c.min_s);
-  c.max_s = UNI(c.max_s);
-  c.n_groups = UNI(c.n_groups);
-  c.mem_off = UNI(c.mem_off);
-  c.steps = UNI(c.steps);
-  c.fast_steps = UNI(c.fast_steps);
-  c.cfg = UNI(c.cfg);
+  ctx_uniform(c);
   const bool prox = UNI(c.proximity) != 0u;
   n_cl = UNI(n_cl);
   steps_before = UNI(steps_before);
@@ -1518,14 +1428,14 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
   if (lane == 0u) STREAM_TRACE(15, n_cl, c.n_cand);
   PM_PROF(const uint64_t sr_t0 = PM_TICKS(); const uint32_t sr_g0 = c.n_groups;)  // (the steps on rows are booked as selection time)
   for (;;) {
-    if (!(c.total_available >= c.min_s && c.n_cand >= c.min_s && c.n_cand > 0u)) break;  // mod.rs:507, 517-519
-    if (!(prox && n_loc > 0u)) {  // first-come from here on (mod.rs:553-561): the whole workgroup's business
+    if (!step_open(c)) break;
+    if (!(prox && n_loc > 0u)) {  // first-come from here on: the whole workgroup's business
       rc = STEP_CONTINUE;
       break;
     }
-    const uint32_t want = c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;  // fill to max (mod.rs:545-551)
-    const bool room = c.n_groups < cap_g && c.mem_off + want + 1u <= cap_m;
-    // ---- the seed: the first candidate WITH a location (mod.rs:526-530) = the lowest live index; its row
+    const uint32_t want = step_want(c);
+    const bool room = step_room(c, want + 1u, cap_g, cap_m);
+    // ---- the seed: the first candidate WITH a location = the lowest live index; its row
     const uint32_t si = (uint32_t)__builtin_ctzll(alive);
     {  // its row: made by a helper wave a step or two ago — or on its way, or (never seen) by nobody: then here
       uint32_t sp_n = 0u;
@@ -1561,13 +1471,14 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
     if (total < c.min_s) break;  // mod.rs:564-566
     // ---- exactness certificate for the distance-ordered part (see carve_exact_step): only when the LAST selected
     // candidate has a location — otherwise every located one is in, and nothing is left to decide
-    bool uncertain = dbg_every && ((steps_before + c.steps + 1u) % dbg_every) == 0u;
+    bool uncertain = step_forced(dbg_every, steps_before + c.steps);
     if (n_sel > 0u && need_unl == 0u) {
       const uint32_t lane_m = 63u - (uint32_t)__builtin_clzll(selm);  // (ascending row: the last selected is the highest)
       const uint64_t last = readlane_u64(rk, lane_m);
       const double a_m = __longlong_as_double((long long)((last >> SB) << SB));
-      const double band = a_m * band_rel + 1e-300;
-      if (a_m > PM_A_MAX_SAFE) uncertain = true;
+      bool unsafe;
+      const double band = cert_band(a_m, band_rel, unsafe);
+      if (unsafe) uncertain = true;
       const bool near = live && fabs(__longlong_as_double((long long)((rk >> SB) << SB)) - a_m) <= band;
       if (__ballot(near) & ~(1ull << lane_m)) {  // someone beside it within the band: at its coordinates?
         const uint32_t im = (uint32_t)last & 63u;
@@ -1590,7 +1501,7 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
       rc = STEP_OVERFLOW;
       break;
     }
-    // ---- commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585): candidate c goes when its place
+    // ---- commit: candidate c goes when its place
     // in the row is among the selected, and the seed
     const uint64_t kill = __ballot(in && lane != si && ((selm >> iv) & 1ull)) | (1ull << si);
     if ((kill >> lane) & 1ull) {
@@ -1599,46 +1510,13 @@ __device__ __noinline__ int stream_small_rows(const CarveArgs& p, StepCtx& c_ref
     }
     alive &= ~kill;
     if (lane == 0u) __hip_atomic_store(alive_pub, alive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (for the helpers)
-    if (need_unl) {  // the lowest live location-less slots (every word below uw holds none for good)
-      uint32_t cnt = 0u;
-      bool first = true;
-      for (uint32_t jb = uw; jb < lw && cnt < need_unl; jb += 64u) {  // 64 words a look, a lane each
-        const uint32_t jl = jb + lane;
-        const uint64_t wl = jl < lw ? (l_alive[jl] & ~l_loc[jl]) : 0ull;
-        uint64_t nz = __ballot(wl != 0ull);
-        if (nz && first) {
-          uw = jb + (uint32_t)__builtin_ctzll(nz);
-          first = false;
-        }
-        for (; nz && cnt < need_unl; nz &= nz - 1ull) {
-          const uint32_t src = (uint32_t)__builtin_ctzll(nz), j = jb + src;
-          const uint64_t w = readlane_u64(wl, src);
-          const uint32_t rk2 = __builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
-          const bool take_me = ((w >> lane) & 1ull) && rk2 < need_unl - cnt;
-          const uint64_t take = __ballot(take_me);
-          if (take_me) mem_g[c.mem_off + 1u + n_sel + cnt + rk2] = j * 64u + lane;
-          if (lane == 0u) {
-            __hip_atomic_fetch_and(&l_alive[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_and(&freeg[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          cnt += (uint32_t)__popcll(take);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the bitmap words are read again by the next step)
-    }
+    if (need_unl) fill_location_less(l_alive, l_loc, freeg, mem_g, c.mem_off + 1u + n_sel, need_unl, lw, lane, uw);
     if (lane == 0u) {
       mem_g[c.mem_off] = seed;
-      gcfg_g[c.n_groups] = c.cfg;
-      gn_g[c.n_groups] = total;
-      goff_g[c.n_groups] = c.mem_off;
+      step_record(gcfg_g, gn_g, goff_g, c.n_groups, c.cfg, total, c.mem_off);
     }
     n_loc -= 1u + n_sel;
-    c.n_groups += 1u;
-    c.mem_off += total;
-    c.cand_sum += c.n_cand;
-    c.n_cand -= total;
-    c.total_available -= total;  // mod.rs:586
-    c.steps += 1u;
+    step_book(c, total);
     c.fast_steps += 1u;  // (not an exact sweep of the workgroup: counted with the steps that came from rows)
   }
   if (lane == 0u) cc_st(&ctl[SRW_QUIT], 1u);  // (the helpers leave: on to the caller's barrier)
@@ -1784,7 +1662,7 @@ __device__ __noinline__ int stream_run_config(const CarveArgs& p, BlockRed& red,
         if (rt != STEP_CONTINUE) return rt;
       }
       // no located candidate is left: the first-come tail, in one go
-      if (!((c.total_available >= c.min_s) && c.n_cand >= c.min_s && c.n_cand > 0u)) return STEP_BREAK;
+      if (!step_open(c)) return STEP_BREAK;
       const int ta = stream_first_come(p, red, c, l_alive, l_stage);
       if (tid == 0) STREAM_TRACE(12, (uint32_t)ta, c.steps);
       if (ta == FAST_DONE) return STEP_BREAK;

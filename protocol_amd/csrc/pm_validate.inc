@@ -201,6 +201,200 @@ enum { FAST_DONE = 0, FAST_SLOW = 1, FAST_OVERFLOW = 2, FAST_AGAIN = 3, FAST_REP
 
 #define FAST_RETURN(code) do { c_ref = c; seed_cur = cur; return (code); } while (0)  // (SLOW_RETURN(why): FAST_SLOW, counted — pm_measure.inc)
 
+// a proposal batch ends (the list is compacted and re-proposed) once fewer than 1 / PM_THIN_DIV of the slots that were
+// alive when its validation started are left; a batch prepared beside the one in front of it is not worth validating
+// when less than 1 / PM_STALE_DIV of its list is still alive (the next one is prepared from the state as it is then)
+#ifndef PM_THIN_DIV
+#define PM_THIN_DIV 3u
+#endif
+#ifndef PM_STALE_DIV
+#define PM_STALE_DIV 3u
+#endif
+
+// ---- The step rule: one step of the reference's try_form_new_groups (mod.rs:507-586), said once for every stepper
+// of this file and of pm_stream.inc.  A stepper differs in where its keys come from and in how many waves work on it;
+// what follows it shares with the others.
+//   step_open    a configuration takes another step `while total_available >= min` (mod.rs:507), unless fewer than min
+//                are compatible (`compatible < min => break`, :517-519).  The merge pass has no pool to count:
+//                `while remaining_groups.len() >= min` (:695).
+//   step_want    a seed wants max - 1 neighbours, or everyone that is left: fill to max (:545-551).  A group of fewer
+//                than min is none (:564-566; the steppers that can come up short test that themselves).
+//   step_room    whether the output arrays hold another group of `total`: if not the launch ends and the host makes room.
+//   step_forced  the debug hook (pm_engine_config::debug_uncertain_every): every N-th step of a match goes to the host as if it
+//                could not be certified.  step_forced_in: the commits that fit in front of the next such step.
+//   cert_band    the certificate: the selection is the reference's if everyone within a relative band — plus an absolute
+//                one, for a key of 0 — around the last selected key sits at that candidate's coordinates (see "Ordering
+//                key" at the top); and no key near the antipode, where the reference's term can round above 1 and its
+//                distance is NaN: unsafe, the host settles it.
+//   step_record  what a commit writes, by one lane or thread (create_group_atomically, :299-322): the group's record.
+//                The members and the bitmaps (healthy_nodes.retain, :585) are the stepper's own.
+//   step_book    what a commit books (total_available -= group.len(), :586).  Steps that were no exact sweep count as
+//                fast_steps too: their steppers say so.
+//   chain_*      the two in-order chains (carve_chain, stream_chain) commit full groups without a look at the context:
+//                what a run starts from, how many commits may follow one another before one of the conditions above
+//                (or the re-proposal threshold) can come true, which of them ends the run, and the books of the run.
+//   first_live_bit, fill_location_less, ctx_uniform: the seed of a step without a seed list (the first located candidate,
+//                :526-530), the location-less candidates that fill a group in input order (:553-561; f64::MAX sorts
+//                behind every located one), and a context whose fields are said to be the same in every lane.
+__device__ __forceinline__ bool step_open(uint32_t total_available, uint32_t n_cand, uint32_t min_s, bool merge = false) {
+  return (merge || total_available >= min_s) && n_cand >= min_s && n_cand > 0u;
+}
+__device__ __forceinline__ bool step_open(const StepCtx& c, bool merge = false) {
+  return step_open(c.total_available, c.n_cand, c.min_s, merge);
+}
+__device__ __forceinline__ uint32_t step_want(const StepCtx& c) {
+  return c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;
+}
+__device__ __forceinline__ bool step_room(const StepCtx& c, uint32_t total, uint32_t cap_g, uint32_t cap_m) {
+  return c.n_groups < cap_g && c.mem_off + total <= cap_m;
+}
+__device__ __forceinline__ bool step_forced(uint32_t every, uint32_t steps_done) {
+  return every && ((steps_done + 1u) % every) == 0u;
+}
+__device__ __forceinline__ uint32_t step_forced_in(uint32_t every, uint32_t steps_done) {
+  return every ? every - (steps_done + 1u) % every : 0xFFFFFFFFu;
+}
+__device__ __forceinline__ double cert_band(double a_m, double band_rel, bool& unsafe) {
+  unsafe = a_m > PM_A_MAX_SAFE;
+  return a_m * band_rel + 1e-300;
+}
+template <typename P>
+__device__ __forceinline__ void step_record(P g_cfg, P g_n, P g_off, uint32_t g, uint32_t cfg, uint32_t n, uint32_t off) {
+  g_cfg[g] = cfg;
+  g_n[g] = n;
+  g_off[g] = off;
+}
+__device__ __forceinline__ void step_book(StepCtx& c, uint32_t total) {
+  c.n_groups += 1u;
+  c.mem_off += total;
+  c.cand_sum += c.n_cand;
+  c.n_cand -= total;
+  c.total_available -= total;
+  c.steps += 1u;
+}
+
+// what a run of a chain starts from (wave-uniform)
+struct ChainRun {
+  uint32_t group_n, cap_g, cap_m, dbg_every, n_list, n_start;
+  uint32_t step0;  // steps of the match in front of the run
+  uint32_t base_cand, base_groups, base_mem;
+};
+__device__ __forceinline__ ChainRun chain_run(const CarveArgs& p, const StepCtx& c, uint32_t steps_before) {
+  ChainRun r;
+  r.group_n = UNI(c.max_s);
+  r.cap_g = UNI(p.cap_groups);
+  r.cap_m = UNI(p.cap_members);
+  r.dbg_every = UNI(p.debug_uncertain_every);
+  r.n_list = UNI(c.n_list);
+  r.n_start = UNI(c.n_start);
+  r.step0 = UNI(steps_before) + UNI(c.steps);
+  r.base_cand = UNI(c.n_cand);
+  r.base_groups = UNI(c.n_groups);
+  r.base_mem = UNI(c.mem_off);
+  return r;
+}
+// Commits that can follow one another before any of the conditions that end a chain can come true (they are looked at
+// again when the budget is used up): candidates for full groups, room in the output arrays, the re-proposal
+// threshold, the debug hook.  >= 1 whenever none of those conditions holds.
+__device__ __forceinline__ uint32_t chain_budget(const ChainRun& r, uint32_t n_cand, uint32_t commits) {
+  uint32_t b = n_cand / r.group_n;
+  const uint32_t room_g = r.cap_g - (r.base_groups + commits), room_m = (r.cap_m - r.base_mem) / r.group_n - commits;
+  b = b < room_g ? b : room_g;
+  b = b < room_m ? b : room_m;
+  if (r.n_list > 256u) {
+    const uint32_t t = n_cand * PM_THIN_DIV >= r.n_start ? (n_cand * PM_THIN_DIV - r.n_start) / (PM_THIN_DIV * r.group_n) + 1u : 1u;
+    b = b < t ? b : t;
+  }
+  const uint32_t f = step_forced_in(r.dbg_every, r.step0 + commits);
+  return b < f ? b : f;
+}
+// Why a chain whose budget is used up stops in front of a live seed; FAST_AGAIN: it does not, and takes a new budget.
+// step_open holds while full groups fit (max_s >= min_s); the last, partial group is carve_fast_steps' business
+// (FAST_SEQ).  FAST_REPROPOSE: a good part of what was alive when the batch started is gone, the neighbour rows are
+// thinning out — re-prepare (compact) and re-propose now, before rows start running out of live entries.
+__device__ __forceinline__ int chain_stop_reason(const ChainRun& r, uint32_t n_cand, uint32_t commits) {
+  if (n_cand < r.group_n) return FAST_SEQ;
+  if (r.base_groups + commits >= r.cap_g || r.base_mem + (commits + 1u) * r.group_n > r.cap_m) return FAST_OVERFLOW;
+  if (n_cand * PM_THIN_DIV < r.n_start && r.n_list > 256u && commits > 0u) return FAST_REPROPOSE;
+  if (step_forced(r.dbg_every, r.step0 + commits)) return FAST_SLOW;
+  return FAST_AGAIN;
+}
+__device__ __forceinline__ void chain_book(StepCtx& c, const ChainRun& r, uint32_t commits, uint32_t n_cand) {
+  c.n_groups = r.base_groups + commits;
+  c.mem_off = r.base_mem + commits * r.group_n;
+  c.n_cand = n_cand;
+  c.total_available -= commits * r.group_n;
+  c.steps += commits;
+  c.fast_steps += commits;
+  // sum over the commits of the live candidates before each: base, base - g, base - 2g, ...
+  c.cand_sum += (unsigned long long)commits * r.base_cand -
+                (unsigned long long)r.group_n * ((unsigned long long)commits * (commits ? commits - 1u : 0u) / 2ull);
+}
+
+// lane j holds word j0 + j of a bitmap: the position of the first set bit of the 64 words, PM_NONE: none is set
+__device__ __forceinline__ uint32_t first_bit_of(uint64_t w, uint32_t j0) {
+  const uint64_t nz = __ballot(w != 0ull);
+  if (!nz) return PM_NONE;
+  const int src = __builtin_ctzll(nz);
+  return (j0 + src) * 64u + __builtin_ctzll(readlane_u64(w, src));
+}
+// the first position whose bit is set in both bitmaps (lw words each), PM_NONE: there is none
+template <typename PA, typename PB>
+__device__ __forceinline__ uint32_t first_live_bit(PA words, PB and_words, uint32_t lw, uint32_t lane) {
+  for (uint32_t j0 = 0; j0 < lw; j0 += 64u) {
+    const uint32_t j = j0 + lane;
+    const uint32_t pos = first_bit_of(j < lw ? (words[j] & and_words[j]) : 0ull, j0);
+    if (pos != PM_NONE) return pos;
+  }
+  return PM_NONE;
+}
+// The lowest `need` live location-less positions become members `mem_at` on and leave the bitmap and its published copy
+// (one wave, a lane a word, 64 words a look).  uw: the first word that may still hold one (every word below it holds
+// none for good).
+template <typename PA, typename PB, typename PF, typename PM>
+__device__ __forceinline__ void fill_location_less(PA l_alive, PB l_loc, PF freeg, PM mem_g, uint32_t mem_at, uint32_t need,
+                                                   uint32_t lw, uint32_t lane, uint32_t& uw) {
+  uint32_t cnt = 0u;
+  bool first = true;
+  for (uint32_t jb = uw; jb < lw && cnt < need; jb += 64u) {
+    const uint32_t jl = jb + lane;
+    const uint64_t wl = jl < lw ? (l_alive[jl] & ~l_loc[jl]) : 0ull;
+    uint64_t nz = __ballot(wl != 0ull);
+    if (nz && first) {
+      uw = jb + (uint32_t)__builtin_ctzll(nz);
+      first = false;
+    }
+    for (; nz && cnt < need; nz &= nz - 1ull) {
+      const uint32_t src = (uint32_t)__builtin_ctzll(nz), j = jb + src;
+      const uint64_t w = readlane_u64(wl, src);
+      const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(w >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)w, 0u));
+      const bool take_me = ((w >> lane) & 1ull) && rk < need - cnt;
+      const uint64_t take = __ballot(take_me);
+      if (take_me) mem_g[mem_at + cnt + rk] = j * 64u + lane;
+      if (lane == 0u) {
+        __hip_atomic_fetch_and(&l_alive[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_and(&freeg[j], ~take, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      cnt += (uint32_t)__popcll(take);
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the bitmap words are read again by the next step)
+}
+// (what is the same in every lane is said to be: a divergent loop counter turns a loop into predicated code)
+__device__ __forceinline__ void ctx_uniform(StepCtx& c) {
+  c.n_list = UNI(c.n_list);
+  c.n_cand = UNI(c.n_cand);
+  c.total_available = UNI(c.total_available);
+  c.min_s = UNI(c.min_s);
+  c.max_s = UNI(c.max_s);
+  c.n_groups = UNI(c.n_groups);
+  c.mem_off = UNI(c.mem_off);
+  c.steps = UNI(c.steps);
+  c.fast_steps = UNI(c.fast_steps);
+  c.cfg = UNI(c.cfg);
+}
+// ---- (the step rule ends here)
+
 // The proposals of a batch as the validating wave sees them: seed number i (rank among the live located slots below
 // prop_limit at preparation time, ascending slot order) -> its slot (seed_slots, dense); its row is row i of `prop`.
 
@@ -260,8 +454,8 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
   PROF_COUNT(20);  // calls
   for (;;) {
     if (done >= max_steps) FAST_RETURN(FAST_AGAIN);
-    if (!(c.total_available >= c.min_s && c.n_cand >= c.min_s && c.n_cand > 0)) FAST_RETURN(FAST_DONE);
-    // ---- seed (mod.rs:526-530): the first live located slot = the first live entry of the batch's seed list
+    if (!step_open(c)) FAST_RETURN(FAST_DONE);
+    // ---- seed: the first live located slot = the first live entry of the batch's seed list
     uint32_t f_loc = PM_NONE;
     if (c.proximity) {
       if (STREAM) {
@@ -283,18 +477,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
         }
         if (f_loc == PM_NONE) {
           cur = PM_NONE;
-          for (uint32_t j0 = 0; j0 < lw; j0 += 64u) {
-            const uint32_t j = j0 + lane;
-            const uint64_t ll = j < lw ? (A[j] & LOC[j]) : 0ull;
-            const uint64_t nz = __ballot(ll != 0ull);
-            if (nz) {
-              const int src = __builtin_ctzll(nz);
-              const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(ll >> 32), src) << 32) |
-                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ll, src);
-              f_loc = (j0 + src) * 64u + __builtin_ctzll(w);
-              break;
-            }
-          }
+          f_loc = first_live_bit(A, LOC, lw, lane);
         }
       } else if (c.prop_k) {
         while (cur < n_seeds) {
@@ -326,27 +509,16 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
           }
         }
       } else {
-        for (uint32_t j0 = 0; j0 < lw; j0 += 64u) {
-          const uint32_t j = j0 + lane;
-          const uint64_t ll = j < lw ? (A[j] & LOC[j]) : 0ull;
-          const uint64_t nz = __ballot(ll != 0ull);
-          if (nz) {
-            const int src = __builtin_ctzll(nz);
-            const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(ll >> 32), src) << 32) |
-                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ll, src);
-            f_loc = (j0 + src) * 64u + __builtin_ctzll(w);
-            break;
-          }
-        }
+        f_loc = first_live_bit(A, LOC, lw, lane);
       }
     }
-    const uint32_t want = c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;  // mod.rs:545-551
-    if (c.n_groups >= cap_groups || c.mem_off + want + 1u > cap_members) FAST_RETURN(FAST_OVERFLOW);
+    const uint32_t want = step_want(c);
+    if (!step_room(c, want + 1u, cap_groups, cap_members)) FAST_RETURN(FAST_OVERFLOW);
 
     if (STREAM && f_loc == PM_NONE) FAST_RETURN(FAST_TAIL);  // (the whole workgroup drains the tail: stream_first_come)
     if (f_loc == PM_NONE) {
       // no located candidate (or proximity off): the group is the first `want + 1` live slots in input
-      // order (mod.rs:553-561; a seed without location makes the sort a no-op, :238).
+      // order (a seed without location makes the sort a no-op, mod.rs:238).
       // Once there is no located candidate there never will be one again, so the rest of the configuration
       // is drained right here; these steps always take the lowest live slots, every word below fc_j is
       // empty for good, and the scan resumes where it stopped.
@@ -356,8 +528,8 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
       unsigned long long cand_sum = 0;
       int ret = FAST_DONE;
       for (;;) {
-        if (!(total_av >= min_s && n_cand >= min_s && n_cand > 0u)) break;
-        const uint32_t need = max_s < n_cand ? max_s : n_cand;  // want + 1 (mod.rs:545-551)
+        if (!step_open(total_av, n_cand, min_s)) break;
+        const uint32_t need = max_s < n_cand ? max_s : n_cand;  // want + 1
         if (n_groups >= cap_groups || mem_off + need > cap_members) {
           ret = FAST_OVERFLOW;
           break;
@@ -379,11 +551,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
           }
           cnt += __popcll(take);
         }
-        if (lane == 0) {
-          g_cfg[n_groups] = cfg;
-          g_n[n_groups] = cnt;
-          g_off[n_groups] = mem_off;
-        }
+        if (lane == 0) step_record(g_cfg, g_n, g_off, n_groups, cfg, cnt, mem_off);
         n_groups += 1;
         mem_off += cnt;
         cand_sum += n_cand;
@@ -405,7 +573,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
     PROF_COUNT(22);  // located sequential steps (attempts)
     const uint32_t seed = f_loc;
     if (c.prop_k == 0 || seed >= c.prop_limit || (STREAM && cur == PM_NONE)) {  SLOW_RETURN(20); }
-    if (dbg_every && ((steps_before + c.steps + 1u) % dbg_every) == 0u) SLOW_RETURN(21);
+    if (step_forced(dbg_every, steps_before + c.steps)) SLOW_RETURN(21);
 
     // ---- the seed's neighbour row: one packed key per lane, ascending.  Candidates with the seed's exact
     // coordinates are at distance 0 and head the row in slot order.  Of the located candidates only those behind the
@@ -457,8 +625,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
     if (want > 0 && !(row_clean && row_safe && (complete || tail_clear))) {
       const uint64_t lm = __ballot(sel && rank == want - 1u);
       const int lane_m = __builtin_ctzll(lm);
-      const uint64_t e_m = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(e >> 32), lane_m) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e, lane_m);
+      const uint64_t e_m = readlane_u64(e, lane_m);
       const uint64_t kb_m = (e_m >> SB) << SB;
       if (kb_m != noloc_key) {
         // exactness certificate: every live candidate of the row within the band AROUND the last selected one
@@ -466,8 +633,9 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
         // order decides).  The test is symmetric: a selected entry of another site just below the boundary and
         // an unselected one of the boundary's site just above it may be ordered either way by the reference.
         const double a_m = __longlong_as_double((long long)kb_m);
-        const double band = a_m * band_rel + 1e-300;
-        if (a_m > PM_A_MAX_SAFE) SLOW_RETURN(31);
+        bool unsafe;
+        const double band = cert_band(a_m, band_rel, unsafe);
+        if (unsafe) SLOW_RETURN(31);
         const uint32_t site_m = site_of((uint32_t)(e_m & SLOT_MASK));
         const uint64_t kb = (e >> SB) << SB;
         const bool near = alive && kb != noloc_key && fabs(__longlong_as_double((long long)kb) - a_m) <= band;
@@ -477,8 +645,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
           // at e_m's site and the proposer verified (tail_ok) that everything unlisted within the band of
           // the last entry is at that site too (then those tie exactly and have larger slots)
           const int last_l = (int)n_k - 1;
-          const uint64_t e_l = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(e >> 32), last_l) << 32) |
-                               (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)e, last_l);
+          const uint64_t e_l = readlane_u64(e, last_l);
           const uint64_t kb_l = (e_l >> SB) << SB;
           if (kb_l != noloc_key && (__longlong_as_double((long long)kb_l) - a_m) <= band) {
             if (!(tail_ok && site_of((uint32_t)(e_l & SLOT_MASK)) == site_m)) SLOW_RETURN(31);
@@ -486,8 +653,7 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
         }
       }
     }
-    // ---- commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585): the seed, then the row's
-    // first `want` live entries in key order
+    // ---- commit: the seed, then the row's first `want` live entries in key order
     if (sel) {
       kill(slot);
       mirror(slot);
@@ -497,16 +663,9 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
       kill(seed);
       mirror(seed);
       members[c.mem_off] = seed;
-      g_cfg[c.n_groups] = c.cfg;
-      g_n[c.n_groups] = want + 1u;
-      g_off[c.n_groups] = c.mem_off;
+      step_record(g_cfg, g_n, g_off, c.n_groups, c.cfg, want + 1u, c.mem_off);
     }
-    c.n_groups += 1;
-    c.mem_off += want + 1u;
-    c.cand_sum += c.n_cand;
-    c.n_cand -= want + 1u;
-    c.total_available -= want + 1u;
-    c.steps += 1;
+    step_book(c, want + 1u);
     c.fast_steps += 1;
     cur += 1u;  // this seed is dead now
     ++done;
@@ -536,15 +695,6 @@ __device__ __noinline__ int carve_fast_steps(const CarveArgs& p, StepCtx& c_ref,
 // else is handed to carve_fast_steps, which looks at the seed at seed_cur with the row's keys: other rows, exhausted
 // rows (-> exact sweep), the debug hook (FAST_SLOW: exactly one step), the last partial group, the first-come tail,
 // the end of the batch (FAST_SEQ).
-// a proposal batch ends (the list is compacted and re-proposed) once fewer than 1 / PM_THIN_DIV of the slots that were
-// alive when its validation started are left; a batch prepared beside the one in front of it is not worth validating
-// when less than 1 / PM_STALE_DIV of its list is still alive (the next one is prepared from the state as it is then)
-#ifndef PM_THIN_DIV
-#define PM_THIN_DIV 3u
-#endif
-#ifndef PM_STALE_DIV
-#define PM_STALE_DIV 3u
-#endif
 #ifndef CHAIN_BLOCK
 #define CHAIN_BLOCK 8u
 #endif
@@ -841,34 +991,12 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
   const uint32_t lane = threadIdx.x & 63u;
   typedef chain_lds_u32 lds_u32;
   const ChainLds L = chain_lds(l_buf);
-  const uint32_t dbg_every = UNI(p.debug_uncertain_every);
   const uint32_t n_seeds = UNI(c.n_seeds);
-  const uint32_t n_list_v = UNI(c.n_list), n_start = UNI(c.n_start);
-  const uint32_t group_n = UNI(c.max_s), want = group_n - 1u;
-  const uint32_t cap_g = UNI(p.cap_groups), cap_m = UNI(p.cap_members);
-  const uint32_t step0 = UNI(steps_before) + UNI(c.steps);
-  const uint32_t base_cand = UNI(c.n_cand), base_groups = UNI(c.n_groups), base_mem = UNI(c.mem_off);
-  uint32_t n_cand = base_cand, commits = 0;
+  const ChainRun run = chain_run(p, c, steps_before);
+  const uint32_t group_n = run.group_n, want = group_n - 1u;
+  uint32_t n_cand = run.base_cand, commits = 0;
   int action = FAST_SEQ;
   uint32_t exit_cur = n_seeds;  // where carve_fast_steps resumes its search for the first live seed
-  // Commits that can follow one another before any of the conditions that end the chain can come true (they are
-  // looked at again when the budget is used up): candidates for full groups, room in the output arrays, the
-  // re-proposal threshold, the debug hook.  >= 1 whenever none of those conditions holds.
-  auto budget_now = [&]() -> uint32_t {
-    uint32_t b = n_cand / group_n;
-    const uint32_t room_g = cap_g - (base_groups + commits), room_m = (cap_m - base_mem) / group_n - commits;
-    b = b < room_g ? b : room_g;
-    b = b < room_m ? b : room_m;
-    if (n_list_v > 256u) {
-      const uint32_t t = n_cand * PM_THIN_DIV >= n_start ? (n_cand * PM_THIN_DIV - n_start) / (PM_THIN_DIV * group_n) + 1u : 1u;
-      b = b < t ? b : t;
-    }
-    if (dbg_every) {
-      const uint32_t r = (step0 + commits + 1u) % dbg_every;
-      b = b < dbg_every - r ? b : dbg_every - r;
-    }
-    return b;
-  };
   CH_DECL;
 
   // ---- start the producer and the collector
@@ -878,8 +1006,8 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
     cc_st(&L.CC[CC_TAIL], 0u);
     cc_st(&L.CC[CC_DONE], 0u);
     cc_st(&L.CC[CC_START], UNI(seed_cur));
-    cc_st(&L.CC[CC_G0], base_groups);
-    cc_st(&L.CC[CC_M0], base_mem);
+    cc_st(&L.CC[CC_G0], run.base_groups);
+    cc_st(&L.CC[CC_M0], run.base_mem);
   }
   cmd_seq += 4u;
   if (lane == 0u) cc_st(&L.CC[CC_CMD], cmd_seq | CH_RUN);
@@ -946,7 +1074,7 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
           // enough live entries, a row whose flags settle the certificate wholesale, and no end of the chain in sight
           good = !live || ((uint32_t)__popcll(selm) == group_n && (m2 & flags_needed) == flags_needed && budget != 0u);
           if (__builtin_expect(!good, 0)) break;
-          // commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585)
+          // commit
           if ((selm >> lane) & 1ull)
             __hip_atomic_fetch_and((lds_u32*)(uintptr_t)ra, ~rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           L.Q[r] = live ? a : 0ull;  // (every lane the same word: the collector re-derives the selection from it)
@@ -961,32 +1089,14 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
         // ---- a live seed that needs a second look (its row is loaded: ra, rb, m2, a)
         if (budget == 0u) {
           exit_cur = UNI(L.RI[r]);
-          // `while total_available >= min` with `compatible < min => break` (mod.rs:507,517-519) hold while full
-          // groups fit (max_s >= min_s); the last, partial group is carve_fast_steps' business
-          if (n_cand < group_n) {
-            action = FAST_SEQ;
+          const int why = chain_stop_reason(run, n_cand, commits);
+          if (why != FAST_AGAIN) {
+            if (why == FAST_REPROPOSE && lane == 0u) p.status->why[0] += 1u;
+            action = why;
             stop = true;
             break;
           }
-          if (base_groups + commits >= cap_g || base_mem + (commits + 1u) * group_n > cap_m) {
-            action = FAST_OVERFLOW;
-            stop = true;
-            break;
-          }
-          // A good part of what was alive when the batch started is gone: the neighbour rows are thinning out.
-          // Re-prepare (compact) and re-propose now, before rows start running out of live entries.
-          if (n_cand * PM_THIN_DIV < n_start && n_list_v > 256u && commits > 0u) {
-            if (lane == 0u) p.status->why[0] += 1u;
-            action = FAST_REPROPOSE;
-            stop = true;
-            break;
-          }
-          if (dbg_every && ((step0 + commits + 1u) % dbg_every) == 0u) {
-            action = FAST_SLOW;
-            stop = true;
-            break;
-          }
-          budget = budget_now();
+          budget = chain_budget(run, n_cand, commits);
         }
         {
           const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(a >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)a, 0u));
@@ -1036,15 +1146,7 @@ __device__ __noinline__ int carve_chain(const CarveArgs& p, StepCtx& c_ref, uint
     if (lane == 0u) cc_st(&L.CC[CC_ABORT], 1u);
     action = FAST_ABORT;  // a hand-shake inside the workgroup timed out: reported as CARVE_STATE_ABORTED (never seen)
   }
-  c.n_groups = base_groups + commits;
-  c.mem_off = base_mem + commits * group_n;
-  c.n_cand = n_cand;
-  c.total_available -= commits * group_n;
-  c.steps += commits;
-  c.fast_steps += commits;
-  // sum over the commits of the live candidates before each: base, base - g, base - 2g, ...
-  c.cand_sum += (unsigned long long)commits * base_cand -
-                (unsigned long long)group_n * ((unsigned long long)commits * (commits ? commits - 1u : 0u) / 2ull);
+  chain_book(c, run, commits, n_cand);
   CH_BOOK();
   c_ref = c;
   seed_cur = exit_cur;
@@ -1069,39 +1171,20 @@ __device__ __noinline__ int carve_exact_step(const CarveArgs& p, BlockRed& red, 
   constexpr double band_rel = BIG ? PM_TIE_BAND_BIG : PM_TIE_BAND;
   const uint32_t lw = (c.n_list + 63u) >> 6;
   auto wid_of = [](uint32_t sl) -> uint32_t { return sl; };  // members are recorded as SLOTS (translated after the run)
-  // FORM: `while total_available >= min` (mod.rs:507) with `compatible < min => break` (:517-519).
-  // MERGE: `while remaining_groups.len() >= min` (mod.rs:695).
-  if (!((c.mode == CARVE_MODE_MERGE || c.total_available >= c.min_s) && c.n_cand >= c.min_s && c.n_cand > 0))
-    return STEP_BREAK;
+  if (!step_open(c, c.mode == CARVE_MODE_MERGE)) return STEP_BREAK;
   PROF_DECL;
-  // ---- seed: first live slot with a location, else first live slot (mod.rs:526-530); every wave finds
-  // it redundantly from the bitmaps with one ballot per 64 words (no barrier, no shuffle tree)
+  // ---- seed: first live slot with a location, else first live slot; every wave finds it redundantly from the
+  // bitmaps with one ballot per 64 words (no barrier, no shuffle tree; both in one pass over LDS)
   uint32_t f_loc = PM_NONE, f_any = PM_NONE;
   for (uint32_t j0 = 0; j0 < lw && (f_loc == PM_NONE || f_any == PM_NONE); j0 += 64u) {
     const uint32_t j = j0 + lane;
     const uint64_t al = j < lw ? l_alive[j] : 0ull;
     const uint64_t ll = j < lw ? (al & l_loc[j]) : 0ull;
-    if (f_any == PM_NONE) {
-      const uint64_t nz = __ballot(al != 0ull);
-      if (nz) {
-        const int src = __builtin_ctzll(nz);
-        const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(al >> 32), src) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)al, src);
-        f_any = (j0 + src) * 64u + __builtin_ctzll(w);
-      }
-    }
-    if (f_loc == PM_NONE) {
-      const uint64_t nz = __ballot(ll != 0ull);
-      if (nz) {
-        const int src = __builtin_ctzll(nz);
-        const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(ll >> 32), src) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)ll, src);
-        f_loc = (j0 + src) * 64u + __builtin_ctzll(w);
-      }
-    }
+    if (f_any == PM_NONE) f_any = first_bit_of(al, j0);
+    if (f_loc == PM_NONE) f_loc = first_bit_of(ll, j0);
   }
 
-  const uint32_t want = c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;  // fill to max (mod.rs:545-551)
+  const uint32_t want = step_want(c);
   uint32_t seed = f_any;
   bool use_dist = false, located_only = false;
   uint64_t last = 0;
@@ -1228,16 +1311,16 @@ __device__ __noinline__ int carve_exact_step(const CarveArgs& p, BlockRed& red, 
   if (c.mode == CARVE_MODE_MERGE && total < 2u) return STEP_BREAK;      // is_merge_beneficial (mod.rs:868-870)
 
   // ---- exactness certificate for a distance-ordered selection (see the comment above carve_kernel)
-  int uncertain = p.debug_uncertain_every && use_dist &&
-                  ((steps_before + c.steps + 1u) % p.debug_uncertain_every) == 0u;
+  int uncertain = step_forced(p.debug_uncertain_every, steps_before + c.steps) && use_dist;
   const uint64_t noloc_key = (PM_KEY_NOLOC >> SB) << SB;
   const uint64_t last_key = (last >> SB) << SB;
   if (use_dist && n_sel > 0 && last_key != noloc_key) {
     const uint32_t ls = (uint32_t)(last & ((1ull << SB) - 1ull));
     const double a_m = __longlong_as_double((long long)last_key);
-    const double band = a_m * band_rel + 1e-300;
+    bool unsafe;
+    const double band = cert_band(a_m, band_rel, unsafe);
     const double mlat = G(p.cc_lat)[ls], mlon = G(p.cc_lon)[ls];  // uniform loads
-    if (a_m > PM_A_MAX_SAFE) uncertain = 1;
+    if (unsafe) uncertain = 1;
     for (uint32_t i = tid; i < n_it; i += CARVE_THREADS) {
       const uint32_t s = slot_of(i);
       const uint64_t k = l_key[i];
@@ -1254,10 +1337,10 @@ __device__ __noinline__ int carve_exact_step(const CarveArgs& p, BlockRed& red, 
 #pragma unroll
   for (uint32_t k = 0; k < CARVE_WAVES; ++k) any |= red.flag[k];
   if (any) return STEP_UNCERTAIN;
-  if (c.n_groups >= p.cap_groups || c.mem_off + total > p.cap_members) return STEP_OVERFLOW;
+  if (!step_room(c, total, p.cap_groups, p.cap_members)) return STEP_OVERFLOW;
 
-  // ---- commit (create_group_atomically mod.rs:299-322; healthy_nodes.retain :585): selected slots =
-  // seed + every key <= last.  Each wave owns whole bitmap words (slot>>6 == j*16 + wave): ballot writes them.
+  // ---- commit: selected slots = seed + every key <= last.  Each wave owns whole bitmap words (slot>>6 == j*16 +
+  // wave): ballot writes them.
   if (SPARSE) {  // (a handful of bits among the live candidates: one atomic each, here and in the published copy)
     for (uint32_t i = tid; i < n_it; i += CARVE_THREADS) {
       const uint32_t s = slot_of(i);
@@ -1284,21 +1367,14 @@ __device__ __noinline__ int carve_exact_step(const CarveArgs& p, BlockRed& red, 
   if (wave == 0) {  // group record + members: LDS -> fire-and-forget global stores
     if (lane == 0) {
       G(p.members)[c.mem_off] = wid_of(seed);
-      G(p.g_cfg)[c.n_groups] = c.cfg;
-      G(p.g_n)[c.n_groups] = total;
-      G(p.g_off)[c.n_groups] = c.mem_off;
+      step_record(G(p.g_cfg), G(p.g_n), G(p.g_off), c.n_groups, c.cfg, total, c.mem_off);
     }
     const uint32_t lim = n_sel < PM_CARVE_SEL_CAP ? n_sel : PM_CARVE_SEL_CAP;
     for (uint32_t r = lane; r < lim; r += 64u) G(p.members)[c.mem_off + 1u + r] = wid_of(sel_out[r]);
   }
   lds_barrier();
   PROF_MARK(22);  // one exact step
-  c.n_groups += 1;
-  c.mem_off += total;
-  c.cand_sum += c.n_cand;
-  c.n_cand -= total;
-  c.total_available -= total;  // mod.rs:586
-  c.steps += 1;
+  step_book(c, total);
   return STEP_CONTINUE;
 }
 
@@ -1390,8 +1466,7 @@ __device__ __noinline__ int carve_run_lds(const CarveArgs& p, BlockRed& red, Ste
 // packed keys, positions and bitmaps live in HBM/L2; one workgroup-wide argmin round per member.
 __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, StepCtx& c, uint64_t* part, uint64_t* key,
                               const uint32_t* wid, uint64_t* alive, const uint64_t* loc, uint32_t steps_before) {
-  if (!((c.mode == CARVE_MODE_MERGE || c.total_available >= c.min_s) && c.n_cand >= c.min_s && c.n_cand > 0))
-    return STEP_BREAK;
+  if (!step_open(c, c.mode == CARVE_MODE_MERGE)) return STEP_BREAK;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   constexpr uint32_t SB = PM_CARVE_SLOT_BITS_MEM;
   const uint32_t lw = (c.n_list + 63u) >> 6;
@@ -1416,7 +1491,7 @@ __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, St
     f_any = min(f_any, red.b[k]);
   }
   __syncthreads();
-  const uint32_t want = c.max_s - 1u < c.n_cand - 1u ? c.max_s - 1u : c.n_cand - 1u;
+  const uint32_t want = step_want(c);
   uint32_t seed = f_any;
   bool use_dist = false, located_only = false;
   uint64_t last = 0;
@@ -1488,15 +1563,15 @@ __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, St
   if (c.mode == CARVE_MODE_FORM && total < c.min_s) return STEP_BREAK;
   if (c.mode == CARVE_MODE_MERGE && total < 2u) return STEP_BREAK;
 
-  int uncertain = p.debug_uncertain_every && use_dist &&
-                  ((steps_before + c.steps + 1u) % p.debug_uncertain_every) == 0u;
+  int uncertain = step_forced(p.debug_uncertain_every, steps_before + c.steps) && use_dist;
   const uint64_t last_key = (last >> SB) << SB;
   if (use_dist && n_sel > 0 && last_key != ((PM_KEY_NOLOC >> SB) << SB)) {
     const uint32_t ls = (uint32_t)(last & ((1ull << SB) - 1ull));
     const double a_m = __longlong_as_double((long long)last_key);
-    const double band = a_m * PM_TIE_BAND_MEM + 1e-300;
+    bool unsafe;
+    const double band = cert_band(a_m, PM_TIE_BAND_MEM, unsafe);
     const double mlat = G(p.cc_lat)[ls], mlon = G(p.cc_lon)[ls];
-    if (a_m > PM_A_MAX_SAFE) uncertain = 1;
+    if (unsafe) uncertain = 1;
     for (uint32_t s = tid; s < c.n_list; s += CARVE_THREADS) {
       const uint64_t k = key[s];
       if (k == ~0ull || s == ls) continue;
@@ -1507,7 +1582,7 @@ __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, St
     }
   }
   if (__syncthreads_or(uncertain)) return STEP_UNCERTAIN;
-  if (c.n_groups >= p.cap_groups || c.mem_off + total > p.cap_members) return STEP_OVERFLOW;
+  if (!step_room(c, total, p.cap_groups, p.cap_members)) return STEP_OVERFLOW;
   for (uint32_t s = tid; s < c.n_list; s += CARVE_THREADS) {
     if (!bit_at(alive, s)) continue;
     if (s == seed || (n_sel > 0 && key[s] <= last))
@@ -1515,17 +1590,10 @@ __device__ __noinline__ int carve_step_mem(const CarveArgs& p, BlockRed& red, St
   }
   if (tid == 0) {
     G(p.members)[c.mem_off] = wid[seed];
-    G(p.g_cfg)[c.n_groups] = c.cfg;
-    G(p.g_n)[c.n_groups] = total;
-    G(p.g_off)[c.n_groups] = c.mem_off;
+    step_record(G(p.g_cfg), G(p.g_n), G(p.g_off), c.n_groups, c.cfg, total, c.mem_off);
   }
   __syncthreads();
-  c.n_groups += 1;
-  c.mem_off += total;
-  c.cand_sum += c.n_cand;
-  c.n_cand -= total;
-  c.total_available -= total;
-  c.steps += 1;
+  step_book(c, total);
   return STEP_CONTINUE;
 }
 

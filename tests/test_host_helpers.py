@@ -464,3 +464,25 @@ def test_measuring_code_stays_out_of_the_kernel_bodies():
                 continue
             bad.append(f"{name}:{i + 1}: {line.strip()}")
     assert not bad, bad
+
+
+def test_step_rule_is_written_once():
+    """The reference's step rule (when a configuration takes another step, how many neighbours a seed wants, the debug
+    hook, the certificate band, what a commit books) stands in one block of helpers behind StepCtx in pm_validate.inc,
+    and the seven steppers of pm_validate.inc and pm_stream.inc call it: the pieces that used to be written out in
+    each of them appear once in the two files together, and no modulo by the debug hook's period outside the block.
+    Text only: nothing is compiled."""
+    from protocol_amd import build as B
+    val = open(os.path.join(B.CSRC, "pm_validate.inc")).read()
+    stream = open(os.path.join(B.CSRC, "pm_stream.inc")).read()
+    both = val + stream
+    for piece in ("+ 1e-300", "PM_A_MAX_SAFE", "c.max_s - 1u < c.n_cand - 1u"):
+        assert both.count(piece) == 1, (piece, both.count(piece))
+    begin, end = "// ---- The step rule", "// ---- (the step rule ends here)"
+    assert val.count(begin) == 1 and val.count(end) == 1 and val.index("struct StepCtx") < val.index(begin) < val.index(end)
+    block = val[val.index(begin):val.index(end)]
+    for piece in ("+ 1e-300", "PM_A_MAX_SAFE", "c.max_s - 1u < c.n_cand - 1u"):
+        assert piece in block, piece
+    outside = val.replace(block, "") + stream
+    assert not re.findall(r"%\s*(?:dbg_every|p\.debug_uncertain_every|\w*every\w*)", outside)
+    assert len(re.findall(r"%\s*every\b", block)) == 2  # step_forced and the commits in front of it
