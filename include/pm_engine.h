@@ -44,8 +44,9 @@ extern "C" {
                             ms_total is the host's clock over the call, ms_sweep_kernel is measured by a time_proposer engine only;
                             + pm_adopt_groups / pm_group_id_state (restart and switch-over), + pm_explain_workers /
                             pm_config_report / pm_task_report (diagnostics), + pm_group_spread / pm_config_spread /
-                            pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates): compatible additions, the
-                            version stays 3 */
+                            pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates),
+                            + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed): compatible
+                            additions, the version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -505,6 +506,52 @@ typedef struct pm_near_row {
 } pm_near_row;
 int32_t pm_nearest_workers(pm_engine*, const pm_near_query* q, uint32_t n_q, uint32_t pool, uint32_t k, pm_near_row* rows,
                            uint32_t* workers /* n_q * k */, double* km /* n_q * k, may be NULL */);
+
+/* ---- assignment change feed (kernels in pm_changes.inc) -------------------------------------------------------------------
+ * Which workers' published rows a publish changed.  The reference cannot tell a node "your task, group or ring position
+ * changed": it renders the task again on every heartbeat (scheduler_impl.rs:33-128 — the group's task, GROUP_ID, GROUP_INDEX,
+ * GROUP_SIZE, NEXT_P2P_ADDRESS; the ring itself: mod.rs:424-434).  With the feed on, the engine compares every publish with the
+ * one before it, on the device, and keeps a list of the workers whose row differs: push on change, render on change, count
+ * reassignments per interval.  Off (the default) a publish is what it was: one host branch more.
+ *
+ * ROW IDENTITY of a worker at a publish: (group_id, group_index, group_size, next_worker, the task ITSELF).  group_slot is not
+ * part of it (slots are renumbered when the group list is compacted, ids are not); neither is the task's position (n tasks
+ * inserted in front move every published position by n and change no row).  A worker in no group: (0, 0, 0, PM_NONE, no task).
+ *
+ * A PUBLISH is every commit of a table: pm_tick, pm_tick_many, pm_match, pm_tasks_insert_front_ex(republish = 1).  A match a
+ * tick queued and abandoned is none.  Publish k gives every worker what(k, w), an OR of
+ *   PM_CHG_GROUP  group_id differs from publish k - 1
+ *   PM_CHG_RING   group_index, group_size or next_worker differs
+ *   PM_CHG_TASK   the task differs
+ * and the feed accumulates what(w) |= what(k, w) until it is drained: a union of per-publish differences, not a difference of
+ * end points — a row that changed and changed back stays listed.  Rows appended since the previous publish compare against
+ * "in no group".
+ *
+ * BETWEEN publishes the published rows may be patched in place (a dissolved group, a dead worker, a deleted task: the row reads
+ * "no group" at once).  Those edits are outside this feed by definition — pm_drain_group_events reports every such dissolution
+ * with its members.  The next publish compares against the previous PUBLISH: a worker whose group was dissolved between two
+ * ticks and who ends the next tick in no group is listed at that tick.
+ *
+ * RESYNC: enabling the feed, pm_upload_tasks, a rebuild of the task table's index space (regrowth or compaction),
+ * pm_reset_groups and pm_upload_workers(keep_groups = 0) make the remembered rows meaningless.  The next publish then lists
+ * EVERY row [0, W) with all three bits, remembers that publish, and the next successful drain returns PM_CHANGES_RESYNC in
+ * *flags, once: the consumer drops what it derived from earlier lists and renders every worker.  pm_upload_workers(keep_groups
+ * = 1) is no resync.
+ *
+ * pm_drain_assignment_changes: the workers with what != 0, ASCENDING by worker index, with their bits; then it clears them.
+ * The convention of pm_drain_group_events: *n and *flags always report what is pending; rows == NULL or cap < *n: PM_ERANGE,
+ * nothing drained, the resync flag stays pending — `pm_drain_assignment_changes(e, NULL, 0, &n, &flags)` is the size query.
+ * The list is made on the device; the count and the n rows cross to the host.  Feed off: PM_ESTATE.
+ *
+ * Multi-GPU engines are out of scope: pm_enable_assignment_changes(on = 1) with dist_world > 1 is PM_ESTATE, and so is
+ * pm_dist_configure(world > 1) while the feed is on. */
+enum { PM_CHG_GROUP = 1, PM_CHG_RING = 2, PM_CHG_TASK = 4 };
+#define PM_CHANGES_RESYNC 1u
+typedef struct pm_change_row {
+  uint32_t worker, what; /* worker index; OR of PM_CHG_* */
+} pm_change_row;
+int32_t pm_enable_assignment_changes(pm_engine*, uint32_t on); /* off also clears; on = resync */
+int32_t pm_drain_assignment_changes(pm_engine*, pm_change_row* rows, uint32_t cap, uint32_t* n, uint32_t* flags);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

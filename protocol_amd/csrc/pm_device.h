@@ -156,6 +156,22 @@ struct NearArgs {
   double* km;
 };
 
+// the change feed (pm_changes.inc): what a publish remembers of a worker's row.  All zeroes = in no group (next_worker and the
+// task handle are stored complemented: PM_NONE reads 0), so rows a grown buffer has just gained need no initialising pass.
+struct alignas(16) ChangeIdent {
+  uint32_t group_id_lo, group_id_hi, group_index, group_size;
+  uint32_t not_next_worker, not_task_handle, unused[2];
+};
+static constexpr uint32_t PM_CHG_SCAN_WORDS = 4;  // bitmap words a thread of change_scan_kernel takes per pass (x 256 threads)
+struct ChangeDiffArgs {
+  uint32_t W, G, resync;        // rows; group slots g_task holds; != 0: every row < W changed, all bits
+  const pm_assignment* table;   // the committed table (d_table)
+  const uint32_t* g_task;       // the committed task words: handles
+  ChangeIdent* ident;           // [W] remembered identities
+  uint8_t* what;                // [W] pending PM_CHG_* bits
+  uint64_t* bitmap;             // [ceil(W / 64)] pending rows
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -385,6 +401,10 @@ void launch_config_spread(const pm_group_spread_row* rows, const uint32_t* row_c
                           SpreadCfgAcc* out, uint32_t max_blocks, hipStream_t s);
 // nearest candidates (pm_near.inc)
 void launch_nearest(const NearArgs& a, hipStream_t s);
+// assignment change feed (pm_changes.inc)
+void launch_assign_diff(const ChangeDiffArgs& a, hipStream_t s);
+void launch_change_list(const uint64_t* bitmap, uint32_t n_words, const uint8_t* what, uint32_t* prefix, uint32_t* total_host,
+                        pm_change_row* out, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

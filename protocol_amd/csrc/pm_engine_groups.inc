@@ -33,6 +33,7 @@ static void reset_groups_locked(pm_engine* e) {
   // against the new list.
   e->groups_epoch++;
   pub_clear(e);
+  e->chg_resync = true;  // (the id stream may repeat: the change feed's remembered ids prove nothing)
 }
 
 // dissolve_group (mod.rs:1423-1487).  A status storm dissolves hundreds of groups per tick; removing each from

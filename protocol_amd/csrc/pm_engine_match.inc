@@ -420,6 +420,7 @@ static int32_t publish_end(pm_engine* e, const PubRun& pr) {
     e->groups[g].task_uid = g_task[g] == PM_NONE ? 0 : (e->tasks_have_uid ? e->h_tuid[g_task[g]] : task_position(e, g_task[g]));
   }
   std::swap(e->d_g_task, e->d_g_task_next);
+  if (e->chg_on) return changes_publish(e);  // (the change feed: this table against the one before it, queued, not waited for)
   return PM_OK;
 }
 

@@ -200,6 +200,20 @@ struct pm_engine {
   DevBuf<double> d_near_out;
   std::vector<double> h_near_out;
 
+  // ---- assignment change feed (pm_engine_changes.inc): remembered identities, pending bits and rows of the workers [0, chg_W);
+  // everything behind chg_W reads zero.  The drain's scratch: per-word prefix, the list, its count in pinned memory.
+  bool chg_on = false;
+  bool chg_resync = false;       // the remembered identities are meaningless: the next publish lists every row
+  bool chg_resync_flag = false;  // ... and did: the next successful drain returns PM_CHANGES_RESYNC
+  bool chg_list_valid = false;   // d_chg_rows / chg_n are the pending marks as they are now
+  uint32_t chg_W = 0, chg_n = 0;
+  DevBuf<ChangeIdent> d_chg_ident;
+  DevBuf<uint8_t> d_chg_what;
+  DevBuf<uint64_t> d_chg_bitmap;
+  DevBuf<uint32_t> d_chg_prefix;
+  DevBuf<pm_change_row> d_chg_rows;
+  uint32_t* h_chg_count = nullptr;
+
   // ---- multi-GPU (pm_dist_*): this engine is rank `dist_rank` of `dist_world`, every rank holds the whole swarm
   uint32_t dist_rank = 0, dist_world = 1;
   std::vector<uint8_t> h_shard;        // owner rank of every worker

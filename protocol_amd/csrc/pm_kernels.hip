@@ -787,5 +787,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_report.inc"        // diagnostics: reason codes, the config and task reports, their launchers
 #include "pm_spread.inc"        // group geography: per-group and per-configuration spread, their launchers
 #include "pm_near.inc"          // nearest candidates: the per-query top-k selection, its launcher
+#include "pm_changes.inc"       // assignment change feed: the per-publish diff, the drain's scan and expansion, their launchers
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

@@ -57,6 +57,10 @@ near_row_dt = np.dtype([("origin", "<u4"), ("n", "<u4"), ("candidates", "<u4"), 
 NEAR_IDLE, NEAR_ELIGIBLE = 0, 1
 NEAR_SEED = 0xFFFFFFFE
 NEAR_MAX_K, NEAR_MAX_QUERIES = 256, 65535
+# pm_change_row (include/pm_engine.h): assignment change feed
+change_row_dt = np.dtype([("worker", "<u4"), ("what", "<u4")])
+CHG_GROUP, CHG_RING, CHG_TASK = 1, 2, 4
+CHANGES_RESYNC = 1
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -125,6 +129,7 @@ EXPORTS = [
     "pm_explain_workers", "pm_config_report", "pm_task_report",
     "pm_group_spread", "pm_config_spread", "pm_force_regroup",
     "pm_nearest_workers",
+    "pm_enable_assignment_changes", "pm_drain_assignment_changes",
 ]
 
 _lib = None
@@ -197,6 +202,8 @@ def lib() -> C.CDLL:
         L.pm_config_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_force_regroup.argtypes = [vp, u32, u32, C.c_double, C.POINTER(u32), C.POINTER(u32)]
         L.pm_nearest_workers.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+        L.pm_enable_assignment_changes.argtypes = [vp, u32]
+        L.pm_drain_assignment_changes.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -526,6 +533,26 @@ class Engine:
                                        rows.ctypes.data if n else None, workers.ctypes.data if n else None,
                                        km.ctypes.data if (want_km and n) else None))
         return rows, workers, km
+
+    # ---- assignment change feed
+    def enable_assignment_changes(self, on: bool = True):
+        """pm_enable_assignment_changes: on = resync (the next publish lists every row); off also clears"""
+        check(lib().pm_enable_assignment_changes(self._h, int(on)))
+
+    def drain_assignment_changes(self):
+        """pm_drain_assignment_changes -> (workers: uint32 [n] ascending, what: uint32 [n] OR of CHG_*, resync: bool).
+        The size query, then the drain (again if a publish lengthened the list in between)."""
+        n, flags = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().pm_drain_assignment_changes(self._h, None, 0, C.byref(n), C.byref(flags))
+        while True:
+            if rc != -5:                                       # (PM_ERANGE is the size query's answer)
+                check(rc)
+            rows = np.zeros(max(n.value, 1), dtype=change_row_dt)
+            rc = lib().pm_drain_assignment_changes(self._h, rows.ctypes.data, len(rows), C.byref(n), C.byref(flags))
+            if rc == 0:
+                break
+        rows = rows[:n.value]
+        return rows["worker"].copy(), rows["what"].copy(), bool(flags.value & CHANGES_RESYNC)
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

@@ -350,6 +350,17 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::optional<NearestNodes> nearest_nodes(const std::optional<std::string>& address, const std::string& configuration_name,
                                             uint32_t pool = PM_NEAR_IDLE, uint32_t k = 16) const;
 
+  // ---- change feed (INTEGRATION.md "Change feed"; gpu_match_changes.cpp): pm_enable_assignment_changes /
+  // pm_drain_assignment_changes by address — the nodes whose published row (task, GROUP_ID, GROUP_INDEX, GROUP_SIZE,
+  // NEXT_P2P_ADDRESS: scheduler_impl.rs:33-128) a tick changed since the last call.
+  struct ChangedNodes {
+    std::vector<std::pair<std::string, uint32_t>> nodes;  // (address, OR of PM_CHG_*), in row order
+    bool resync = false;  // the engine lost track (include/pm_engine.h "RESYNC"): every node is listed, render them all
+  };
+  void enable_change_feed(bool on) const;  // off also clears; on = resync
+  // drains the feed.  std::out_of_range: the engine lists a row the node table does not hold.
+  ChangedNodes changed_nodes() const;
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());

@@ -140,6 +140,14 @@ int32_t pmx_force_regroup(pmx_plugin*, const char* configuration_name, uint32_t 
 int32_t pmx_nearest_nodes(pmx_plugin*, const char* address, const char* configuration_name, uint32_t pool, uint32_t k,
                           int32_t* found, char* out, size_t cap, size_t* needed);
 
+/* ---- change feed (pm_plugin_changes_c.cpp): GpuMatchPlugin::enable_change_feed / changed_nodes.  The text of
+ * pmx_changed_nodes: the first line is "resync\t<0|1>", then one line "<address>\t<what>" per node whose published row changed
+ * since the last drain, in row order (what: the OR of PM_CHG_GROUP = 1, PM_CHG_RING = 2, PM_CHG_TASK = 4, decimal).  The drain
+ * empties the feed, so its text is held until a call's buffer has taken it: the size query (out NULL, cap 0) and the call
+ * behind it hand over one drain. */
+int32_t pmx_enable_change_feed(pmx_plugin*, int32_t on);
+int32_t pmx_changed_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

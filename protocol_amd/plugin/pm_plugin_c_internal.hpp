@@ -60,6 +60,8 @@ struct pmx_plugin {
   std::unique_ptr<orchestrator::Scheduler> scheduler;
   std::atomic<uint64_t> upload_count{0};
   std::string restore_report;  // the last pmx_restore_groups' report (pmx_take_restore_report)
+  std::string changed_text;    // pmx_changed_nodes: a drain's text, held while changed_text_pending (until a buffer took it)
+  bool changed_text_pending = false;
 };
 
 #endif

@@ -219,6 +219,20 @@ pub const NEAR_ELIGIBLE: u32 = 1;
 pub const NEAR_SEED: u32 = 0xFFFF_FFFE;
 pub const NEAR_MAX_K: u32 = 256;
 
+/// pm_change_row (include/pm_engine.h): a worker whose published row changed, and how
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_change_row {
+    pub worker: u32,
+    pub what: u32,
+}
+
+/// the bits of pm_change_row.what (PM_CHG_*) and pm_drain_assignment_changes' flag
+pub const CHG_GROUP: u32 = 1;
+pub const CHG_RING: u32 = 2;
+pub const CHG_TASK: u32 = 4;
+pub const CHANGES_RESYNC: u32 = 1;
+
 /// pm_force_regroup's metrics (PM_REGROUP_*)
 pub const REGROUP_ALL: u32 = 0;
 pub const REGROUP_DIAMETER: u32 = 1;
@@ -300,6 +314,8 @@ extern "C" {
                         affected_workers: *mut u32) -> i32;
     fn pm_nearest_workers(e: *mut c_void, q: *const pm_near_query, n_q: u32, pool: u32, k: u32, rows: *mut pm_near_row,
                           workers: *mut u32, km: *mut f64) -> i32;
+    fn pm_enable_assignment_changes(e: *mut c_void, on: u32) -> i32;
+    fn pm_drain_assignment_changes(e: *mut c_void, rows: *mut pm_change_row, cap: u32, n: *mut u32, flags: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -514,6 +530,13 @@ pub struct ConfigurationSpread {
 pub struct ForceRegroupResult {
     pub dissolved_groups: u32,
     pub affected_nodes: u32,
+}
+
+/// changed_nodes' answer (gpu_match_changes.cpp's ChangedNodes)
+#[derive(Default, Debug, Clone)]
+pub struct ChangedNodes {
+    pub nodes: Vec<(String, u32)>,            // (address, OR of CHG_*), in row order
+    pub resync: bool,                         // the engine lost track: every node is listed, render them all
 }
 
 /// nearest_nodes' answer (gpu_match_near.cpp's NearestNodes)
@@ -1403,6 +1426,36 @@ impl GpuMatchPlugin {
             located: r.located,
             nodes: workers.iter().zip(km.iter()).take(r.n as usize).map(|(&w, &d)| (t.address_strings[w as usize].clone(), d)).collect(),
         }))
+    }
+
+    // ---- change feed (INTEGRATION.md "Change feed"): pm_enable_assignment_changes / pm_drain_assignment_changes by address
+
+    /// off also clears; on = resync
+    pub fn enable_change_feed(&self, on: bool) -> Result<()> {
+        check(unsafe { pm_enable_assignment_changes(self.engine, on as u32) })
+    }
+
+    /// drains the feed.  Err: the engine lists a row the node table does not hold.
+    pub fn changed_nodes(&self) -> Result<ChangedNodes> {
+        let t = self.nodes.read();           // (LOCK ORDER: nodes, the engine)
+        let mut rows: Vec<pm_change_row> = Vec::new();
+        let (mut n, mut flags) = (0u32, 0u32);
+        let mut rc = unsafe { pm_drain_assignment_changes(self.engine, std::ptr::null_mut(), 0, &mut n, &mut flags) };  // the size query
+        while rc == PM_ERANGE {              // (a publish between two calls lengthens the list: ask again, never read short)
+            rows.resize(n.max(1) as usize, pm_change_row::default());
+            rc = unsafe { pm_drain_assignment_changes(self.engine, rows.as_mut_ptr(), rows.len() as u32, &mut n, &mut flags) };
+        }
+        check(rc)?;
+        if n as usize > rows.len() { return Err(anyhow!("changed_nodes: the engine reports more rows than it was given room for")); }
+        for r in &rows[..n as usize] {
+            if r.worker as usize >= t.address_strings.len() {
+                return Err(anyhow!("changed_nodes: the engine lists a row the node table does not hold"));
+            }
+        }
+        Ok(ChangedNodes {
+            resync: flags & CHANGES_RESYNC != 0,
+            nodes: rows[..n as usize].iter().map(|r| (t.address_strings[r.worker as usize].clone(), r.what)).collect(),
+        })
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).
