@@ -45,7 +45,8 @@ extern "C" {
                             + pm_adopt_groups / pm_group_id_state (restart and switch-over), + pm_explain_workers /
                             pm_config_report / pm_task_report (diagnostics), + pm_group_spread / pm_config_spread /
                             pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates),
-                            + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed): compatible
+                            + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed),
+                            + pm_probe_configs / pm_config_overlap (probes and configuration overlap): compatible
                             additions, the version stays 3 */
 
 enum {
@@ -506,6 +507,56 @@ typedef struct pm_near_row {
 } pm_near_row;
 int32_t pm_nearest_workers(pm_engine*, const pm_near_query* q, uint32_t n_q, uint32_t pool, uint32_t k, pm_near_row* rows,
                            uint32_t* workers /* n_q * k */, double* km /* n_q * k, may be NULL */);
+
+/* ---- probes and configuration overlap (kernel in pm_probe.inc) -----------------------------------------------------------
+ * "If I add this configuration, or create a task with these requirements, what would it find right now?" and "which
+ * configurations compete for the same idle workers?"  The reference answers neither: create_task (api/routes/task.rs:41-88)
+ * accepts any topology and the task simply never runs, and a configuration whose candidates also meet one earlier in the carve
+ * order (node_groups/mod.rs:150-164, 399-418) just never forms.  One sweep over the worker table answers both, read-only.
+ *
+ * A PROBE is a configuration row that is NOT installed.  The probes have their own alternative table (alt_begin / alt_count
+ * index `alts`) and their own model bit table (model_row indexes `model_bits`; rows of (n_classes + 31) / 32 words as in
+ * pm_set_model_table, built with pm_host_build_model_table against the SAME spec model list as the installed table).
+ * n_classes must equal the engine's current class count (pm_set_model_table's, 0 before it): PM_EINVAL otherwise — a table
+ * built before the host interned a new model.  PM_EINVAL too when a PM_G_MODEL alternative's model_row >= n_model_rows, or
+ * n_classes == 0 with such an alternative present.
+ *
+ * rows[p].why: the reason codes are exactly pm_explain_workers' (the largest code over alternatives included), counted over
+ * the ELIGIBLE workers; "eligible" and "idle" are the reports' definitions, from the host's current flags and group membership,
+ * status changes and dissolutions that have not gone up yet included.  The compat masks are not read.
+ * overlap[p * n_cfgs + c]: the idle workers that meet probe p AND installed configuration c (pm_set_configs row order, enabled
+ * or not).  idle_exclusive uses the pm_set_enabled_mask bits.  mask_out[w] bit p: worker w meets probe p, for every row w < W
+ * whatever its state — the orientation of pm_compat_masks.  groups_max / groups_exclusive are bounds from counts (a quotient
+ * by min_group_size), not a prediction of what the carve would form: the carve also looks at sizes up to max_group_size, at
+ * the order of the configurations and at proximity.
+ *
+ * pm_config_overlap is the same sweep with the installed table on both sides: overlap[a * C + b] = the idle workers that
+ * meet both a and b — symmetric, the diagonal equal to pm_config_report's idle_meets.  The size query works as in
+ * pm_config_report: *n_cfgs = C always; cap < C * C: PM_ERANGE, nothing written (overlap may be NULL then).
+ *
+ * ERRORS of pm_probe_configs: n_probes == 0: PM_OK, nothing written.  n_probes > PM_MAX_CONFIGS; NULL probes or rows with
+ * n_probes > 0; a probe with min_group_size == 0 or max_group_size < min_group_size (the rules of pm_set_configs): PM_EINVAL.
+ * An alternative range outside `alts`: PM_ERANGE.  Both calls: PM_ESTATE inside a stepwise tick (dist_phase != 0) and before
+ * configurations and workers are uploaded.  An error leaves every output buffer untouched.
+ *
+ * Both calls leave the engine as they found it, as the reports do: no pending delta consumed, nothing compacted, no cache flag
+ * of the tick cleared, the installed tables and the compat masks' validity untouched; their scratch is their own. */
+typedef struct pm_probe_row {
+  uint32_t why[PM_WHY_N];    /* eligible workers (Healthy, p2p id) by reason code for this probe */
+  uint32_t eligible_meets;   /* == why[PM_WHY_OK] */
+  uint32_t idle_meets;       /* of them in no group: what a carve could take for it now */
+  uint32_t idle_located;     /* of those with PM_W_HAS_LOC */
+  uint32_t idle_exclusive;   /* idle, meet the probe, meet NO installed configuration whose enabled bit is set */
+  uint32_t groups_max;       /* idle_meets / min_group_size */
+  uint32_t groups_exclusive; /* idle_exclusive / min_group_size */
+} pm_probe_row;
+int32_t pm_probe_configs(pm_engine*, const pm_config_row* probes, uint32_t n_probes,
+                         const pm_gpu_alt_row* alts, uint32_t n_alts,
+                         const uint32_t* model_bits, uint32_t n_model_rows, uint32_t n_classes,
+                         pm_probe_row* rows /* n_probes */,
+                         uint32_t* overlap /* n_probes * n_cfgs, may be NULL */,
+                         uint64_t* mask_out /* W, may be NULL */);
+int32_t pm_config_overlap(pm_engine*, uint32_t* overlap /* n_cfgs * n_cfgs */, uint32_t cap, uint32_t* n_cfgs);
 
 /* ---- assignment change feed (kernels in pm_changes.inc) -------------------------------------------------------------------
  * Which workers' published rows a publish changed.  The reference cannot tell a node "your task, group or ring position

@@ -156,6 +156,24 @@ struct NearArgs {
   double* km;
 };
 
+// pm_probe_configs / pm_config_overlap (pm_probe.inc).  Counters of one probe in ProbeArgs::out / the LDS copy (PRB_STRIDE
+// words a probe), then the P x C matrix of idle workers that meet probe p and installed configuration c.
+enum : uint32_t {
+  PRB_WHY = 0,  // [0, PM_WHY_N): eligible workers by code
+  PRB_IDLE = PM_WHY_N,
+  PRB_LOCATED,
+  PRB_EXCL,
+  PRB_STRIDE = 16
+};
+struct ProbeArgs {
+  CompatArgs c;             // worker columns (flags: the current host column) and the INSTALLED tables
+  CompatArgs p;             // the same columns with the probes' rows, alternatives and model bits (n_cfgs = probes)
+  const int32_t* group_of;  // current (host truth): -1 = in no group
+  uint64_t enabled;         // pm_set_enabled_mask bits (idle_exclusive)
+  uint32_t* out;            // [P][PRB_STRIDE] then [P][C], zeroed beforehand
+  uint64_t* mask_out;       // [W] or nullptr
+};
+
 // the change feed (pm_changes.inc): what a publish remembers of a worker's row.  All zeroes = in no group (next_worker and the
 // task handle are stored complemented: PM_NONE reads 0), so rows a grown buffer has just gained need no initialising pass.
 struct alignas(16) ChangeIdent {
@@ -401,6 +419,8 @@ void launch_config_spread(const pm_group_spread_row* rows, const uint32_t* row_c
                           SpreadCfgAcc* out, uint32_t max_blocks, hipStream_t s);
 // nearest candidates (pm_near.inc)
 void launch_nearest(const NearArgs& a, hipStream_t s);
+// probes and configuration overlap (pm_probe.inc)
+void launch_probe(const ProbeArgs& a, uint32_t max_blocks, hipStream_t s);
 // assignment change feed (pm_changes.inc)
 void launch_assign_diff(const ChangeDiffArgs& a, hipStream_t s);
 void launch_change_list(const uint64_t* bitmap, uint32_t n_words, const uint8_t* what, uint32_t* prefix, uint32_t* total_host,

@@ -220,6 +220,7 @@ void pm_engine_destroy(pm_engine* e) {
   e->d_rep_tprefix.release(); e->d_rep_cnt.release(); e->d_rep_task.release(); e->d_rep_gof.release();
   e->d_spr_idx.release(); e->d_spr_rows.release(); e->d_spr_acc.release();
   e->d_near_q.release(); e->d_near_out.release();
+  e->d_probe_in.release(); e->d_probe_out.release();
   changes_release(e);
   delete e->form;
   delete e;
@@ -285,6 +286,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_report.inc"
 #include "pm_engine_spread.inc"
 #include "pm_engine_near.inc"
+#include "pm_engine_probe.inc"
 #define PM_CHANGES_ABI
 #include "pm_engine_changes.inc"
 #undef PM_CHANGES_ABI

@@ -199,6 +199,12 @@ struct pm_engine {
   DevBuf<pm_near_query> d_near_q;
   DevBuf<double> d_near_out;
   std::vector<double> h_near_out;
+  // ... of pm_probe_configs / pm_config_overlap (pm_engine_probe.inc): the probes' rows, alternatives and model bits, packed;
+  // the masks (u64 a worker, when asked for) and the counters behind them, packed
+  DevBuf<uint32_t> d_probe_in;
+  DevBuf<uint64_t> d_probe_out;
+  std::vector<uint32_t> h_probe_in;
+  std::vector<uint64_t> h_probe_out;
 
   // ---- assignment change feed (pm_engine_changes.inc): remembered identities, pending bits and rows of the workers [0, chg_W);
   // everything behind chg_W reads zero.  The drain's scratch: per-word prefix, the list, its count in pinned memory.

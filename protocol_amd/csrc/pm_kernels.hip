@@ -12,6 +12,8 @@
 //   config_spread_kernel the NEXT_P2P_ADDRESS ring (scheduler_impl.rs:115-116) (pm_spread.inc)
 //   nearest_kernel       mod.rs:234-255 (sort_nodes_by_proximity) over the carve's candidate set (:492-497, :511-515,
 //                        :526-551), the first k per query (pm_near.inc)
+//   probe_kernel         the clauses of compat_kernel for configurations that are not installed, against the live flags and
+//                        group membership, and the idle workers two configurations share (pm_probe.inc)
 //   carve_kernel         orchestrator/src/plugins/node_groups/mod.rs:478-628 (try_form_new_groups)
 //                        with :218-255 (Haversine proximity) and, in MERGE mode, the selection half
 //                        of :752-860 (attempt_group_merge)
@@ -787,6 +789,7 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_report.inc"        // diagnostics: reason codes, the config and task reports, their launchers
 #include "pm_spread.inc"        // group geography: per-group and per-configuration spread, their launchers
 #include "pm_near.inc"          // nearest candidates: the per-query top-k selection, its launcher
+#include "pm_probe.inc"         // probes against the live swarm and configuration overlap: one sweep, its launcher
 #include "pm_changes.inc"       // assignment change feed: the per-publish diff, the drain's scan and expansion, their launchers
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

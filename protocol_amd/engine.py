@@ -57,6 +57,10 @@ near_row_dt = np.dtype([("origin", "<u4"), ("n", "<u4"), ("candidates", "<u4"), 
 NEAR_IDLE, NEAR_ELIGIBLE = 0, 1
 NEAR_SEED = 0xFFFFFFFE
 NEAR_MAX_K, NEAR_MAX_QUERIES = 256, 65535
+# pm_probe_row (include/pm_engine.h): probes against the live swarm
+probe_row_dt = np.dtype([("why", "<u4", (10,)), ("eligible_meets", "<u4"), ("idle_meets", "<u4"), ("idle_located", "<u4"),
+                         ("idle_exclusive", "<u4"), ("groups_max", "<u4"), ("groups_exclusive", "<u4")])
+assert probe_row_dt.itemsize == 64
 # pm_change_row (include/pm_engine.h): assignment change feed
 change_row_dt = np.dtype([("worker", "<u4"), ("what", "<u4")])
 CHG_GROUP, CHG_RING, CHG_TASK = 1, 2, 4
@@ -129,6 +133,7 @@ EXPORTS = [
     "pm_explain_workers", "pm_config_report", "pm_task_report",
     "pm_group_spread", "pm_config_spread", "pm_force_regroup",
     "pm_nearest_workers",
+    "pm_probe_configs", "pm_config_overlap",
     "pm_enable_assignment_changes", "pm_drain_assignment_changes",
 ]
 
@@ -202,6 +207,8 @@ def lib() -> C.CDLL:
         L.pm_config_spread.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_force_regroup.argtypes = [vp, u32, u32, C.c_double, C.POINTER(u32), C.POINTER(u32)]
         L.pm_nearest_workers.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp]
+        L.pm_probe_configs.argtypes = [vp, vp, u32, vp, u32, vp, u32, u32, vp, vp, vp]
+        L.pm_config_overlap.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_enable_assignment_changes.argtypes = [vp, u32]
         L.pm_drain_assignment_changes.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
@@ -533,6 +540,33 @@ class Engine:
                                        rows.ctypes.data if n else None, workers.ctypes.data if n else None,
                                        km.ctypes.data if (want_km and n) else None))
         return rows, workers, km
+
+    # ---- probes and configuration overlap (read-only)
+    def probe_configs(self, cfg_rows, alt_rows, bits, n_model_rows, n_classes, want_overlap=True, want_mask=True):
+        """pm_probe_configs -> (rows: probe_row_dt [P], overlap: uint32 [P, C] or None, mask: uint64 [W] or None).
+        `cfg_rows` / `alt_rows` / `bits`: configuration rows that are NOT installed, with their own alternative and model
+        bit tables (host.pack_probes builds them); n_classes must be the installed table's class count."""
+        cfg_rows = _arr(cfg_rows, config_row_dt)
+        alt_rows = _arr(alt_rows, alt_row_dt)
+        bits = _arr(bits, np.uint32)
+        n = len(cfg_rows)
+        rows = np.zeros(n, dtype=probe_row_dt)
+        overlap = np.zeros((n, self.C), dtype=np.uint32) if want_overlap else None
+        mask = np.zeros(self.W, dtype=np.uint64) if want_mask else None
+        check(lib().pm_probe_configs(self._h, cfg_rows.ctypes.data if n else None, n,
+                                     alt_rows.ctypes.data if len(alt_rows) else None, len(alt_rows),
+                                     bits.ctypes.data if bits.size else None, int(n_model_rows), int(n_classes),
+                                     rows.ctypes.data if n else None,
+                                     overlap.ctypes.data if (want_overlap and overlap.size) else None,
+                                     mask.ctypes.data if (want_mask and self.W) else None))
+        return rows, overlap, mask
+
+    def config_overlap(self) -> np.ndarray:
+        """pm_config_overlap -> uint32 [C, C]: the idle workers that meet both configurations (pm_set_configs row order)"""
+        out = np.zeros((self.C, self.C), dtype=np.uint32)
+        n = C.c_uint32(0)
+        check(lib().pm_config_overlap(self._h, out.ctypes.data if self.C else None, out.size, C.byref(n)))
+        return out
 
     # ---- assignment change feed
     def enable_assignment_changes(self, on: bool = True):

@@ -75,6 +75,14 @@ def build_model_table(req_models: list, spec_models: list) -> np.ndarray:
     return bits[:n_rows * words]
 
 
+def pack_probes(probes: list, spec_models: list):
+    """Probes — [(name, min, max, requirement string | None)], configurations that are NOT installed — packed for
+    Engine.probe_configs against a swarm's interned spec model names (the list the installed model table was built against):
+    -> (cfg_rows, alt_rows, bits, n_model_rows, n_classes)."""
+    cfg_rows, alt_rows, req_models = pack_configs(probes)
+    return cfg_rows, alt_rows, build_model_table(req_models, spec_models), len(req_models), len(spec_models)
+
+
 def to_lowercase(text: str) -> str:
     """str::to_lowercase as the product evaluates it (pm_host_to_lowercase)"""
     raw = text.encode()

@@ -189,9 +189,8 @@ GpuMatchPlugin::~GpuMatchPlugin() {
 // NodeGroupConfiguration + its requirement string -> pm_config_row / pm_gpu_alt_row (set_configs of the Rust shim;
 // the field-by-field projection there is pm_host_parse_requirements here, the same product parser the tests pin to
 // the reference's vectors)
-void GpuMatchPlugin::set_configs(const std::vector<NodeGroupConfiguration>& templates) {
-  std::vector<pm_config_row> rows;
-  std::vector<pm_gpu_alt_row> alts;
+void GpuMatchPlugin::pack_templates(const std::vector<NodeGroupConfiguration>& templates, std::vector<pm_config_row>& rows,
+                                    std::vector<pm_gpu_alt_row>& alts, std::vector<std::string>& req_models) {
   for (const NodeGroupConfiguration& t : templates) {
     pm_config_row row{};
     if (t.compute_requirements) {
@@ -212,8 +211,8 @@ void GpuMatchPlugin::set_configs(const std::vector<NodeGroupConfiguration>& temp
         pm_gpu_alt_row g = a[k];
         if (g.flags & PM_G_MODEL) {  // (model_row comes back as a byte offset into `models`)
           const std::string m(models.c_str() + g.model_row);
-          g.model_row = uint32_t(req_models_.size());
-          req_models_.push_back(m);
+          g.model_row = uint32_t(req_models.size());
+          req_models.push_back(m);
         }
         alts.push_back(g);
       }
@@ -222,6 +221,12 @@ void GpuMatchPlugin::set_configs(const std::vector<NodeGroupConfiguration>& temp
     row.max_group_size = uint32_t(t.max_group_size);
     rows.push_back(row);
   }
+}
+
+void GpuMatchPlugin::set_configs(const std::vector<NodeGroupConfiguration>& templates) {
+  std::vector<pm_config_row> rows;
+  std::vector<pm_gpu_alt_row> alts;
+  pack_templates(templates, rows, alts, req_models_);
   const int32_t rc = pm_set_configs(engine_, rows.data(), uint32_t(rows.size()), alts.data(), uint32_t(alts.size()));
   if (rc == PM_EINVAL) throw std::invalid_argument("Plugin configuration is invalid");  // mod.rs:145-147
   check(rc);

@@ -350,6 +350,27 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::optional<NearestNodes> nearest_nodes(const std::optional<std::string>& address, const std::string& configuration_name,
                                             uint32_t pool = PM_NEAR_IDLE, uint32_t k = 16) const;
 
+  // ---- probing configurations (INTEGRATION.md "Diagnostics: probing configurations"; gpu_match_probe.cpp): pm_probe_configs /
+  // pm_config_overlap by name.  What a configuration that is NOT installed — or a task's requirements — would find in the
+  // swarm right now, and which installed configurations compete for the same idle nodes.
+  struct ProbeResult {
+    std::string name;
+    std::array<uint32_t, 10> why{};  // Healthy nodes with a p2p id by reason code (why[0] == eligible_meets)
+    uint32_t eligible_meets = 0, idle_meets = 0, idle_located = 0, idle_exclusive = 0;
+    uint32_t groups_max = 0, groups_exclusive = 0;  // bounds from counts (/ min_group_size), not what a carve would form
+    // (installed configuration name, idle nodes that meet the probe AND it), constructor order
+    std::vector<std::pair<std::string, uint32_t>> overlap;
+  };
+  // name, sizes and requirement string of every probe, packed exactly as the constructor packs the installed ones, the model
+  // rule against the node table's interned spec models.  A requirement string that does not parse: the constructor's
+  // std::invalid_argument, before any engine call.  One result per probe, in the given order.
+  std::vector<ProbeResult> probe_configurations(const std::vector<NodeGroupConfiguration>& probes) const;
+  struct ConfigurationOverlap {
+    std::vector<std::string> names;  // constructor order
+    std::vector<uint32_t> idle;      // [a * names.size() + b]: idle nodes that meet both a and b (symmetric)
+  };
+  ConfigurationOverlap configuration_overlap() const;
+
   // ---- change feed (INTEGRATION.md "Change feed"; gpu_match_changes.cpp): pm_enable_assignment_changes /
   // pm_drain_assignment_changes by address — the nodes whose published row (task, GROUP_ID, GROUP_INDEX, GROUP_SIZE,
   // NEXT_P2P_ADDRESS: scheduler_impl.rs:33-128) a tick changed since the last call.
@@ -399,6 +420,10 @@ class GpuMatchPlugin : public SchedulerPlugin {
   };
 
   void check(int32_t rc) const;
+  // templates -> rows and alternatives appended to `alts`, requirement model strings appended to `req_models` (alt.model_row
+  // indexes it); std::invalid_argument on a requirement string that does not parse
+  static void pack_templates(const std::vector<NodeGroupConfiguration>& templates, std::vector<pm_config_row>& rows,
+                             std::vector<pm_gpu_alt_row>& alts, std::vector<std::string>& req_models);
   void set_configs(const std::vector<NodeGroupConfiguration>& templates);
   void push_model_table(const NodeTable& nodes) const;
   static Row project(const OrchestratorNode& node, NodeTable& table, bool* new_model);

@@ -140,6 +140,15 @@ int32_t pmx_force_regroup(pmx_plugin*, const char* configuration_name, uint32_t 
 int32_t pmx_nearest_nodes(pmx_plugin*, const char* address, const char* configuration_name, uint32_t pool, uint32_t k,
                           int32_t* found, char* out, size_t cap, size_t* needed);
 
+/* ---- probing configurations (pm_plugin_probe_c.cpp): GpuMatchPlugin::probe_configurations / configuration_overlap.
+ *   pmx_probe_configurations   one line per probe, in the given order: "<name>\t<eligible_meets>\t<idle_meets>\t<idle_located>\t
+ *                              <idle_exclusive>\t<groups_max>\t<groups_exclusive>\t<why[0]>\t...\t<why[9]>", then one field
+ *                              "\t<installed configuration name>=<idle nodes that meet both>" per installed configuration
+ *                              (constructor order).  A requirement string that does not parse is an error (-1).
+ *   pmx_configuration_overlap  one line per installed configuration a: "<name of a>\t<idle[a][0]>\t...\t<idle[a][C - 1]>" */
+int32_t pmx_probe_configurations(pmx_plugin*, const pmx_config* probes, uint32_t n, char* out, size_t cap, size_t* needed);
+int32_t pmx_configuration_overlap(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 /* ---- change feed (pm_plugin_changes_c.cpp): GpuMatchPlugin::enable_change_feed / changed_nodes.  The text of
  * pmx_changed_nodes: the first line is "resync\t<0|1>", then one line "<address>\t<what>" per node whose published row changed
  * since the last drain, in row order (what: the OR of PM_CHG_GROUP = 1, PM_CHG_RING = 2, PM_CHG_TASK = 4, decimal).  The drain

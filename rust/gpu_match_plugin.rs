@@ -219,6 +219,19 @@ pub const NEAR_ELIGIBLE: u32 = 1;
 pub const NEAR_SEED: u32 = 0xFFFF_FFFE;
 pub const NEAR_MAX_K: u32 = 256;
 
+/// pm_probe_row (include/pm_engine.h): what a configuration that is not installed would find right now
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_probe_row {
+    pub why: [u32; 10],
+    pub eligible_meets: u32,
+    pub idle_meets: u32,
+    pub idle_located: u32,
+    pub idle_exclusive: u32,
+    pub groups_max: u32,
+    pub groups_exclusive: u32,
+}
+
 /// pm_change_row (include/pm_engine.h): a worker whose published row changed, and how
 #[repr(C)]
 #[derive(Default, Clone, Copy)]
@@ -314,6 +327,10 @@ extern "C" {
                         affected_workers: *mut u32) -> i32;
     fn pm_nearest_workers(e: *mut c_void, q: *const pm_near_query, n_q: u32, pool: u32, k: u32, rows: *mut pm_near_row,
                           workers: *mut u32, km: *mut f64) -> i32;
+    fn pm_probe_configs(e: *mut c_void, probes: *const pm_config_row, n_probes: u32, alts: *const pm_gpu_alt_row, n_alts: u32,
+                        model_bits: *const u32, n_model_rows: u32, n_classes: u32, rows: *mut pm_probe_row,
+                        overlap: *mut u32, mask_out: *mut u64) -> i32;
+    fn pm_config_overlap(e: *mut c_void, overlap: *mut u32, cap: u32, n_cfgs: *mut u32) -> i32;
     fn pm_enable_assignment_changes(e: *mut c_void, on: u32) -> i32;
     fn pm_drain_assignment_changes(e: *mut c_void, rows: *mut pm_change_row, cap: u32, n: *mut u32, flags: *mut u32) -> i32;
 }
@@ -548,6 +565,27 @@ pub struct NearestNodes {
     pub nodes: Vec<(String, f64)>,            // (address, km), nearest first; km = f64::MAX: not measured
 }
 
+/// probe_configurations' answer per probe (gpu_match_probe.cpp's ProbeResult)
+#[derive(Default, Debug, Clone)]
+pub struct ProbeResult {
+    pub name: String,
+    pub why: [u32; 10],                       // Healthy nodes with a p2p id by reason code (why[0] == eligible_meets)
+    pub eligible_meets: u32,
+    pub idle_meets: u32,
+    pub idle_located: u32,
+    pub idle_exclusive: u32,
+    pub groups_max: u32,                      // bounds from counts (/ min_group_size), not what a carve would form
+    pub groups_exclusive: u32,
+    pub overlap: Vec<(String, u32)>,          // (installed configuration name, idle nodes that meet the probe AND it)
+}
+
+/// configuration_overlap's answer (gpu_match_probe.cpp's ConfigurationOverlap)
+#[derive(Default, Debug, Clone)]
+pub struct ConfigurationOverlap {
+    pub names: Vec<String>,                   // constructor order
+    pub idle: Vec<u32>,                       // [a * names.len() + b]: idle nodes that meet both a and b (symmetric)
+}
+
 /// reason names in PM_WHY_* order
 const WHY_NAMES: [&str; 10] = ["ok", "no_specs", "cpu", "ram", "storage", "gpu_none", "gpu_count", "gpu_model", "gpu_mem", "gpu_total"];
 
@@ -610,9 +648,9 @@ impl GpuMatchPlugin {
     /// NodeGroupConfiguration (mod.rs:30-37) + ComputeRequirements / GpuRequirements (shared/models/node.rs:49-70)
     /// -> pm_config_row / pm_gpu_alt_row.  The requirement strings were already parsed by
     /// `ComputeRequirements::from_str` (serde), so this is a field-by-field projection.
-    fn set_configs(&mut self, templates: &[NodeGroupConfiguration]) {
+    fn pack_templates(templates: &[NodeGroupConfiguration], alts: &mut Vec<pm_gpu_alt_row>,
+                      req_models: &mut Vec<CString>) -> Vec<pm_config_row> {
         let mut rows = Vec::with_capacity(templates.len());
-        let mut alts: Vec<pm_gpu_alt_row> = Vec::new();
         let opt = |v: Option<u32>, bit: u32, flags: &mut u32| -> u32 { if v.is_some() { *flags |= bit; } v.unwrap_or(0) };
         for t in templates {
             let mut row = pm_config_row { min_group_size: t.min_group_size as u32, max_group_size: t.max_group_size as u32,
@@ -637,14 +675,20 @@ impl GpuMatchPlugin {
                     a.total_memory_max = opt(g.total_memory_max, G_TOT_MAX, &mut a.flags);
                     if let Some(m) = &g.model {
                         a.flags |= G_MODEL;
-                        a.model_row = self.req_models.len() as u32;
-                        self.req_models.push(CString::new(m.as_str()).expect("model string"));
+                        a.model_row = req_models.len() as u32;
+                        req_models.push(CString::new(m.as_str()).expect("model string"));
                     }
                     alts.push(a);
                 }
             }
             rows.push(row);
         }
+        rows
+    }
+
+    fn set_configs(&mut self, templates: &[NodeGroupConfiguration]) {
+        let mut alts: Vec<pm_gpu_alt_row> = Vec::new();
+        let rows = Self::pack_templates(templates, &mut alts, &mut self.req_models);
         let rc = unsafe { pm_set_configs(self.engine, rows.as_ptr(), rows.len() as u32, alts.as_ptr(), alts.len() as u32) };
         if rc == PM_EINVAL { panic!("Plugin configuration is invalid"); }                                   // mod.rs:145-147
         check(rc).expect("pm_set_configs");
@@ -1426,6 +1470,54 @@ impl GpuMatchPlugin {
             located: r.located,
             nodes: workers.iter().zip(km.iter()).take(r.n as usize).map(|(&w, &d)| (t.address_strings[w as usize].clone(), d)).collect(),
         }))
+    }
+
+    // ---- probing configurations (INTEGRATION.md "Diagnostics: probing configurations"): pm_probe_configs / pm_config_overlap
+
+    /// name, sizes and requirements of every probe, packed exactly as the constructor packs the installed ones, the model rule
+    /// against the node table's interned spec models.  One result per probe, in the given order.
+    pub fn probe_configurations(&self, probes: &[NodeGroupConfiguration]) -> Result<Vec<ProbeResult>> {
+        let mut alts: Vec<pm_gpu_alt_row> = Vec::new();
+        let mut req_models: Vec<CString> = Vec::new();
+        let rows = Self::pack_templates(probes, &mut alts, &mut req_models);
+        let t = self.nodes.read();           // (LOCK ORDER: nodes, the engine)
+        // the probes' model rule against the interned spec models: the list the installed table was last built against
+        let spec: Vec<CString> = t.spec_models.iter().map(|s| CString::new(s.as_str()).unwrap()).collect();
+        let spec_p: Vec<*const c_char> = spec.iter().map(|s| s.as_ptr()).collect();
+        let req_p: Vec<*const c_char> = req_models.iter().map(|s| s.as_ptr()).collect();
+        let words = (spec.len() + 31) / 32;
+        let mut bits = vec![0u32; (req_models.len() * words).max(1)];
+        check(unsafe { pm_host_build_model_table(req_p.as_ptr(), req_p.len() as u32, spec_p.as_ptr(), spec_p.len() as u32,
+                                                 bits.as_mut_ptr()) })?;
+        let c = self.config_names.len();
+        let mut out = vec![pm_probe_row::default(); rows.len().max(1)];
+        let mut overlap = vec![0u32; (rows.len() * c).max(1)];
+        check(unsafe { pm_probe_configs(self.engine, rows.as_ptr(), rows.len() as u32, alts.as_ptr(), alts.len() as u32,
+                                        bits.as_ptr(), req_p.len() as u32, spec_p.len() as u32, out.as_mut_ptr(),
+                                        overlap.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok(probes.iter().enumerate().map(|(p, probe)| {
+            let k = &out[p];
+            ProbeResult {
+                name: probe.name.clone(),
+                why: k.why,
+                eligible_meets: k.eligible_meets,
+                idle_meets: k.idle_meets,
+                idle_located: k.idle_located,
+                idle_exclusive: k.idle_exclusive,
+                groups_max: k.groups_max,
+                groups_exclusive: k.groups_exclusive,
+                overlap: self.config_names.iter().enumerate().map(|(i, n)| (n.clone(), overlap[p * c + i])).collect(),
+            }
+        }).collect())
+    }
+
+    pub fn configuration_overlap(&self) -> Result<ConfigurationOverlap> {
+        let c = self.config_names.len();
+        let mut idle = vec![0u32; (c * c).max(1)];
+        let mut n = 0u32;
+        check(unsafe { pm_config_overlap(self.engine, idle.as_mut_ptr(), (c * c) as u32, &mut n) })?;
+        idle.truncate(c * c);
+        Ok(ConfigurationOverlap { names: self.config_names.clone(), idle })
     }
 
     // ---- change feed (INTEGRATION.md "Change feed"): pm_enable_assignment_changes / pm_drain_assignment_changes by address
