@@ -46,7 +46,8 @@ extern "C" {
                             pm_config_report / pm_task_report (diagnostics), + pm_group_spread / pm_config_spread /
                             pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates),
                             + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed),
-                            + pm_probe_configs / pm_config_overlap (probes and configuration overlap): compatible
+                            + pm_probe_configs / pm_config_overlap (probes and configuration overlap),
+                            + pm_liveness_enable / _set / _get / _sweep / _transitions (liveness sweep): compatible
                             additions, the version stays 3 */
 
 enum {
@@ -603,6 +604,82 @@ typedef struct pm_change_row {
 } pm_change_row;
 int32_t pm_enable_assignment_changes(pm_engine*, uint32_t on); /* off also clears; on = resync */
 int32_t pm_drain_assignment_changes(pm_engine*, pm_change_row* rows, uint32_t cap, uint32_t* n, uint32_t* flags);
+
+/* ---- liveness (kernels in pm_liveness.inc) ----------------------------------------------------------------------------------
+ * The producer of the status changes pm_on_worker_status{,_many} consumes: NodeStatusUpdater::process_nodes / process_node
+ * (orchestrator/src/status_update/mod.rs:144-372), the reference's second per-interval loop over every node, as one sweep
+ * over the engine's worker rows.  Off by default; with it off nothing of the engine changes.
+ *
+ * THE LEDGER: two device-resident columns that the sweep alone reads and writes: a status byte (PM_NS_*, NodeStatus of
+ * models/node.rs:75-85 in its order) and a u32 unhealthy counter (heartbeat_store.rs' unhealthy counter) per worker row.
+ * pm_liveness_enable(on = 1) creates it for the rows [0, W): a row is Healthy if the host's current flags of it have
+ * PM_W_HEALTHY, else Discovered (NodeStatus::default); its counter is 0.  Rows appended later (pm_append_workers,
+ * pm_upload_workers(keep_groups = 1)) get the same initial value when the next liveness call first sees them.
+ * pm_upload_workers(keep_groups = 0) re-initialises every row and empties the list (the row identities are gone).  Enabling
+ * again re-initialises; on = 0 releases everything.  missing_heartbeat_threshold is the reference's constructor argument
+ * (mod.rs:43: 3 where the host gives none); any u32 is valid.
+ *
+ * pm_liveness_set is for every writer of a status other than the sweep: the discovery monitor's Dead / Ejected / Discovered /
+ * LowBalance (discovery/monitor.rs:262-389), the ban route (api/routes/nodes.rs:365), the invite (node/invite.rs:168-176:
+ * WaitingForHeartbeat and a cleared counter), a restart handing a predecessor's pm_liveness_get over.  counter == NULL writes 0.
+ * An index given more than once takes its last entry.  It touches the ledger only: the caller still tells the engine about
+ * flags and dissolutions through pm_on_worker_status*, as without liveness.
+ *
+ * pm_liveness_sweep is one process_nodes pass over the rows [0, W).  A row's heartbeat is PRESENT iff last_beat_ms[w] != 0 and
+ * (last_beat_ms[w] > now_ms or now_ms - last_beat_ms[w] <= PM_LIVE_TTL_MS); 0 means never beaten.  The reference leaves the
+ * edge millisecond to Redis (SET ... EX 90, heartbeat_store.rs:32: a key is gone some time after 90 s); here a beat exactly
+ * PM_LIVE_TTL_MS old is present and one a millisecond older is not.  in_pool_bits is the host's cached answer of
+ * is_node_in_pool (mod.rs:380-390), bit w & 63 of word w / 64; NULL is the cfg(test) stub: every row in the pool.  Per row,
+ * with m = the threshold and c the row's counter (mod.rs:215-311):
+ *   present, Unhealthy / Waiting / Discovered / Dead   -> in pool: Healthy, else Discovered; LISTED, also Discovered ->
+ *                                                         Discovered (status_changed = true, :242, :251)
+ *   present, Healthy / Ejected / Banned / LowBalance   -> unchanged, not listed
+ *   present, any                                       -> counter := 0 (:255-261)
+ *   absent, any                                        -> c' = c + 1, saturating at UINT32_MAX; counter := c' (:265-271)
+ *   absent, Healthy                                    -> Unhealthy, listed (:274-277)
+ *   absent, Unhealthy                                  -> Dead iff c' >= m (:278-283); listed iff changed
+ *   absent, Discovered                                 -> in pool: Unhealthy (:285-291); else Dead iff c' > PM_LIVE_GIVE_UP
+ *                                                         (:295); listed iff changed
+ *   absent, Waiting                                    -> Unhealthy iff c' >= m (:301-308); listed iff changed
+ *   absent, Dead / Ejected / Banned / LowBalance       -> unchanged, not listed (the counter still counts)
+ * DEVIATION: the counter saturates at UINT32_MAX; the reference's parse::<u32> of the incremented key fails there.
+ * The reference runs its nodes through FuturesUnordered, so its order is unpinned; ours is ascending row index.
+ *
+ * census[s] = the rows of [0, W) with status s AFTER the sweep; *n_transitions = the listed rows.  Either may be NULL.  The
+ * sweep always commits, and its list stays in the engine until the next sweep.  pm_liveness_transitions copies it out,
+ * ascending by worker index, counter = the value after the sweep; the convention of pm_drain_group_events: *n always,
+ * cap < *n or rows == NULL is PM_ERANGE with nothing copied.  Reading consumes nothing: a second call returns the same list.
+ * The list is made on the device; the count and the n rows cross to the host.
+ *
+ * apply != 0: after the list has reached the host every listed row goes through the body of pm_on_worker_status_many, in
+ * list order, with flags_new = the host's current flags of the row with PM_W_HEALTHY set iff new_status == Healthy and
+ * dead = (new_status == Dead): the life-cycle feed, the patched published rows, the pending deltas and the change feed are
+ * what that call by hand gives.  apply == 0 only reports.
+ *
+ * ERRORS.  PM_ESTATE: liveness is off; a stepwise tick is in progress; dist_world > 1 (and pm_dist_configure(world > 1) while
+ * liveness is on); workers were not uploaded yet (pm_liveness_enable alone may come first: it touches no row, and the first
+ * upload's rows are initialised like appended ones).  PM_EINVAL: last_beat_ms == NULL with W > 0; a status >= PM_NS_N.
+ * PM_ERANGE: an index >= W in set / get.  A failing call applies nothing and leaves the ledger and the previous list as they
+ * were.  A sweep with apply == 0, set, get and transitions leave the tick alone: no pending delta is consumed, nothing is
+ * compacted, no cache flag is cleared. */
+enum { PM_NS_DISCOVERED = 0, PM_NS_WAITING = 1, PM_NS_HEALTHY = 2, PM_NS_UNHEALTHY = 3,
+       PM_NS_DEAD = 4, PM_NS_EJECTED = 5, PM_NS_BANNED = 6, PM_NS_LOWBALANCE = 7, PM_NS_N = 8 };
+#define PM_LIVE_TTL_MS 90000u /* heartbeat_store.rs:32 (EX 90) */
+#define PM_LIVE_GIVE_UP 360u  /* status_update/mod.rs:295 */
+typedef struct pm_live_row {
+  uint32_t worker;
+  uint8_t old_status, new_status; /* PM_NS_* */
+  uint16_t _pad;
+  uint32_t counter; /* after the sweep */
+} pm_live_row;
+int32_t pm_liveness_enable(pm_engine*, uint32_t on, uint32_t missing_heartbeat_threshold);
+int32_t pm_liveness_set(pm_engine*, const uint32_t* idx, const uint8_t* status, const uint32_t* counter /* NULL = 0 */,
+                        uint32_t n);
+int32_t pm_liveness_get(pm_engine*, const uint32_t* idx, uint32_t n, uint8_t* status, uint32_t* counter /* either may be NULL */);
+int32_t pm_liveness_sweep(pm_engine*, uint64_t now_ms, const uint64_t* last_beat_ms /* W */,
+                          const uint64_t* in_pool_bits /* (W + 63) / 64 words, NULL = all in pool */, uint32_t apply,
+                          uint32_t* n_transitions, uint32_t* census /* PM_NS_N words */);
+int32_t pm_liveness_transitions(pm_engine*, pm_live_row* rows, uint32_t cap, uint32_t* n);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

@@ -190,6 +190,19 @@ struct ChangeDiffArgs {
   uint64_t* bitmap;             // [ceil(W / 64)] pending rows
 };
 
+// liveness (pm_liveness.inc): one process_nodes pass over the ledger
+struct LiveSweepArgs {
+  uint32_t W, m;             // rows; missing_heartbeat_threshold
+  uint64_t now_ms;
+  const uint64_t* beat;      // [W] last beat, ms; 0 = never
+  const uint64_t* pool;      // [ceil(W / 64)] is_node_in_pool bits, or nullptr = all in pool
+  uint8_t* status;           // [W] PM_NS_*
+  uint32_t* counter;         // [W]
+  uint8_t* old_status;       // [W] written for listed rows only
+  uint64_t* bitmap;          // [ceil(W / 64)] listed rows: every word is stored
+  uint32_t* census;          // [PM_NS_N], zero at launch
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -425,6 +438,14 @@ void launch_probe(const ProbeArgs& a, uint32_t max_blocks, hipStream_t s);
 void launch_assign_diff(const ChangeDiffArgs& a, hipStream_t s);
 void launch_change_list(const uint64_t* bitmap, uint32_t n_words, const uint8_t* what, uint32_t* prefix, uint32_t* total_host,
                         pm_change_row* out, hipStream_t s);
+// liveness (pm_liveness.inc)
+void launch_liveness_init(const uint32_t* flags, uint32_t first, uint32_t W, uint8_t* status, uint32_t* counter, hipStream_t s);
+void launch_liveness_sweep(const LiveSweepArgs& a, hipStream_t s);
+void launch_liveness_list(const uint64_t* bitmap, uint32_t n_words, const uint8_t* old_status, const uint8_t* status,
+                          const uint32_t* counter, uint32_t* prefix, uint32_t* total_host, pm_live_row* out, hipStream_t s);
+void launch_liveness_set(const uint32_t* stage, uint32_t n, uint8_t* status, uint32_t* counter, hipStream_t s);
+void launch_liveness_get(const uint32_t* idx, uint32_t n, const uint8_t* status, const uint32_t* counter, uint32_t* out,
+                         hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

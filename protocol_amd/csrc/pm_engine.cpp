@@ -65,6 +65,7 @@ namespace pm {
 #include "pm_engine_groups.inc"
 #include "pm_engine_carve.inc"
 #include "pm_engine_changes.inc"
+#include "pm_engine_liveness.inc"
 #include "pm_engine_match.inc"
 #include "pm_engine_merge.inc"
 }  // namespace pm
@@ -222,6 +223,7 @@ void pm_engine_destroy(pm_engine* e) {
   e->d_near_q.release(); e->d_near_out.release();
   e->d_probe_in.release(); e->d_probe_out.release();
   changes_release(e);
+  liveness_release(e);
   delete e->form;
   delete e;
 }
@@ -290,6 +292,9 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #define PM_CHANGES_ABI
 #include "pm_engine_changes.inc"
 #undef PM_CHANGES_ABI
+#define PM_LIVENESS_ABI
+#include "pm_engine_liveness.inc"
+#undef PM_LIVENESS_ABI
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

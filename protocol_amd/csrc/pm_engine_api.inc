@@ -19,14 +19,10 @@ int32_t pm_on_worker_status(pm_engine* e, uint32_t worker, uint32_t flags_new, u
   return PM_OK;
 }
 
-int32_t pm_on_worker_status_many(pm_engine* e, const uint32_t* workers, const uint32_t* flags_new, const uint32_t* dead,
-                                 uint32_t n) {
-  if (!e || (n && (!workers || !flags_new))) return set_error(PM_EINVAL, "null argument");
-  std::lock_guard<std::mutex> lk(e->mu);
-  if (e->dist_phase != 0) return set_error(PM_ESTATE, "a stepwise tick is in progress");
-  if (!e->have_workers) return set_error(PM_ERANGE, "worker index out of range");
-  for (uint32_t k = 0; k < n; ++k)
-    if (workers[k] >= e->W) return set_error(PM_ERANGE, "worker index out of range");
+// pm_on_worker_status_many's body, under the engine mutex, every index below W (also what an applying pm_liveness_sweep runs
+// its list through)
+static int32_t worker_status_many_locked(pm_engine* e, const uint32_t* workers, const uint32_t* flags_new, const uint32_t* dead,
+                                         uint32_t n) {
   if (!n) return PM_OK;
   HIPCHK(hipSetDevice(e->cfg.device));
 #ifdef PM_HOST_MARKS_STATUS  // (a measuring build: where a status sweep's time goes)
@@ -65,6 +61,17 @@ int32_t pm_on_worker_status_many(pm_engine* e, const uint32_t* workers, const ui
   host_mark("status: published rows patched");
 #endif
   return PM_OK;
+}
+
+int32_t pm_on_worker_status_many(pm_engine* e, const uint32_t* workers, const uint32_t* flags_new, const uint32_t* dead,
+                                 uint32_t n) {
+  if (!e || (n && (!workers || !flags_new))) return set_error(PM_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->dist_phase != 0) return set_error(PM_ESTATE, "a stepwise tick is in progress");
+  if (!e->have_workers) return set_error(PM_ERANGE, "worker index out of range");
+  for (uint32_t k = 0; k < n; ++k)
+    if (workers[k] >= e->W) return set_error(PM_ERANGE, "worker index out of range");
+  return worker_status_many_locked(e, workers, flags_new, dead, n);
 }
 
 int32_t pm_enable_group_events(pm_engine* e, uint32_t on) {

@@ -238,4 +238,25 @@ struct pm_engine {
   float k_ms_propose = 0;
   std::vector<hipEvent_t> prop_ev;  // (start, stop) pairs of the proposer launches of the current poll interval
   size_t prop_ev_used = 0;
+
+  // ---- liveness (pm_engine_liveness.inc; behind everything else, so that every member above keeps its place): the ledger
+  // (status byte, unhealthy counter) of the workers [0, live_W); rows behind live_W hold nothing yet (the init step writes
+  // them from the host's flags when the next liveness call sees them).  The last sweep's list: bitmap, old-status side bytes,
+  // per-word prefix, the rows; its count and the census in pinned memory.
+  bool live_on = false;
+  bool live_reinit = false;     // the row identities are gone (an upload that dropped the groups): initialise every row again
+  bool live_rows_host = false;  // h_live_rows holds the last sweep's list (an apply sweep brought it over)
+  uint32_t live_m = 0;          // missing_heartbeat_threshold
+  uint32_t live_W = 0, live_n = 0;
+  DevBuf<uint8_t> d_live_status, d_live_old;
+  DevBuf<uint32_t> d_live_counter;
+  DevBuf<uint64_t> d_live_bitmap;
+  DevBuf<uint32_t> d_live_prefix;
+  DevBuf<pm_live_row> d_live_rows;
+  DevBuf<uint32_t> d_live_census;  // PM_NS_N words
+  DevBuf<uint64_t> d_live_beat;    // the sweep's inputs: the beat column, behind it the pool bits
+  DevBuf<uint32_t> d_live_stage;   // set / get / init: indices, counters, packed status bytes
+  std::vector<pm_live_row> h_live_rows;
+  std::vector<uint32_t> h_live_stage;
+  uint32_t* h_live_count = nullptr;  // [0] listed rows, [1, 1 + PM_NS_N) census
 };

@@ -119,8 +119,12 @@ int32_t pm_upload_workers(pm_engine* e, const pm_worker_soa* w, uint32_t keep_gr
   int32_t rc = upload_worker_columns(e);
   if (rc) return rc;
   e->have_workers = true;
-  if (!keep_groups || e->h_group_of.size() > n) reset_groups_locked(e);
-  else e->h_group_of.resize(n, -1);  // (rows behind the known ones are new: in no group)
+  if (!keep_groups || e->h_group_of.size() > n) {
+    e->live_reinit = true;  // (liveness: the row identities are gone, the next liveness call starts the ledger over)
+    reset_groups_locked(e);
+  } else {
+    e->h_group_of.resize(n, -1);  // (rows behind the known ones are new: in no group)
+  }
   e->groups_dirty = true, e->groups_delta_ok = false;
   return PM_OK;
 }

@@ -791,5 +791,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_near.inc"          // nearest candidates: the per-query top-k selection, its launcher
 #include "pm_probe.inc"         // probes against the live swarm and configuration overlap: one sweep, its launcher
 #include "pm_changes.inc"       // assignment change feed: the per-publish diff, the drain's scan and expansion, their launchers
+#include "pm_liveness.inc"      // liveness sweep: process_node per row, the list's expansion, set / get, their launchers
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

@@ -65,6 +65,11 @@ assert probe_row_dt.itemsize == 64
 change_row_dt = np.dtype([("worker", "<u4"), ("what", "<u4")])
 CHG_GROUP, CHG_RING, CHG_TASK = 1, 2, 4
 CHANGES_RESYNC = 1
+# pm_live_row, PM_NS_* (include/pm_engine.h): liveness
+live_row_dt = np.dtype([("worker", "<u4"), ("old_status", "u1"), ("new_status", "u1"), ("_pad", "<u2"), ("counter", "<u4")])
+assert live_row_dt.itemsize == 12
+NS_DISCOVERED, NS_WAITING, NS_HEALTHY, NS_UNHEALTHY, NS_DEAD, NS_EJECTED, NS_BANNED, NS_LOWBALANCE, NS_N = range(9)
+LIVE_TTL_MS, LIVE_GIVE_UP = 90000, 360
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -135,6 +140,7 @@ EXPORTS = [
     "pm_nearest_workers",
     "pm_probe_configs", "pm_config_overlap",
     "pm_enable_assignment_changes", "pm_drain_assignment_changes",
+    "pm_liveness_enable", "pm_liveness_set", "pm_liveness_get", "pm_liveness_sweep", "pm_liveness_transitions",
 ]
 
 _lib = None
@@ -211,6 +217,11 @@ def lib() -> C.CDLL:
         L.pm_config_overlap.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_enable_assignment_changes.argtypes = [vp, u32]
         L.pm_drain_assignment_changes.argtypes = [vp, vp, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.pm_liveness_enable.argtypes = [vp, u32, u32]
+        L.pm_liveness_set.argtypes = [vp, vp, vp, vp, u32]
+        L.pm_liveness_get.argtypes = [vp, vp, u32, vp, vp]
+        L.pm_liveness_sweep.argtypes = [vp, u64, vp, vp, u32, C.POINTER(u32), vp]
+        L.pm_liveness_transitions.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -587,6 +598,52 @@ class Engine:
                 break
         rows = rows[:n.value]
         return rows["worker"].copy(), rows["what"].copy(), bool(flags.value & CHANGES_RESYNC)
+
+    # ---- liveness
+    def liveness_enable(self, on: bool = True, missing_heartbeat_threshold: int = 3):
+        """pm_liveness_enable: on = (re-)initialise the ledger from the host's flags; off releases it"""
+        check(lib().pm_liveness_enable(self._h, int(on), int(missing_heartbeat_threshold)))
+
+    def liveness_set(self, idx, status, counter=None):
+        """pm_liveness_set: ledger rows idx <- (status, counter or 0); a repeated index takes its last entry"""
+        i, s = _arr(idx, np.uint32), _arr(status, np.uint8)
+        c = _arr(counter, np.uint32) if counter is not None else None
+        assert len(i) == len(s) and (c is None or len(c) == len(i))
+        n = len(i)
+        check(lib().pm_liveness_set(self._h, i.ctypes.data if n else None, s.ctypes.data if n else None,
+                                    c.ctypes.data if c is not None and n else None, n))
+
+    def liveness_get(self, idx=None):
+        """pm_liveness_get -> (status uint8 [n], counter uint32 [n]) of the rows idx (None = every row)"""
+        i = _arr(idx, np.uint32) if idx is not None else np.arange(self.W, dtype=np.uint32)
+        n = len(i)
+        s, c = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32)
+        check(lib().pm_liveness_get(self._h, i.ctypes.data if n else None, n, s.ctypes.data if n else None,
+                                    c.ctypes.data if n else None))
+        return s, c
+
+    def liveness_sweep(self, now_ms: int, last_beat_ms, in_pool_bits=None, apply: bool = False):
+        """pm_liveness_sweep -> (n_transitions, census uint32 [NS_N]).  last_beat_ms: uint64 [W]; in_pool_bits: uint64
+        [(W + 63) // 64] or None (all in pool)"""
+        b = _arr(last_beat_ms, np.uint64) if last_beat_ms is not None else None
+        assert b is None or len(b) == self.W
+        p = _arr(in_pool_bits, np.uint64) if in_pool_bits is not None else None
+        assert p is None or len(p) == (self.W + 63) // 64
+        n, census = C.c_uint32(0), np.zeros(NS_N, dtype=np.uint32)
+        check(lib().pm_liveness_sweep(self._h, int(now_ms), b.ctypes.data if b is not None and len(b) else None,
+                                      p.ctypes.data if p is not None and len(p) else None, int(apply), C.byref(n),
+                                      census.ctypes.data))
+        return n.value, census
+
+    def liveness_transitions(self) -> np.ndarray:
+        """pm_liveness_transitions -> live_row_dt [n], ascending by worker: the last sweep's list (reading consumes nothing)"""
+        n = C.c_uint32(0)
+        rc = lib().pm_liveness_transitions(self._h, None, 0, C.byref(n))
+        if rc != -5:                                           # (PM_ERANGE is the size query's answer)
+            check(rc)
+        rows = np.zeros(max(n.value, 1), dtype=live_row_dt)
+        check(lib().pm_liveness_transitions(self._h, rows.ctypes.data, len(rows), C.byref(n)))
+        return rows[:n.value]
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

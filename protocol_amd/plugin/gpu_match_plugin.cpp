@@ -332,6 +332,7 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
         appended.push(row, i);
       }
     }
+    grow_beats_locked(t.rows.size());  // (the beat column covers every row a beat can find in the index)
     // The row map above is the plugin's truth from here on; the engine calls below bring the engine's worker table to
     // it.  If one of them fails the two have diverged (tombstones recorded here and never sent, rows appended here the
     // engine does not have): the next interval then re-sends the whole table instead of deltas.
@@ -866,8 +867,20 @@ void GpuMatchPlugin::handle_status_change(const OrchestratorNode& node) {
     nodes_.rows[w].flags = flags;
     dead = (node.status == NodeStatus::Dead || node.status == NodeStatus::LowBalance) ? 1u : 0u;
     check(pm_on_worker_status(engine_, w, flags, dead));
+    if (liveness_note_) liveness_note_(*this, w, node.status);  // (liveness on: the ledger learns what the host has set)
   }
   if (dead) emit_group_webhooks();  // the whole group was dissolved (status_update_impl.rs:17-29)
+}
+
+// the beat column holds at least `rows` entries (exclusive node lock): the values move, new entries read "never beaten"
+void GpuMatchPlugin::grow_beats_locked(size_t rows) {
+  if (rows <= beats_cap_) return;
+  const size_t cap = rows + rows / 2 + 64;
+  std::unique_ptr<std::atomic<uint64_t>[]> grown(new std::atomic<uint64_t>[cap]);
+  for (size_t i = 0; i < cap; ++i)
+    grown[i].store(i < beats_cap_ ? beats_[i].load(std::memory_order_relaxed) : 0, std::memory_order_relaxed);
+  beats_ = std::move(grown);
+  beats_cap_ = cap;
 }
 
 size_t GpuMatchPlugin::known_nodes() const {

@@ -382,6 +382,25 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // drains the feed.  std::out_of_range: the engine lists a row the node table does not hold.
   ChangedNodes changed_nodes() const;
 
+  // ---- liveness (INTEGRATION.md "Liveness"; gpu_match_liveness.cpp): NodeStatusUpdater::process_nodes
+  // (status_update/mod.rs:144-372) as pm_liveness_sweep over the plugin's rows, and the heartbeat route's
+  // heartbeat_store.beat (routes/heartbeat.rs:54-93) as a store into a column of atomics indexed by the node's row.
+  struct StatusTransition {
+    std::string address;
+    NodeStatus old_status, new_status;
+  };
+  // pm_liveness_enable(on = 1): the ledger starts from the rows' Healthy bit; from here on handle_status_change also
+  // writes the ledger (pm_liveness_set: the status; the counter kept, cleared by WaitingForHeartbeat as the invite does)
+  void enable_liveness(uint32_t missing_heartbeat_threshold = 3);
+  // no engine call: under the shared node lock.  An address the node table does not hold is ignored (the route answers
+  // such a node before it gets here).
+  void beat(const Address& address, uint64_t now_ms) const;
+  // one process_nodes pass: the engine sweeps with apply = 1 (flags, dissolutions and webhooks as handle_status_change would
+  // have them), the rows' Healthy bits follow, and the transitions come back in row order for the host's metric clean-up
+  // and chain sync (mod.rs:314-350, :118-142).  out_of_pool: the nodes is_node_in_pool (mod.rs:380-390) is false for;
+  // empty = the cfg(test) stub.
+  std::vector<StatusTransition> sweep_statuses(uint64_t now_ms, const std::vector<Address>& out_of_pool = {});
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -455,6 +474,15 @@ class GpuMatchPlugin : public SchedulerPlugin {
   mutable std::shared_mutex nodes_mu_;
   NodeTable nodes_;
   bool engine_rows_stale_ = false;   // an engine call of sync_nodes failed half-way: the next one re-sends every row
+  // liveness: the beat column (last beat in ms per row, 0 = never): stored under the SHARED node lock, grown and read whole
+  // under the exclusive one (sync_nodes, sweep_statuses)
+  std::unique_ptr<std::atomic<uint64_t>[]> beats_;
+  size_t beats_cap_ = 0;
+  void grow_beats_locked(size_t rows);
+  // set by enable_liveness to liveness_note (gpu_match_liveness.cpp; a pointer, so that gpu_match_plugin.cpp stays linkable
+  // against an engine without the liveness exports): handle_status_change's write to the ledger
+  void (*liveness_note_)(const GpuMatchPlugin&, uint32_t row, NodeStatus status) = nullptr;
+  static void liveness_note(const GpuMatchPlugin& self, uint32_t row, NodeStatus status);
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

@@ -157,6 +157,16 @@ int32_t pmx_configuration_overlap(pmx_plugin*, char* out, size_t cap, size_t* ne
 int32_t pmx_enable_change_feed(pmx_plugin*, int32_t on);
 int32_t pmx_changed_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
 
+/* ---- liveness (pm_plugin_liveness_c.cpp): GpuMatchPlugin::enable_liveness / beat / sweep_statuses.  out_of_pool: the addresses
+ * is_node_in_pool is false for (none = every node in the pool).  The text of pmx_sweep_statuses: one line
+ * "<address>\t<old status>\t<new status>" per transition, in row order (NodeStatus as its number, models/node.rs:75-85).  A
+ * sweep commits, so its text is held until a call's buffer has taken it: the size query (out NULL, cap 0) and the call behind
+ * it hand over one sweep. */
+int32_t pmx_enable_liveness(pmx_plugin*, uint32_t missing_heartbeat_threshold);
+int32_t pmx_beat(pmx_plugin*, const char* address, uint64_t now_ms);
+int32_t pmx_sweep_statuses(pmx_plugin*, uint64_t now_ms, const char* const* out_of_pool, uint32_t n_out_of_pool, char* out,
+                           size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

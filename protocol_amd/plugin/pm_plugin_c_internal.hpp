@@ -62,6 +62,8 @@ struct pmx_plugin {
   std::string restore_report;  // the last pmx_restore_groups' report (pmx_take_restore_report)
   std::string changed_text;    // pmx_changed_nodes: a drain's text, held while changed_text_pending (until a buffer took it)
   bool changed_text_pending = false;
+  std::string sweep_text;      // pmx_sweep_statuses: a sweep's text, held while sweep_text_pending (until a buffer took it)
+  bool sweep_text_pending = false;
 };
 
 #endif

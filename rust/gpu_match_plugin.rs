@@ -246,6 +246,56 @@ pub const CHG_RING: u32 = 2;
 pub const CHG_TASK: u32 = 4;
 pub const CHANGES_RESYNC: u32 = 1;
 
+/// pm_live_row (include/pm_engine.h): a row the last liveness sweep listed
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_live_row {
+    pub worker: u32,
+    pub old_status: u8,
+    pub new_status: u8,
+    pub _pad: u16,
+    pub counter: u32,
+}
+
+/// PM_NS_* (NodeStatus, models/node.rs:75-85, in its order), PM_LIVE_TTL_MS, PM_LIVE_GIVE_UP
+pub const NS_DISCOVERED: u8 = 0;
+pub const NS_WAITING: u8 = 1;
+pub const NS_HEALTHY: u8 = 2;
+pub const NS_UNHEALTHY: u8 = 3;
+pub const NS_DEAD: u8 = 4;
+pub const NS_EJECTED: u8 = 5;
+pub const NS_BANNED: u8 = 6;
+pub const NS_LOWBALANCE: u8 = 7;
+pub const NS_N: u8 = 8;
+pub const LIVE_TTL_MS: u32 = 90000;
+pub const LIVE_GIVE_UP: u32 = 360;
+
+fn node_status_code(s: &NodeStatus) -> u8 {
+    match s {
+        NodeStatus::Discovered => NS_DISCOVERED,
+        NodeStatus::WaitingForHeartbeat => NS_WAITING,
+        NodeStatus::Healthy => NS_HEALTHY,
+        NodeStatus::Unhealthy => NS_UNHEALTHY,
+        NodeStatus::Dead => NS_DEAD,
+        NodeStatus::Ejected => NS_EJECTED,
+        NodeStatus::Banned => NS_BANNED,
+        NodeStatus::LowBalance => NS_LOWBALANCE,
+    }
+}
+
+fn node_status_of(code: u8) -> NodeStatus {
+    match code {
+        NS_DISCOVERED => NodeStatus::Discovered,
+        NS_WAITING => NodeStatus::WaitingForHeartbeat,
+        NS_HEALTHY => NodeStatus::Healthy,
+        NS_UNHEALTHY => NodeStatus::Unhealthy,
+        NS_DEAD => NodeStatus::Dead,
+        NS_EJECTED => NodeStatus::Ejected,
+        NS_BANNED => NodeStatus::Banned,
+        _ => NodeStatus::LowBalance,          // (NS_LOWBALANCE: sweep_statuses has refused codes >= NS_N)
+    }
+}
+
 /// pm_force_regroup's metrics (PM_REGROUP_*)
 pub const REGROUP_ALL: u32 = 0;
 pub const REGROUP_DIAMETER: u32 = 1;
@@ -333,6 +383,12 @@ extern "C" {
     fn pm_config_overlap(e: *mut c_void, overlap: *mut u32, cap: u32, n_cfgs: *mut u32) -> i32;
     fn pm_enable_assignment_changes(e: *mut c_void, on: u32) -> i32;
     fn pm_drain_assignment_changes(e: *mut c_void, rows: *mut pm_change_row, cap: u32, n: *mut u32, flags: *mut u32) -> i32;
+    fn pm_liveness_enable(e: *mut c_void, on: u32, missing_heartbeat_threshold: u32) -> i32;
+    fn pm_liveness_set(e: *mut c_void, idx: *const u32, status: *const u8, counter: *const u32, n: u32) -> i32;
+    fn pm_liveness_get(e: *mut c_void, idx: *const u32, n: u32, status: *mut u8, counter: *mut u32) -> i32;
+    fn pm_liveness_sweep(e: *mut c_void, now_ms: u64, last_beat_ms: *const u64, in_pool_bits: *const u64, apply: u32,
+                         n_transitions: *mut u32, census: *mut u32) -> i32;
+    fn pm_liveness_transitions(e: *mut c_void, rows: *mut pm_live_row, cap: u32, n: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -448,6 +504,11 @@ struct NodeTable {
     /// an engine call of sync_nodes failed half-way: the row map above is ahead of the engine's worker table (tombstones
     /// recorded here and never sent, rows appended here the engine does not have) — the next interval re-sends every row
     engine_rows_stale: bool,
+    /// liveness: the last beat per row in ms, 0 = never — stored under the READ lock (beat), grown and read whole under the
+    /// write lock (sync_nodes, sweep_statuses)
+    beats: Vec<AtomicU64>,
+    /// enable_liveness was called: handle_status_change also writes the engine's ledger
+    liveness_on: bool,
 }
 
 pub struct GpuMatchPlugin {
@@ -781,6 +842,8 @@ impl GpuMatchPlugin {
                 }
             }
         }
+        let n_rows = t.rows.len();
+        t.beats.resize_with(n_rows, || AtomicU64::new(0));  // (the beat column covers every row a beat can find in the index)
         // The row map above is the plugin's truth from here on; the engine calls below bring the engine's worker table
         // to it.  If one of them fails the two have diverged: the next interval then re-sends the whole table.
         if t.engine_rows_stale {
@@ -1550,6 +1613,79 @@ impl GpuMatchPlugin {
         })
     }
 
+    // ---- liveness (INTEGRATION.md "Liveness"): NodeStatusUpdater::process_nodes (status_update/mod.rs:144-372) as
+    // pm_liveness_sweep over the plugin's rows; the heartbeat route's heartbeat_store.beat (routes/heartbeat.rs:54-93) as a
+    // store into a column of atomics indexed by the node's row
+
+    /// pm_liveness_enable(on = 1): the ledger starts from the rows' Healthy bit; from here on handle_status_change also
+    /// writes the ledger
+    pub fn enable_liveness(&self, missing_heartbeat_threshold: u32) -> Result<()> {
+        let mut t = self.nodes.write();       // (LOCK ORDER: nodes, the engine)
+        check(unsafe { pm_liveness_enable(self.engine, 1, missing_heartbeat_threshold) })?;
+        t.liveness_on = true;
+        Ok(())
+    }
+
+    /// handle_status_change's write to the ledger (the write lock is held): the discovery monitor's and the ban route's
+    /// statuses leave the unhealthy counter alone, the invite's WaitingForHeartbeat clears it (node/invite.rs:168-176)
+    fn liveness_note(&self, row: u32, status: &NodeStatus) -> Result<()> {
+        let s = node_status_code(status);
+        let mut counter = 0u32;
+        if *status != NodeStatus::WaitingForHeartbeat {
+            check(unsafe { pm_liveness_get(self.engine, &row, 1, std::ptr::null_mut(), &mut counter) })?;
+        }
+        check(unsafe { pm_liveness_set(self.engine, &row, &s, &counter, 1) })
+    }
+
+    /// no engine call: under the read lock.  An address the node table does not hold is ignored.
+    pub fn beat(&self, address: &Address, now_ms: u64) {
+        let t = self.nodes.read();
+        if let Some(&w) = t.index.get(address) {
+            if let Some(b) = t.beats.get(w as usize) { b.store(now_ms, Ordering::Relaxed); }
+        }
+    }
+
+    /// one process_nodes pass: the engine sweeps with apply = 1, the rows' Healthy bits follow, and the transitions come
+    /// back in row order for the host's metric clean-up and chain sync (mod.rs:314-350, :118-142).  out_of_pool: the nodes
+    /// is_node_in_pool (mod.rs:380-390) is false for; empty = the cfg(test) stub.
+    pub fn sweep_statuses(&self, now_ms: u64, out_of_pool: &[Address]) -> Result<Vec<(String, NodeStatus, NodeStatus)>> {
+        let mut t = self.nodes.write();       // (LOCK ORDER: nodes, the engine; the rows' flags are written below)
+        let w_rows = t.rows.len();
+        let beats: Vec<u64> = (0..w_rows).map(|w| t.beats.get(w).map_or(0, |b| b.load(Ordering::Relaxed))).collect();
+        let mut pool: Vec<u64> = Vec::new();
+        if !out_of_pool.is_empty() {
+            pool = vec![!0u64; (w_rows + 63) / 64];
+            for a in out_of_pool {
+                if let Some(&w) = t.index.get(a) { pool[(w >> 6) as usize] &= !(1u64 << (w & 63)); }
+            }
+        }
+        let mut n = 0u32;
+        check(unsafe { pm_liveness_sweep(self.engine, now_ms, if w_rows != 0 { beats.as_ptr() } else { std::ptr::null() },
+                                         if pool.is_empty() { std::ptr::null() } else { pool.as_ptr() }, 1, &mut n,
+                                         std::ptr::null_mut()) })?;
+        let mut rows = vec![pm_live_row::default(); n.max(1) as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_liveness_transitions(self.engine, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;
+        if got != n { return Err(anyhow!("sweep_statuses: the list is not the sweep's")); }
+        for r in &rows[..n as usize] {
+            if r.worker as usize >= w_rows || r.old_status >= NS_N || r.new_status >= NS_N {
+                return Err(anyhow!("sweep_statuses: the engine lists a row the node table does not hold"));
+            }
+        }
+        let mut out = Vec::with_capacity(n as usize);
+        let mut any_dead = false;
+        for r in &rows[..n as usize] {
+            let mut flags = t.rows[r.worker as usize].flags & !W_HEALTHY;   // (what the engine's apply gave the row)
+            if r.new_status == NS_HEALTHY { flags |= W_HEALTHY; }
+            t.rows[r.worker as usize].flags = flags;
+            any_dead = any_dead || r.new_status == NS_DEAD;
+            out.push((t.address_strings[r.worker as usize].clone(), node_status_of(r.old_status), node_status_of(r.new_status)));
+        }
+        drop(t);
+        if any_dead { self.emit_group_webhooks()?; }       // whole groups were dissolved (status_update_impl.rs:17-29)
+        Ok(out)
+    }
+
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).
     pub(crate) fn handle_status_change(&self, node: &OrchestratorNode) -> Result<()> {
         let mut t = self.nodes.write();
@@ -1559,6 +1695,7 @@ impl GpuMatchPlugin {
         t.rows[w as usize].flags = flags;
         let dead = matches!(node.status, NodeStatus::Dead | NodeStatus::LowBalance) as u32;
         check(unsafe { pm_on_worker_status(self.engine, w, flags, dead) })?;
+        if t.liveness_on { self.liveness_note(w, &node.status)?; }   // (the ledger learns what the host has set)
         drop(t);
         if dead != 0 { self.emit_group_webhooks()?; }      // the whole group was dissolved (status_update_impl.rs:17-29)
         Ok(())

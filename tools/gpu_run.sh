@@ -22,6 +22,8 @@
 #   host                     PM_TRACE_HOST marks of a cold match and of churn ticks + the rocprofv3 kernel timeline of a match
 #   profiles:<rNN>           tools/collect_profiles.py <rNN>: kernel statistics, PMC passes, bench line -> gpurun_out/<rNN>/
 #   fuzz[:<swarms>[:<seed>[:<kind>,<kind>]]]  tools/parity_fuzz.py (engine against oracle on random swarms; all kinds unless named)
+#   liveness[:<args>]        tools/liveness_probe.py [W] [--bench DIR]: pm_liveness_sweep at W rows (100000), reporting and applying
+#                            -> r18_liveness.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -137,6 +139,9 @@ PY
       IFS=: read -r swarms seed kinds <<< "$arg"
       timeout 3000 python tools/parity_fuzz.py ${swarms:+--swarms $swarms} ${seed:+--seed $seed} ${kinds:+--kinds $kinds} > "$out/${n}_fuzz.txt" 2>&1; echo "fuzz rc=$?"
       tail -15 "$out/${n}_fuzz.txt" ;;
+    liveness)
+      timeout -k 10 300 python tools/liveness_probe.py $arg --out "$out/r18_liveness.txt" > "$out/${n}_liveness.log" 2>&1; echo "liveness rc=$?"
+      tail -12 "$out/${n}_liveness.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
