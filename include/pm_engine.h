@@ -47,8 +47,8 @@ extern "C" {
                             pm_force_regroup (group geography), + pm_nearest_workers (nearest candidates),
                             + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed),
                             + pm_probe_configs / pm_config_overlap (probes and configuration overlap),
-                            + pm_liveness_enable / _set / _get / _sweep / _transitions (liveness sweep): compatible
-                            additions, the version stays 3 */
+                            + pm_liveness_enable / _set / _get / _sweep / _transitions (liveness sweep),
+                            + pm_discovery_sync (discovery sync): compatible additions, the version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -619,8 +619,8 @@ int32_t pm_drain_assignment_changes(pm_engine*, pm_change_row* rows, uint32_t ca
  * again re-initialises; on = 0 releases everything.  missing_heartbeat_threshold is the reference's constructor argument
  * (mod.rs:43: 3 where the host gives none); any u32 is valid.
  *
- * pm_liveness_set is for every writer of a status other than the sweep: the discovery monitor's Dead / Ejected / Discovered /
- * LowBalance (discovery/monitor.rs:262-389), the ban route (api/routes/nodes.rs:365), the invite (node/invite.rs:168-176:
+ * pm_liveness_set is for every writer of a status other than the sweep and the discovery monitor (which has its own call,
+ * pm_discovery_sync below): the ban route (api/routes/nodes.rs:365), the invite (node/invite.rs:168-176:
  * WaitingForHeartbeat and a cleared counter), a restart handing a predecessor's pm_liveness_get over.  counter == NULL writes 0.
  * An index given more than once takes its last entry.  It touches the ledger only: the caller still tells the engine about
  * flags and dissolutions through pm_on_worker_status*, as without liveness.
@@ -680,6 +680,73 @@ int32_t pm_liveness_sweep(pm_engine*, uint64_t now_ms, const uint64_t* last_beat
                           const uint64_t* in_pool_bits /* (W + 63) / 64 words, NULL = all in pool */, uint32_t apply,
                           uint32_t* n_transitions, uint32_t* census /* PM_NS_N words */);
 int32_t pm_liveness_transitions(pm_engine*, pm_live_row* rows, uint32_t cap, uint32_t* n);
+
+/* ---- discovery sync (kernels in pm_discovery.inc) ---------------------------------------------------------------------------
+ * The other producer of status changes: DiscoveryMonitor::get_nodes -> sync_single_node_with_discovery
+ * (orchestrator/src/discovery/monitor.rs:218-435) for a whole de-duplicated discovery list (:202-209) in one call.  It reads and
+ * writes the liveness ledger's status byte (pm_liveness_enable must be on; the counter column is not touched).
+ *
+ * The reference syncs row j against the store as the rows 0..j-1 left it, and per row fetches every node to count the OTHER
+ * Healthy nodes with the discovery row's ip and port (:218-234).  Here endpoints are dense ids the host interns from "ip:port"
+ * (as it interns spec models); the table's endpoint column comes whole with every call (row_endpoint[w], PM_EP_NONE = a row
+ * that matches nothing), the engine keeps none.  The count is exact for the sequential pass, see DESIGN.md "Discovery sync":
+ *   cnt(j, k) =   #{unlisted Healthy table rows with endpoint k}
+ *               + #{listed, initially Healthy rows i with table endpoint k and position p_i > j}
+ *               + #{listed, initially Healthy rows i, Healthy after their own step, endpoint after their step k, p_i < j}
+ *
+ * A row (pm_disc_row) is a table row or PM_DISC_NEW.  NEW (:397-413): cnt >= max_healthy_same_endpoint -> PM_DO_SKIP, else
+ * PM_DO_ADMIT; nothing is written, the host appends the admitted ones afterwards and the ledger's ordinary initialisation makes
+ * them Discovered (old_status = PM_NS_N, final_status = Discovered if admitted, else PM_NS_N).  A TABLE ROW (:252-396), s = its
+ * ledger status:
+ *   1. cnt > 0 and s != Healthy -> update(Dead); done.
+ *   2. VALIDATED and not WHITELISTED -> update(Ejected).
+ *   3. VALIDATED and WHITELISTED and s == Ejected -> update(Dead).
+ *   4. not ACTIVE and s == Healthy, and last_change_ms == 0 or now_ms - last_change_ms > PM_DISC_GRACE_MS (signed: a stamp in
+ *      the future does not mark) -> update(Ejected if not WHITELISTED, else Dead).
+ *   5. endpoint_after != row_endpoint[row] -> PM_DO_IP_REWRITE: add_node(snapshot with the new ip) PUTS THE SNAPSHOT'S STATUS
+ *      AND STAMP BACK over what 2-4 wrote (node_store.rs:27-60, 211-226), no handler fired.
+ *   6. LOCATION_NEW -> PM_DO_LOCATION (the store write is the host's).
+ *   7. s == Dead, both stamps non-zero, last_change_ms < last_updated_ms: SPECS_DIFFER -> PM_DO_SPECS_REWRITE, again the
+ *      whole snapshot (status Dead, the old stamp, the OLD ip); then update(Discovered).
+ *   8. BALANCE_ZERO -> update(LowBalance).
+ * update(n) records (the store's current status, n) in upd_old / upd_new — what the handlers saw (:65-88) — and sets the
+ * status; at most three per row.  The row's endpoint after its step is endpoint_after iff 5 ran and 7's rewrite did not.
+ * PM_DO_STAMP_NOW: the store's last_status_change ends as now_ms (an update came after the last put-back).
+ *
+ * The call always commits status[row] = final_status for listed table rows.  apply != 0: still under the engine mutex every
+ * update goes, in discovery order, through the body of pm_on_worker_status_many with flags_new = the host's current flags with
+ * PM_W_HEALTHY cleared and dead = (new is Dead or LowBalance: status_update_impl.rs:16-29); where a put-back left
+ * final_status == Healthy after an update, one more entry for that row follows (PM_W_HEALTHY set, dead = 0).
+ * *n_updates_total = the sum of n_updates.  One staged copy in, four kernels, one copy back, one stream synchronisation.
+ *
+ * ERRORS.  PM_ESTATE exactly where the liveness calls give it.  PM_EINVAL: rows == NULL with n_rows > 0; row_endpoint == NULL
+ * with W > 0; unknown flag bits; a table row listed twice; n_endpoints > W + 2 n_rows.  PM_ERANGE: a row >= W other than
+ * PM_DISC_NEW; an endpoint >= n_endpoints (endpoint_after: on table rows); a row_endpoint[w] >= n_endpoints other than
+ * PM_EP_NONE.  A failing call applies nothing and leaves the ledger as it was.  n_rows == 0 is PM_OK and changes nothing. */
+#define PM_DISC_NEW 0xFFFFFFFFu  /* pm_disc_row.row: the address is not in the table */
+#define PM_EP_NONE 0xFFFFFFFFu   /* row_endpoint[w]: matches nothing (a row the host has retired) */
+#define PM_DISC_GRACE_MS 300000u /* monitor.rs:304 */
+enum { PM_DF_VALIDATED = 1, PM_DF_WHITELISTED = 2, PM_DF_ACTIVE = 4, PM_DF_LOCATION_NEW = 8,
+       PM_DF_SPECS_DIFFER = 16, PM_DF_BALANCE_ZERO = 32 };
+typedef struct pm_disc_row {   /* 32 bytes */
+  uint32_t row;                /* table row or PM_DISC_NEW */
+  uint32_t endpoint;           /* interned "ip:port" of the DISCOVERY row: the key of the count */
+  uint32_t endpoint_after;     /* interned "discovery ip : STORED port": what the row holds after step 5; ignored for new rows */
+  uint32_t flags;              /* PM_DF_* */
+  uint64_t last_change_ms;     /* ex.last_status_change, 0 = None */
+  uint64_t last_updated_ms;    /* discovery.last_updated, 0 = None */
+} pm_disc_row;
+enum { PM_DO_ADMIT = 1, PM_DO_SKIP = 2, PM_DO_IP_REWRITE = 4, PM_DO_LOCATION = 8, PM_DO_SPECS_REWRITE = 16,
+       PM_DO_STAMP_NOW = 32 };
+typedef struct pm_disc_result { /* 16 bytes, one per input row, in input order */
+  uint32_t healthy_same_endpoint; /* cnt, for every row, the Healthy ones too */
+  uint8_t old_status, final_status, n_updates, ops;
+  uint8_t upd_old[3], upd_new[3]; /* the updates in order: what the handlers saw */
+  uint16_t _pad;
+} pm_disc_result;
+int32_t pm_discovery_sync(pm_engine*, uint64_t now_ms, const uint32_t* row_endpoint /* W */, uint32_t n_endpoints,
+                          uint32_t max_healthy_same_endpoint, const pm_disc_row* rows, uint32_t n_rows, uint32_t apply,
+                          pm_disc_result* out /* n_rows, may be NULL */, uint32_t* n_updates_total /* may be NULL */);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

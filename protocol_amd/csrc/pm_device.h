@@ -203,6 +203,23 @@ struct LiveSweepArgs {
   uint32_t* census;          // [PM_NS_N], zero at launch
 };
 
+// discovery sync (pm_discovery.inc): one DiscoveryMonitor pass, the ledger's status column joined with the discovery list
+struct DiscArgs {
+  uint32_t W, D, E, max_same;  // table rows; discovery rows; endpoint ids; max_healthy_nodes_with_same_endpoint
+  uint64_t now_ms;
+  const pm_disc_row* rows;     // [D]
+  const uint32_t* row_endpoint;  // [W] endpoint id or PM_EP_NONE
+  uint8_t* status;             // [W] the ledger's status bytes
+  uint32_t* pos_of_row;        // [W] position in the list, preset to PM_DISC_NEW (= unlisted)
+  uint32_t* base;              // [E] S: unlisted Healthy rows per endpoint, zero at launch
+  uint32_t* ev_cnt;            // [E] events per endpoint, zero at launch
+  uint32_t* ev_off;            // [E] first event of the endpoint's segment (written where ev_cnt != 0)
+  uint32_t* ev_fill;           // [E] scatter cursor inside the segment, zero at launch
+  uint32_t* cursor;            // [1] segments handed out so far, zero at launch
+  uint64_t* events;            // [sum of ev_cnt <= 2 D] position << 1 | kind (0 = before, 1 = after)
+  pm_disc_result* out;         // [D]
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -446,6 +463,8 @@ void launch_liveness_list(const uint64_t* bitmap, uint32_t n_words, const uint8_
 void launch_liveness_set(const uint32_t* stage, uint32_t n, uint8_t* status, uint32_t* counter, hipStream_t s);
 void launch_liveness_get(const uint32_t* idx, uint32_t n, const uint8_t* status, const uint32_t* counter, uint32_t* out,
                          hipStream_t s);
+// discovery sync (pm_discovery.inc): mark, base, segments + scatter, query and decide, in this order on s
+void launch_discovery_sync(const DiscArgs& a, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -65,6 +65,7 @@ namespace pm {
 #include "pm_engine_groups.inc"
 #include "pm_engine_carve.inc"
 #include "pm_engine_changes.inc"
+#include "pm_engine_discovery.inc"
 #include "pm_engine_liveness.inc"
 #include "pm_engine_match.inc"
 #include "pm_engine_merge.inc"
@@ -295,6 +296,9 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #define PM_LIVENESS_ABI
 #include "pm_engine_liveness.inc"
 #undef PM_LIVENESS_ABI
+#define PM_DISCOVERY_ABI
+#include "pm_engine_discovery.inc"
+#undef PM_DISCOVERY_ABI
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

@@ -13,6 +13,7 @@ static void liveness_release(pm_engine* e) {
   e->d_live_status.release(); e->d_live_old.release(); e->d_live_counter.release(); e->d_live_bitmap.release();
   e->d_live_prefix.release(); e->d_live_rows.release(); e->d_live_census.release(); e->d_live_beat.release();
   e->d_live_stage.release();
+  discovery_release(e);
   if (e->h_live_count) (void)hipHostFree(e->h_live_count);
   e->h_live_count = nullptr;
   e->h_live_rows.clear();

@@ -259,4 +259,14 @@ struct pm_engine {
   std::vector<pm_live_row> h_live_rows;
   std::vector<uint32_t> h_live_stage;
   uint32_t* h_live_count = nullptr;  // [0] listed rows, [1, 1 + PM_NS_N) census
+
+  // ---- discovery sync (pm_engine_discovery.inc): scratch of one pm_discovery_sync, released with the ledger
+  DevBuf<uint64_t> d_disc_in;      // the staged inputs: the rows (32 bytes each), behind them the endpoint column
+  DevBuf<uint32_t> d_disc_work;    // pos_of_row [W] | base, ev_cnt, ev_fill [E each], cursor [1] | ev_off [E]
+  DevBuf<uint64_t> d_disc_events;  // [2 n_rows]
+  DevBuf<pm_disc_result> d_disc_out;
+  std::vector<uint64_t> h_disc_in;
+  std::vector<pm_disc_result> h_disc_out;
+  std::vector<uint32_t> h_disc_seen;  // [W] the call (disc_epoch) that last listed the row: a row listed twice
+  uint32_t disc_epoch = 0;
 };

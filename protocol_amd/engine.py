@@ -70,6 +70,15 @@ live_row_dt = np.dtype([("worker", "<u4"), ("old_status", "u1"), ("new_status", 
 assert live_row_dt.itemsize == 12
 NS_DISCOVERED, NS_WAITING, NS_HEALTHY, NS_UNHEALTHY, NS_DEAD, NS_EJECTED, NS_BANNED, NS_LOWBALANCE, NS_N = range(9)
 LIVE_TTL_MS, LIVE_GIVE_UP = 90000, 360
+# pm_disc_row, pm_disc_result, PM_DF_*, PM_DO_* (include/pm_engine.h): discovery sync
+disc_row_dt = np.dtype([("row", "<u4"), ("endpoint", "<u4"), ("endpoint_after", "<u4"), ("flags", "<u4"),
+                        ("last_change_ms", "<u8"), ("last_updated_ms", "<u8")])
+disc_result_dt = np.dtype([("healthy_same_endpoint", "<u4"), ("old_status", "u1"), ("final_status", "u1"), ("n_updates", "u1"),
+                           ("ops", "u1"), ("upd_old", "u1", (3,)), ("upd_new", "u1", (3,)), ("_pad", "<u2")])
+assert disc_row_dt.itemsize == 32 and disc_result_dt.itemsize == 16
+DISC_NEW, EP_NONE, DISC_GRACE_MS = 0xFFFFFFFF, 0xFFFFFFFF, 300000
+DF_VALIDATED, DF_WHITELISTED, DF_ACTIVE, DF_LOCATION_NEW, DF_SPECS_DIFFER, DF_BALANCE_ZERO = 1, 2, 4, 8, 16, 32
+DO_ADMIT, DO_SKIP, DO_IP_REWRITE, DO_LOCATION, DO_SPECS_REWRITE, DO_STAMP_NOW = 1, 2, 4, 8, 16, 32
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -141,6 +150,7 @@ EXPORTS = [
     "pm_probe_configs", "pm_config_overlap",
     "pm_enable_assignment_changes", "pm_drain_assignment_changes",
     "pm_liveness_enable", "pm_liveness_set", "pm_liveness_get", "pm_liveness_sweep", "pm_liveness_transitions",
+    "pm_discovery_sync",
 ]
 
 _lib = None
@@ -222,6 +232,7 @@ def lib() -> C.CDLL:
         L.pm_liveness_get.argtypes = [vp, vp, u32, vp, vp]
         L.pm_liveness_sweep.argtypes = [vp, u64, vp, vp, u32, C.POINTER(u32), vp]
         L.pm_liveness_transitions.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_discovery_sync.argtypes = [vp, u64, vp, u32, u32, vp, u32, u32, vp, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -644,6 +655,21 @@ class Engine:
         rows = np.zeros(max(n.value, 1), dtype=live_row_dt)
         check(lib().pm_liveness_transitions(self._h, rows.ctypes.data, len(rows), C.byref(n)))
         return rows[:n.value]
+
+    # ---- discovery sync
+    def discovery_sync(self, now_ms: int, row_endpoint, n_endpoints: int, max_healthy_same_endpoint: int, rows,
+                       apply: bool = False):
+        """pm_discovery_sync -> (disc_result_dt [n_rows] in input order, n_updates_total).  row_endpoint: uint32 [W] (EP_NONE =
+        matches nothing); rows: disc_row_dt [n_rows], the de-duplicated discovery list in order"""
+        ep = _arr(row_endpoint, np.uint32) if row_endpoint is not None else None
+        assert ep is None or len(ep) == self.W
+        r = np.ascontiguousarray(rows, dtype=disc_row_dt)
+        n, total = len(r), C.c_uint32(0)
+        out = np.zeros(n, dtype=disc_result_dt)
+        check(lib().pm_discovery_sync(self._h, int(now_ms), ep.ctypes.data if ep is not None and len(ep) else None,
+                                      int(n_endpoints), int(max_healthy_same_endpoint), r.ctypes.data if n else None, n,
+                                      int(apply), out.ctypes.data if n else None, C.byref(total)))
+        return out, total.value
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

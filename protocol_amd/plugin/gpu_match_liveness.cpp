@@ -62,6 +62,7 @@ std::vector<GpuMatchPlugin::StatusTransition> GpuMatchPlugin::sweep_statuses(uin
       uint32_t flags = t.rows[r.worker].flags & ~uint32_t(PM_W_HEALTHY);  // (what the engine's apply gave the row)
       if (r.new_status == PM_NS_HEALTHY) flags |= PM_W_HEALTHY;
       t.rows[r.worker].flags = flags;
+      note_stamp_locked(r.worker, now_ms);
       any_dead = any_dead || r.new_status == PM_NS_DEAD;
       out.push_back(StatusTransition{t.address_strings[r.worker], NodeStatus(r.old_status), NodeStatus(r.new_status)});
     }

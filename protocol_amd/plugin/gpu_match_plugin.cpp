@@ -868,6 +868,7 @@ void GpuMatchPlugin::handle_status_change(const OrchestratorNode& node) {
     dead = (node.status == NodeStatus::Dead || node.status == NodeStatus::LowBalance) ? 1u : 0u;
     check(pm_on_worker_status(engine_, w, flags, dead));
     if (liveness_note_) liveness_note_(*this, w, node.status);  // (liveness on: the ledger learns what the host has set)
+    note_stamp_locked(w, uint64_t(clock()));  // (update_node_status stamps last_status_change: node_store.rs:284-305)
   }
   if (dead) emit_group_webhooks();  // the whole group was dissolved (status_update_impl.rs:17-29)
 }
@@ -881,6 +882,12 @@ void GpuMatchPlugin::grow_beats_locked(size_t rows) {
     grown[i].store(i < beats_cap_ ? beats_[i].load(std::memory_order_relaxed) : 0, std::memory_order_relaxed);
   beats_ = std::move(grown);
   beats_cap_ = cap;
+}
+
+// last_status_change of a row (exclusive node lock): what sync_discovery hands the engine as the snapshot's stamp
+void GpuMatchPlugin::note_stamp_locked(uint32_t row, uint64_t ms) {
+  if (stamps_.size() <= row) stamps_.resize(nodes_.rows.size() > row ? nodes_.rows.size() : size_t(row) + 1, 0);
+  stamps_[row] = ms;
 }
 
 size_t GpuMatchPlugin::known_nodes() const {

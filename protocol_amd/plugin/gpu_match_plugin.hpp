@@ -401,6 +401,41 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // empty = the cfg(test) stub.
   std::vector<StatusTransition> sweep_statuses(uint64_t now_ms, const std::vector<Address>& out_of_pool = {});
 
+  // ---- discovery sync (INTEGRATION.md "Discovery sync"; gpu_match_discovery.cpp): DiscoveryMonitor::get_nodes ->
+  // sync_single_node_with_discovery (discovery/monitor.rs:218-435) as pm_discovery_sync over the plugin's rows.  Needs
+  // enable_liveness (the statuses are the ledger's).  The plugin keeps the store's ip and port per row (the endpoint column;
+  // OrchestratorNode does not carry them: set_endpoint tells them, and a sync's own ip rewrites follow), the interning map
+  // "ip:port" -> endpoint id, and last_status_change per row (set by handle_status_change, sweep_statuses and sync_discovery).
+  struct DiscoverySighting {       // what sync_single_node_with_discovery reads of a DiscoveryNode
+    Address address;
+    std::string ip_address;
+    uint16_t port = 0;
+    bool is_validated = false, is_provider_whitelisted = false, is_active = false;
+    bool location_new = false;     // the store's location is None and discovery's is Some (monitor.rs:345)
+    bool specs_differ = false;     // existing_node.compute_specs != discovery_node.compute_specs (:367)
+    bool balance_zero = false;     // latest_balance == Some(0) (:385-386)
+    uint64_t last_updated_ms = 0;  // discovery.last_updated, 0 = None
+  };
+  struct DiscoveryOutcome {        // one per sighting, in order
+    enum class Kind { Admitted, Skipped, Synced } kind = Kind::Synced;
+    std::string address;
+    uint32_t healthy_same_endpoint = 0;
+    NodeStatus old_status = NodeStatus::Discovered, final_status = NodeStatus::Discovered;  // (Synced)
+    std::vector<std::pair<NodeStatus, NodeStatus>> updates;                                // (old, new) as the handlers saw them
+    bool ip_rewritten = false, location_new = false, specs_rewritten = false, stamped_now = false;
+  };
+  // the store's ip and port of a node the plugin has a row for (start-up, add_node by another writer); unknown addresses are
+  // remembered until sync_nodes brings their row
+  void set_endpoint(const Address& address, const std::string& ip_address, uint16_t port);
+  // one get_nodes pass, applied (flags, dissolutions, webhooks as handle_status_change would have them; the rows' Healthy bits,
+  // stamps and endpoints follow).  A sighting whose address has no present row is the reference's Ok(None): admitted or
+  // skipped.  ADMITTED NODES ARE RETURNED, NOT APPENDED: the caller adds them to its store and the next sync_nodes brings their
+  // rows (their endpoint is remembered from the sighting).  The store writes of location and specs are the caller's.
+  std::vector<DiscoveryOutcome> sync_discovery(uint64_t now_ms, const std::vector<DiscoverySighting>& sightings,
+                                               uint32_t max_same_endpoint);
+  std::optional<std::pair<std::string, uint16_t>> endpoint_of(const Address& address) const;  // (what the tests look at)
+  uint64_t last_status_change_ms(const Address& address) const;                               // 0 = None
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -483,6 +518,20 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // against an engine without the liveness exports): handle_status_change's write to the ledger
   void (*liveness_note_)(const GpuMatchPlugin&, uint32_t row, NodeStatus status) = nullptr;
   static void liveness_note(const GpuMatchPlugin& self, uint32_t row, NodeStatus status);
+  // discovery sync (exclusive node lock): the endpoint column by row (ip empty = unknown: PM_EP_NONE), the interning map, the
+  // endpoints of addresses without a row yet; last_status_change per row in ms, 0 = None.  Both grow lazily to the rows.
+  struct EndpointColumn {
+    std::vector<std::string> ip;
+    std::vector<uint16_t> port;
+    std::vector<uint32_t> id;
+    std::unordered_map<std::string, uint32_t> intern;
+    std::unordered_map<Address, std::pair<std::string, uint16_t>, AddressHash> pending;
+  };
+  EndpointColumn endpoints_;
+  std::vector<uint64_t> stamps_;
+  void note_stamp_locked(uint32_t row, uint64_t ms);
+  uint32_t intern_endpoint_locked(const std::string& ip, uint16_t port);
+  void fit_endpoints_locked();
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

@@ -167,6 +167,23 @@ int32_t pmx_beat(pmx_plugin*, const char* address, uint64_t now_ms);
 int32_t pmx_sweep_statuses(pmx_plugin*, uint64_t now_ms, const char* const* out_of_pool, uint32_t n_out_of_pool, char* out,
                            size_t cap, size_t* needed);
 
+/* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
+ * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
+ * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's
+ * endpoint, ops = the letters of i (ip rewritten), l (location new), s (specs rewritten), n (last_status_change is now), the
+ * updates as the handlers saw them.  Admitted nodes are returned, not appended: the next pmx_sync_nodes brings their rows.  A sync
+ * commits, so its text is held until a call's buffer has taken it, as pmx_sweep_statuses' is. */
+typedef struct pmx_sighting {
+  const char* address;
+  const char* ip_address;
+  uint16_t port;
+  uint8_t is_validated, is_provider_whitelisted, is_active, location_new, specs_differ, balance_zero;
+  uint64_t last_updated_ms; /* 0 = None */
+} pmx_sighting;
+int32_t pmx_set_endpoint(pmx_plugin*, const char* address, const char* ip_address, uint16_t port);
+int32_t pmx_sync_discovery(pmx_plugin*, uint64_t now_ms, const pmx_sighting* sightings, uint32_t n, uint32_t max_same_endpoint,
+                           char* out, size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,8 @@ struct pmx_plugin {
   bool changed_text_pending = false;
   std::string sweep_text;      // pmx_sweep_statuses: a sweep's text, held while sweep_text_pending (until a buffer took it)
   bool sweep_text_pending = false;
+  std::string discovery_text;  // pmx_sync_discovery: a sync's text, held while discovery_text_pending (until a buffer took it)
+  bool discovery_text_pending = false;
 };
 
 #endif

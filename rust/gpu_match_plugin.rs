@@ -270,6 +270,82 @@ pub const NS_N: u8 = 8;
 pub const LIVE_TTL_MS: u32 = 90000;
 pub const LIVE_GIVE_UP: u32 = 360;
 
+/// pm_disc_row (include/pm_engine.h): one row of the de-duplicated discovery list
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_disc_row {
+    pub row: u32,
+    pub endpoint: u32,
+    pub endpoint_after: u32,
+    pub flags: u32,
+    pub last_change_ms: u64,
+    pub last_updated_ms: u64,
+}
+
+/// pm_disc_result (include/pm_engine.h): what pm_discovery_sync made of a row
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_disc_result {
+    pub healthy_same_endpoint: u32,
+    pub old_status: u8,
+    pub final_status: u8,
+    pub n_updates: u8,
+    pub ops: u8,
+    pub upd_old: [u8; 3],
+    pub upd_new: [u8; 3],
+    pub _pad: u16,
+}
+
+/// PM_DISC_NEW, PM_EP_NONE, PM_DISC_GRACE_MS, PM_DF_*, PM_DO_*
+pub const DISC_NEW: u32 = 0xFFFF_FFFF;
+pub const EP_NONE: u32 = 0xFFFF_FFFF;
+pub const DISC_GRACE_MS: u32 = 300000;
+pub const DF_VALIDATED: u32 = 1;
+pub const DF_WHITELISTED: u32 = 2;
+pub const DF_ACTIVE: u32 = 4;
+pub const DF_LOCATION_NEW: u32 = 8;
+pub const DF_SPECS_DIFFER: u32 = 16;
+pub const DF_BALANCE_ZERO: u32 = 32;
+pub const DO_ADMIT: u32 = 1;
+pub const DO_SKIP: u32 = 2;
+pub const DO_IP_REWRITE: u32 = 4;
+pub const DO_LOCATION: u32 = 8;
+pub const DO_SPECS_REWRITE: u32 = 16;
+pub const DO_STAMP_NOW: u32 = 32;
+
+/// what sync_single_node_with_discovery reads of a DiscoveryNode (GpuMatchPlugin::sync_discovery)
+#[derive(Clone, Debug, Default)]
+pub struct DiscoverySighting {
+    pub address: Address,
+    pub ip_address: String,
+    pub port: u16,
+    pub is_validated: bool,
+    pub is_provider_whitelisted: bool,
+    pub is_active: bool,
+    pub location_new: bool,        // the store's location is None and discovery's is Some (monitor.rs:345)
+    pub specs_differ: bool,        // existing_node.compute_specs != discovery_node.compute_specs (:367)
+    pub balance_zero: bool,        // latest_balance == Some(0) (:385-386)
+    pub last_updated_ms: u64,      // discovery.last_updated, 0 = None
+}
+
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum DiscoveryKind { Admitted, Skipped, Synced }
+
+/// one per sighting, in order
+#[derive(Clone, Debug)]
+pub struct DiscoveryOutcome {
+    pub kind: DiscoveryKind,
+    pub address: String,
+    pub healthy_same_endpoint: u32,
+    pub old_status: NodeStatus,                     // (Synced)
+    pub final_status: NodeStatus,
+    pub updates: Vec<(NodeStatus, NodeStatus)>,     // (old, new) as the handlers saw them
+    pub ip_rewritten: bool,
+    pub location_new: bool,
+    pub specs_rewritten: bool,
+    pub stamped_now: bool,
+}
+
 fn node_status_code(s: &NodeStatus) -> u8 {
     match s {
         NodeStatus::Discovered => NS_DISCOVERED,
@@ -389,6 +465,9 @@ extern "C" {
     fn pm_liveness_sweep(e: *mut c_void, now_ms: u64, last_beat_ms: *const u64, in_pool_bits: *const u64, apply: u32,
                          n_transitions: *mut u32, census: *mut u32) -> i32;
     fn pm_liveness_transitions(e: *mut c_void, rows: *mut pm_live_row, cap: u32, n: *mut u32) -> i32;
+    fn pm_discovery_sync(e: *mut c_void, now_ms: u64, row_endpoint: *const u32, n_endpoints: u32, max_healthy_same_endpoint: u32,
+                         rows: *const pm_disc_row, n_rows: u32, apply: u32, out: *mut pm_disc_result,
+                         n_updates_total: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -509,6 +588,14 @@ struct NodeTable {
     beats: Vec<AtomicU64>,
     /// enable_liveness was called: handle_status_change also writes the engine's ledger
     liveness_on: bool,
+    /// discovery sync: the endpoint column by row (ip empty = unknown: EP_NONE), the interning map "ip:port" -> id, the
+    /// endpoints of addresses without a row yet; last_status_change per row in ms, 0 = None.  Both grow lazily to the rows.
+    ep_ip: Vec<String>,
+    ep_port: Vec<u16>,
+    ep_id: Vec<u32>,
+    ep_intern: HashMap<String, u32>,
+    ep_pending: HashMap<Address, (String, u16)>,
+    stamps: Vec<u64>,
 }
 
 pub struct GpuMatchPlugin {
@@ -1678,11 +1765,130 @@ impl GpuMatchPlugin {
             let mut flags = t.rows[r.worker as usize].flags & !W_HEALTHY;   // (what the engine's apply gave the row)
             if r.new_status == NS_HEALTHY { flags |= W_HEALTHY; }
             t.rows[r.worker as usize].flags = flags;
+            note_stamp(&mut t, r.worker, now_ms);
             any_dead = any_dead || r.new_status == NS_DEAD;
             out.push((t.address_strings[r.worker as usize].clone(), node_status_of(r.old_status), node_status_of(r.new_status)));
         }
         drop(t);
         if any_dead { self.emit_group_webhooks()?; }       // whole groups were dissolved (status_update_impl.rs:17-29)
+        Ok(out)
+    }
+
+    // ---- discovery sync (INTEGRATION.md "Discovery sync"): DiscoveryMonitor::get_nodes -> sync_single_node_with_discovery
+    // (discovery/monitor.rs:218-435) as pm_discovery_sync over the plugin's rows.  Needs enable_liveness.
+
+    /// the store's ip and port of a node (start-up, add_node by another writer); unknown addresses are remembered until
+    /// sync_nodes brings their row
+    pub fn set_endpoint(&self, address: &Address, ip_address: &str, port: u16) {
+        let mut t = self.nodes.write();
+        t.ep_pending.insert(address.clone(), (ip_address.to_string(), port));
+        fit_endpoints(&mut t);
+    }
+
+    pub fn endpoint_of(&self, address: &Address) -> Option<(String, u16)> {
+        let t = self.nodes.read();
+        let w = *t.index.get(address)? as usize;
+        if w >= t.ep_ip.len() || t.ep_ip[w].is_empty() { return None; }
+        Some((t.ep_ip[w].clone(), t.ep_port[w]))
+    }
+
+    pub fn last_status_change_ms(&self, address: &Address) -> u64 {
+        let t = self.nodes.read();
+        t.index.get(address).and_then(|&w| t.stamps.get(w as usize).copied()).unwrap_or(0)
+    }
+
+    /// one get_nodes pass, applied.  A sighting whose address has no present row is the reference's Ok(None): admitted or
+    /// skipped.  ADMITTED NODES ARE RETURNED, NOT APPENDED: the caller adds them to its store and the next sync_nodes brings
+    /// their rows (their endpoint is remembered from the sighting).  The store writes of location and specs are the caller's.
+    pub fn sync_discovery(&self, now_ms: u64, sightings: &[DiscoverySighting], max_same_endpoint: u32) -> Result<Vec<DiscoveryOutcome>> {
+        let mut guard = self.nodes.write();   // (LOCK ORDER: nodes, the engine; flags, stamps and endpoints are written below)
+        let t = &mut *guard;
+        let (w_rows, d_rows) = (t.rows.len(), sightings.len());
+        fit_endpoints(t);
+        let mut rows = vec![pm_disc_row::default(); d_rows];
+        let mut pass = 0;
+        loop {
+            for (j, s) in sightings.iter().enumerate() {
+                let r = &mut rows[j];
+                *r = pm_disc_row::default();
+                r.endpoint = intern_endpoint(t, &s.ip_address, s.port);
+                r.flags = (if s.is_validated { DF_VALIDATED } else { 0 }) | (if s.is_provider_whitelisted { DF_WHITELISTED } else { 0 })
+                    | (if s.is_active { DF_ACTIVE } else { 0 }) | (if s.balance_zero { DF_BALANCE_ZERO } else { 0 });
+                r.last_updated_ms = s.last_updated_ms;
+                let w = match t.index.get(&s.address) {   // get_node is Ok(None) (a tombstoned row left the store)
+                    Some(&w) if t.present[w as usize] => w,
+                    _ => { r.row = DISC_NEW; continue; }
+                };
+                r.row = w;
+                // "discovery ip : STORED port" (a row whose endpoint nobody told has no stored port: the sighting's)
+                let stored_port = if t.ep_ip[w as usize].is_empty() { s.port } else { t.ep_port[w as usize] };
+                r.endpoint_after = intern_endpoint(t, &s.ip_address, stored_port);
+                r.flags |= (if s.location_new { DF_LOCATION_NEW } else { 0 }) | (if s.specs_differ { DF_SPECS_DIFFER } else { 0 });
+                r.last_change_ms = t.stamps[w as usize];
+            }
+            if t.ep_intern.len() <= w_rows + 2 * d_rows || pass != 0 { break; }
+            // ids of endpoints nobody holds any more have piled up past what the engine accepts: intern the column afresh
+            pass += 1;
+            t.ep_intern.clear();
+            for w in 0..w_rows {
+                let (ip, port) = (t.ep_ip[w].clone(), t.ep_port[w]);
+                t.ep_id[w] = if ip.is_empty() { EP_NONE } else { intern_endpoint(t, &ip, port) };
+            }
+        }
+        // (a node that left the store is no "other node")
+        let column: Vec<u32> = (0..w_rows).map(|w| if t.present[w] { t.ep_id[w] } else { EP_NONE }).collect();
+        let mut res = vec![pm_disc_result::default(); d_rows.max(1)];
+        check(unsafe { pm_discovery_sync(self.engine, now_ms, if w_rows != 0 { column.as_ptr() } else { std::ptr::null() },
+                                         t.ep_intern.len() as u32, max_same_endpoint,
+                                         if d_rows != 0 { rows.as_ptr() } else { std::ptr::null() }, d_rows as u32, 1,
+                                         res.as_mut_ptr(), std::ptr::null_mut()) })?;
+        for j in 0..d_rows {
+            if rows[j].row != DISC_NEW && (res[j].old_status >= NS_N || res[j].final_status >= NS_N || res[j].n_updates > 3) {
+                return Err(anyhow!("sync_discovery: a result that is no node status"));
+            }
+        }
+        let mut out = Vec::with_capacity(d_rows);
+        let mut any_dead = false;
+        for (j, s) in sightings.iter().enumerate() {
+            let r = res[j];
+            let ops = r.ops as u32;
+            let mut o = DiscoveryOutcome {
+                kind: DiscoveryKind::Synced, address: s.address.to_string(), healthy_same_endpoint: r.healthy_same_endpoint,
+                old_status: NodeStatus::Discovered, final_status: NodeStatus::Discovered, updates: Vec::new(),
+                ip_rewritten: false, location_new: false, specs_rewritten: false, stamped_now: false,
+            };
+            if rows[j].row == DISC_NEW {
+                o.kind = if ops & DO_ADMIT != 0 { DiscoveryKind::Admitted } else { DiscoveryKind::Skipped };
+                if ops & DO_ADMIT != 0 { t.ep_pending.insert(s.address.clone(), (s.ip_address.clone(), s.port)); }
+                out.push(o);
+                continue;
+            }
+            let w = rows[j].row as usize;
+            o.old_status = node_status_of(r.old_status);
+            o.final_status = node_status_of(r.final_status);
+            for u in 0..r.n_updates as usize {
+                o.updates.push((node_status_of(r.upd_old[u]), node_status_of(r.upd_new[u])));
+                any_dead = any_dead || r.upd_new[u] == NS_DEAD || r.upd_new[u] == NS_LOWBALANCE;
+            }
+            o.ip_rewritten = ops & DO_IP_REWRITE != 0;
+            o.location_new = ops & DO_LOCATION != 0;
+            o.specs_rewritten = ops & DO_SPECS_REWRITE != 0;
+            o.stamped_now = ops & DO_STAMP_NOW != 0;
+            if o.ip_rewritten && !o.specs_rewritten {   // (the specs put-back restores the old ip)
+                if t.ep_ip[w].is_empty() { t.ep_port[w] = s.port; }
+                t.ep_ip[w] = s.ip_address.clone();
+                t.ep_id[w] = rows[j].endpoint_after;
+            }
+            if r.n_updates != 0 {   // (what the engine's apply gave the row)
+                let mut flags = t.rows[w].flags & !W_HEALTHY;
+                if r.final_status == NS_HEALTHY { flags |= W_HEALTHY; }
+                t.rows[w].flags = flags;
+            }
+            if o.stamped_now { t.stamps[w] = now_ms; }
+            out.push(o);
+        }
+        drop(guard);
+        if any_dead { self.emit_group_webhooks()?; }       // whole groups were dissolved (status_update_impl.rs:16-29)
         Ok(out)
     }
 
@@ -1696,9 +1902,40 @@ impl GpuMatchPlugin {
         let dead = matches!(node.status, NodeStatus::Dead | NodeStatus::LowBalance) as u32;
         check(unsafe { pm_on_worker_status(self.engine, w, flags, dead) })?;
         if t.liveness_on { self.liveness_note(w, &node.status)?; }   // (the ledger learns what the host has set)
+        note_stamp(&mut t, w, chrono::Utc::now().timestamp_millis() as u64);   // (update_node_status stamps: node_store.rs:284-305)
         drop(t);
         if dead != 0 { self.emit_group_webhooks()?; }      // the whole group was dissolved (status_update_impl.rs:17-29)
         Ok(())
+    }
+}
+
+/// last_status_change of a row (write lock): what sync_discovery hands the engine as the snapshot's stamp
+fn note_stamp(t: &mut NodeTable, row: u32, ms: u64) {
+    if t.stamps.len() <= row as usize { t.stamps.resize(t.rows.len().max(row as usize + 1), 0); }
+    t.stamps[row as usize] = ms;
+}
+
+fn intern_endpoint(t: &mut NodeTable, ip: &str, port: u16) -> u32 {
+    let next = t.ep_intern.len() as u32;
+    *t.ep_intern.entry(format!("{ip}:{port}")).or_insert(next)
+}
+
+/// the column covers every row; the endpoints remembered for addresses that have a row by now move into it
+fn fit_endpoints(t: &mut NodeTable) {
+    let w_rows = t.rows.len();
+    if t.ep_ip.len() < w_rows {
+        t.ep_ip.resize(w_rows, String::new());
+        t.ep_port.resize(w_rows, 0);
+        t.ep_id.resize(w_rows, EP_NONE);
+    }
+    if t.stamps.len() < w_rows { t.stamps.resize(w_rows, 0); }
+    let arrived: Vec<Address> = t.ep_pending.keys().filter(|a| t.index.contains_key(*a)).cloned().collect();
+    for a in arrived {
+        let (ip, port) = t.ep_pending.remove(&a).unwrap();
+        let w = t.index[&a] as usize;
+        t.ep_id[w] = intern_endpoint(t, &ip, port);
+        t.ep_ip[w] = ip;
+        t.ep_port[w] = port;
     }
 }
 

@@ -24,6 +24,8 @@
 #   fuzz[:<swarms>[:<seed>[:<kind>,<kind>]]]  tools/parity_fuzz.py (engine against oracle on random swarms; all kinds unless named)
 #   liveness[:<args>]        tools/liveness_probe.py [W] [--bench DIR]: pm_liveness_sweep at W rows (100000), reporting and applying
 #                            -> r18_liveness.txt (copy it to profiles/)
+#   discovery[:<args>]       tools/discovery_probe.py [W] [--bench DIR]: pm_discovery_sync at W rows (100000), three shapes, beside each
+#                            the sequential D x W loop on one host thread -> r19_discovery.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -142,6 +144,9 @@ PY
     liveness)
       timeout -k 10 300 python tools/liveness_probe.py $arg --out "$out/r18_liveness.txt" > "$out/${n}_liveness.log" 2>&1; echo "liveness rc=$?"
       tail -12 "$out/${n}_liveness.log" ;;
+    discovery)
+      timeout -k 10 300 python tools/discovery_probe.py $arg --out "$out/r19_discovery.txt" > "$out/${n}_discovery.log" 2>&1; echo "discovery rc=$?"
+      tail -12 "$out/${n}_discovery.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
