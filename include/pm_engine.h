@@ -48,7 +48,9 @@ extern "C" {
                             + pm_enable_assignment_changes / pm_drain_assignment_changes (assignment change feed),
                             + pm_probe_configs / pm_config_overlap (probes and configuration overlap),
                             + pm_liveness_enable / _set / _get / _sweep / _transitions (liveness sweep),
-                            + pm_discovery_sync (discovery sync): compatible additions, the version stays 3 */
+                            + pm_discovery_sync (discovery sync),
+                            + pm_metrics_enable / _ingest / _totals / _rows (metrics ledger): compatible additions, the version
+                            stays 3 */
 
 enum {
   PM_OK = 0,
@@ -747,6 +749,90 @@ typedef struct pm_disc_result { /* 16 bytes, one per input row, in input order *
 int32_t pm_discovery_sync(pm_engine*, uint64_t now_ms, const uint32_t* row_endpoint /* W */, uint32_t n_endpoints,
                           uint32_t max_healthy_same_endpoint, const pm_disc_row* rows, uint32_t n_rows, uint32_t apply,
                           pm_disc_result* out /* n_rows, may be NULL */, uint32_t* n_updates_total /* may be NULL */);
+
+/* ---- metrics ledger (kernels in pm_metrics.inc) -----------------------------------------------------------------------------
+ * The store the heartbeat route writes for every node on every beat (orchestrator/src/store/domains/metrics_store.rs,
+ * api/routes/heartbeat.rs:94-151) and the reads over it: the per-series aggregates (get_aggregate_metrics_for_all_tasks /
+ * _for_task), the listings (get_all_metrics, get_metrics_for_node) and the sync service's join of every entry with its node's
+ * group id and configuration (metrics/sync_service.rs:127-200).  Off by default; with it off nothing of the engine changes.
+ *
+ * THE LEDGER: a device-resident sparse table, one row per worker row plus the MANUAL ROW (PM_MX_MANUAL: Address::ZERO of
+ * store_manual_metrics; it belongs to no group), each a set of (series, value) entries with every series at most once.  A
+ * SERIES is a dense u32 the host interns from the reference's hash field "{task_id or "manual"}:{label without ':'}"; the engine
+ * sees no strings.  Values are doubles and are kept bit for bit.  Whether an entry follows the keep-the-maximum rule is a flag
+ * of the INCOMING entry (the reference tests the original label for "dashboard-progress", metrics_store.rs:52), never stored.
+ * Layout: worker-major CSR (the manual row in front), rows sorted by series, two buffers: an ingest writes the new table
+ * from the old one (fold the touched rows and count, scan, fold and write, copy the other rows) and a refused batch never
+ * swaps.  pm_metrics_enable(on = 1) creates an empty ledger (again: empties it), on = 0 releases everything.  Appended workers
+ * start empty; pm_upload_workers(keep_groups = 0) empties every worker row and keeps the manual row.
+ *
+ * pm_metrics_ingest applies n_beats beats in batch order.  A beat names a row (a worker index or PM_MX_MANUAL), a kind and the
+ * entries [first, first + n) of `entries`; `old` = the row's value of the entry's series, if it holds one:
+ *   PM_MXB_REPLACE  the heartbeat (heartbeat.rs:94-151): first every series of the row that does not occur in this beat is
+ *                   dropped, then the entries are folded in order: without PM_MXF_MAX the value is set; with it, it is set iff
+ *                   the series is absent or value > old (an IEEE comparison: a stored NaN stays, a NaN is stored only into an
+ *                   absent series, 0.0 does not replace -0.0).  n = 0 is Some(vec![]): it empties the row; it is also what the
+ *                   host sends where the reference deletes a node's metrics (Ejected, Banned: status_update/mod.rs:314-343).
+ *   PM_MXB_MERGE    store_metrics alone (the manual route, restores): the same fold, nothing dropped.
+ *   PM_MXB_DELETE   delete_metric: the listed series are removed; values and flags are ignored; an absent series is no error.
+ * A row may occur in any number of beats and a series any number of times in a beat: the result is that of applying the beats
+ * one after another, entry by entry, whatever wave a row is dealt to (a row's beats are folded in order by ONE wave; rows run
+ * in parallel).  n_series bounds every series of the call; the ledger remembers the largest it was told.
+ * A row holds at most PM_MX_ROW_MAX series AT ANY MOMENT of the fold: a batch in which an entry would make a row longer is
+ * refused whole (PM_ERANGE), the ledger as it was.
+ *
+ * pm_metrics_totals: sum[s] = the sum of the values of series s over all rows, count[s] = the rows that hold it, for
+ * s < *n_series (the largest n_series an ingest stated; cap < *n_series or a NULL array: PM_ERANGE, nothing copied, *n_series
+ * set).  The device half of both get_aggregate_* functions (the host rolls series up to label names).  DETERMINISTIC: the sum
+ * of a series starts at +0.0 (or_insert(0.0), metrics_store.rs:196) and adds its values one by one in ascending row order,
+ * the manual row first — a stable radix regroup of the entries by series (integer histograms over fixed 1024-entry chunks),
+ * then one ordered sum per series; no floating-point atomics, nothing depends on the number of workgroups or on earlier
+ * calls.  (The reference's order is that of SCAN and a HashMap: unpinned.)  The result is cached until the ledger changes.
+ *
+ * pm_metrics_rows is the listing, joined on the device with what pm_get_groups would report at this moment: group_id / config
+ * of the row's worker, PM_NONE (as u64: 0xFFFFFFFF) / 0 for a worker in no group and for the manual row.  rows == NULL: every
+ * entry, the manual row's first, then ascending (worker, series) (get_all_metrics, the sync service); else the entries of
+ * the n named rows in the order named, ascending series inside a row (get_metrics_for_node).  The convention of
+ * pm_liveness_transitions: *n_out always, cap < *n_out or out == NULL is PM_ERANGE with nothing copied.
+ *
+ * THE LIVENESS HOOK: with both ledgers on, pm_liveness_sweep empties the metrics row of every listed worker whose new status
+ * is Dead (status_update/mod.rs:314-343), on the device, from its transition list, before it returns.  With metrics off the
+ * sweep is what it was.
+ *
+ * ERRORS.  PM_ESTATE: the ledger is off; a stepwise tick is in progress; dist_world > 1 (and pm_dist_configure(world > 1)
+ * while it is on); no workers uploaded and a beat or a named row is not the manual row.  PM_EINVAL: a null argument; an
+ * unknown kind or flag; first + n > n_entries.  PM_ERANGE: a row >= W other than PM_MX_MANUAL; a series >= n_series; the
+ * row bound.  Everything is checked on the host first, the row bound on the device before anything is written: a refused
+ * call leaves the ledger as it was.  No metrics call consumes a pending delta, compacts groups or clears a cache flag. */
+#define PM_MX_MANUAL 0xFFFFFFFFu /* the manual row (Address::ZERO) */
+#define PM_MX_ROW_MAX 1024u      /* series a row can hold */
+enum { PM_MXB_REPLACE = 0, PM_MXB_MERGE = 1, PM_MXB_DELETE = 2 };
+enum { PM_MXF_MAX = 1 };
+typedef struct pm_mx_beat {
+  uint32_t row;   /* worker index or PM_MX_MANUAL */
+  uint32_t kind;  /* PM_MXB_* */
+  uint32_t first; /* entries [first, first + n) */
+  uint32_t n;
+} pm_mx_beat;
+typedef struct pm_mx_entry { /* 16 bytes */
+  uint32_t series;
+  uint32_t flags; /* PM_MXF_* */
+  double value;
+} pm_mx_entry;
+typedef struct pm_mx_row { /* 32 bytes */
+  uint32_t row;    /* worker index or PM_MX_MANUAL */
+  uint32_t series;
+  double value;
+  uint64_t group_id; /* PM_NONE: in no group */
+  uint32_t config;
+  uint32_t _pad;
+} pm_mx_row;
+int32_t pm_metrics_enable(pm_engine*, uint32_t on);
+int32_t pm_metrics_ingest(pm_engine*, const pm_mx_beat* beats, uint32_t n_beats, const pm_mx_entry* entries, uint32_t n_entries,
+                          uint32_t n_series);
+int32_t pm_metrics_totals(pm_engine*, double* sum, uint32_t* count, uint32_t cap, uint32_t* n_series);
+int32_t pm_metrics_rows(pm_engine*, const uint32_t* rows /* NULL = all */, uint32_t n, pm_mx_row* out, uint32_t cap,
+                        uint32_t* n_out);
 
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).

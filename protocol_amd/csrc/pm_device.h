@@ -220,6 +220,38 @@ struct DiscArgs {
   pm_disc_result* out;         // [D]
 };
 
+// metrics ledger (pm_metrics.inc).  Internal row 0 is the manual row, internal row w + 1 is worker w; R = rows of the table.
+static constexpr uint32_t PM_MX_TOUCHED = 0x80000000u;  // a row's new length word: the fold wrote it (the copy skips the row)
+static constexpr uint32_t PM_MX_CHUNK = 1024;           // entries of one radix chunk: fixed, so the regroup does not depend on the grid
+struct MxFoldArgs {
+  uint32_t n_touched;
+  const uint32_t* t_row;     // [n_touched] internal row, no two equal
+  const uint32_t* t_first;   // [n_touched] first of the row's beats in `beats`
+  const uint32_t* t_nb;      // [n_touched] its beats (contiguous, in batch order)
+  const pm_mx_beat* beats;   // the batch's beats, stably sorted by row
+  const pm_mx_entry* entries;
+  const uint32_t* off_old;   // [R + 1]
+  const uint32_t* ser_old;
+  const double* val_old;
+  uint32_t* new_n;           // [R] count pass: length | PM_MX_TOUCHED of every touched row
+  uint32_t* over;            // [1] count pass: != 0 = a row would pass PM_MX_ROW_MAX
+  const uint32_t* off_new;   // [R + 1] write pass
+  uint32_t* ser_new;
+  double* val_new;
+};
+struct MxRowsArgs {
+  uint32_t n, total;           // listed rows; entries to write
+  const uint32_t* rows;        // [n] internal rows, or nullptr: row k is internal row k
+  const uint32_t* out_off;     // [n + 1] first output entry of listed row k
+  const uint32_t* off;         // [R + 1] the ledger
+  const uint32_t* ser;
+  const double* val;
+  const int32_t* group_of;     // [W] host truth, -1 = in no group
+  const uint64_t* g_id;        // per group slot
+  const uint32_t* g_cfg;
+  pm_mx_row* out;
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -465,6 +497,23 @@ void launch_liveness_get(const uint32_t* idx, uint32_t n, const uint8_t* status,
                          hipStream_t s);
 // discovery sync (pm_discovery.inc): mark, base, segments + scatter, query and decide, in this order on s
 void launch_discovery_sync(const DiscArgs& a, hipStream_t s);
+// metrics ledger (pm_metrics.inc)
+void launch_mx_fill(uint32_t* p, uint32_t first, uint32_t end, uint32_t v, hipStream_t s);
+void launch_mx_lengths(const uint32_t* off, uint32_t R, uint32_t* new_n, hipStream_t s);
+void launch_mx_fold(const MxFoldArgs& a, bool write, hipStream_t s);
+// out[i] = sum of (in[j] & ~PM_MX_TOUCHED) over j < i, out[n] = the total (also to *total_host where given: pinned)
+void launch_mx_scan(const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* total_host, hipStream_t s);
+void launch_mx_copy(const uint32_t* off_old, const uint32_t* new_n, const uint32_t* off_new, uint32_t R, uint32_t N_old,
+                    const uint32_t* ser_old, const double* val_old, uint32_t* ser_new, double* val_new, hipStream_t s);
+void launch_mx_mark_dead(const pm_live_row* list, uint32_t n, uint32_t R, const uint32_t* off, uint32_t* new_n, uint32_t* hit_host,
+                         hipStream_t s);
+void launch_mx_row_lengths(const uint32_t* rows, uint32_t n, const uint32_t* off, uint32_t* len, hipStream_t s);
+void launch_mx_rows(const MxRowsArgs& a, hipStream_t s);
+// one radix pass over digit (series >> shift) & 255: hist [256][chunks] (digit-major), scanned in place into `hist_scan`
+void launch_mx_radix_pass(const uint32_t* ser_in, const double* val_in, uint32_t N, uint32_t shift, uint32_t* hist,
+                          uint32_t* hist_scan, uint32_t* ser_out, double* val_out, hipStream_t s);
+void launch_mx_sums(const uint32_t* ser_sorted, const double* val_sorted, uint32_t N, uint32_t n_series, double* sum,
+                    uint32_t* count, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -66,6 +66,7 @@ namespace pm {
 #include "pm_engine_carve.inc"
 #include "pm_engine_changes.inc"
 #include "pm_engine_discovery.inc"
+#include "pm_engine_metrics.inc"
 #include "pm_engine_liveness.inc"
 #include "pm_engine_match.inc"
 #include "pm_engine_merge.inc"
@@ -225,6 +226,7 @@ void pm_engine_destroy(pm_engine* e) {
   e->d_probe_in.release(); e->d_probe_out.release();
   changes_release(e);
   liveness_release(e);
+  metrics_release(e);
   delete e->form;
   delete e;
 }
@@ -299,6 +301,9 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #define PM_DISCOVERY_ABI
 #include "pm_engine_discovery.inc"
 #undef PM_DISCOVERY_ABI
+#define PM_METRICS_ABI
+#include "pm_engine_metrics.inc"
+#undef PM_METRICS_ABI
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

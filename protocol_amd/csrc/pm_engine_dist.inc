@@ -43,6 +43,7 @@ int32_t pm_dist_configure(pm_engine* e, uint32_t rank, uint32_t world, const uin
   if (e->dist_phase != 0) return set_error(PM_ESTATE, "a stepwise tick is in progress");
   if (world > 1 && e->chg_on) return set_error(PM_ESTATE, "the assignment change feed is on: it does not cover multi-GPU engines");
   if (world > 1 && e->live_on) return set_error(PM_ESTATE, "liveness is on: it does not cover multi-GPU engines");
+  if (world > 1 && e->mx_on) return set_error(PM_ESTATE, "the metrics ledger is on: it does not cover multi-GPU engines");
   if (world > 1 && !e->have_workers) return set_error(PM_ESTATE, "workers must be uploaded first");
   if (world > 1 && e->W && !shard_of_worker) return set_error(PM_EINVAL, "null shard column");
   e->dist_rank = world > 1 ? rank : 0;

@@ -173,6 +173,8 @@ int32_t pm_liveness_sweep(pm_engine* e, uint64_t now_ms, const uint64_t* last_be
     HIPCHK(hipStreamSynchronize(e->stream));
     if (e->h_live_count[0] > W) return set_error(PM_ESTATE, "liveness: more listed rows than rows");
     e->live_n = e->h_live_count[0];
+    // (metrics on: the rows that became Dead lose their metrics, status_update/mod.rs:314-343 — on the device, from the list)
+    if (e->mx_on && e->live_n && (rc = metrics_clear_dead(e))) return rc;
   }
   if (n_transitions) *n_transitions = e->live_n;
   if (census) std::copy(e->h_live_count + 1, e->h_live_count + 1 + PM_NS_N, census);

@@ -269,4 +269,30 @@ struct pm_engine {
   std::vector<pm_disc_result> h_disc_out;
   std::vector<uint32_t> h_disc_seen;  // [W] the call (disc_epoch) that last listed the row: a row listed twice
   uint32_t disc_epoch = 0;
+
+  // ---- metrics ledger (pm_engine_metrics.inc): a CSR over the internal rows [0, mx_R) — 0 the manual row, w + 1 worker w —
+  // in two buffers (mx_cur is the table, the other one the next ingest's target); mx_N its entries.  Rows behind mx_R hold
+  // nothing yet: the next metrics call extends the offsets.
+  bool mx_on = false;
+  bool mx_reinit = false;        // an upload dropped the row identities: every worker row is emptied by the next metrics call
+  bool mx_totals_valid = false;  // h_mx_sum / h_mx_cnt are the totals of the table as it stands
+  uint32_t mx_cur = 0, mx_R = 0, mx_N = 0, mx_n_series = 0;
+  DevBuf<uint32_t> d_mx_off[2], d_mx_ser[2];
+  DevBuf<double> d_mx_val[2];
+  DevBuf<uint32_t> d_mx_new_n;     // [R] a rebuild's row lengths (| PM_MX_TOUCHED)
+  DevBuf<uint32_t> d_mx_stage;     // an ingest's touched rows (3 columns); a listing's rows, lengths and offsets
+  DevBuf<pm_mx_beat> d_mx_beats;
+  DevBuf<pm_mx_entry> d_mx_entries;
+  DevBuf<uint32_t> d_mx_flag;      // [1] the count pass's "a row would pass the bound"
+  DevBuf<uint32_t> d_mx_sort_ser[2], d_mx_hist, d_mx_hist_scan, d_mx_cnt, d_mx_gcfg;
+  DevBuf<double> d_mx_sort_val[2], d_mx_sum;
+  DevBuf<int32_t> d_mx_gof;        // the join's inputs: the host's group_of, the groups' ids and configurations by slot
+  DevBuf<uint64_t> d_mx_gid;
+  DevBuf<pm_mx_row> d_mx_out;
+  uint32_t* h_mx_pin = nullptr;    // pinned: [0] a scan's total, [1] the bound flag, [2] the liveness hook's "a row was emptied"
+  std::vector<double> h_mx_sum;
+  std::vector<uint32_t> h_mx_cnt, h_mx_stage;
+  std::vector<pm_mx_beat> h_mx_beats;
+  std::vector<uint64_t> h_mx_gid;
+  std::vector<uint32_t> h_mx_gcfg;
 };

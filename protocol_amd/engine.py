@@ -79,6 +79,14 @@ assert disc_row_dt.itemsize == 32 and disc_result_dt.itemsize == 16
 DISC_NEW, EP_NONE, DISC_GRACE_MS = 0xFFFFFFFF, 0xFFFFFFFF, 300000
 DF_VALIDATED, DF_WHITELISTED, DF_ACTIVE, DF_LOCATION_NEW, DF_SPECS_DIFFER, DF_BALANCE_ZERO = 1, 2, 4, 8, 16, 32
 DO_ADMIT, DO_SKIP, DO_IP_REWRITE, DO_LOCATION, DO_SPECS_REWRITE, DO_STAMP_NOW = 1, 2, 4, 8, 16, 32
+# pm_mx_beat, pm_mx_entry, pm_mx_row, PM_MX* (include/pm_engine.h): metrics ledger
+mx_beat_dt = np.dtype([("row", "<u4"), ("kind", "<u4"), ("first", "<u4"), ("n", "<u4")])
+mx_entry_dt = np.dtype([("series", "<u4"), ("flags", "<u4"), ("value", "<f8")])
+mx_row_dt = np.dtype([("row", "<u4"), ("series", "<u4"), ("value", "<f8"), ("group_id", "<u8"), ("config", "<u4"), ("_pad", "<u4")])
+assert mx_beat_dt.itemsize == 16 and mx_entry_dt.itemsize == 16 and mx_row_dt.itemsize == 32
+MX_MANUAL, MX_ROW_MAX = 0xFFFFFFFF, 1024
+MXB_REPLACE, MXB_MERGE, MXB_DELETE = 0, 1, 2
+MXF_MAX = 1
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
                           ("next_worker", "<u4"), ("group_id", "<u8")], align=True)
 assert config_row_dt.itemsize == 32 and alt_row_dt.itemsize == 32 and assignment_dt.itemsize == 32
@@ -151,6 +159,7 @@ EXPORTS = [
     "pm_enable_assignment_changes", "pm_drain_assignment_changes",
     "pm_liveness_enable", "pm_liveness_set", "pm_liveness_get", "pm_liveness_sweep", "pm_liveness_transitions",
     "pm_discovery_sync",
+    "pm_metrics_enable", "pm_metrics_ingest", "pm_metrics_totals", "pm_metrics_rows",
 ]
 
 _lib = None
@@ -233,6 +242,10 @@ def lib() -> C.CDLL:
         L.pm_liveness_sweep.argtypes = [vp, u64, vp, vp, u32, C.POINTER(u32), vp]
         L.pm_liveness_transitions.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_discovery_sync.argtypes = [vp, u64, vp, u32, u32, vp, u32, u32, vp, C.POINTER(u32)]
+        L.pm_metrics_enable.argtypes = [vp, u32]
+        L.pm_metrics_ingest.argtypes = [vp, vp, u32, vp, u32, u32]
+        L.pm_metrics_totals.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
+        L.pm_metrics_rows.argtypes = [vp, vp, u32, vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -670,6 +683,43 @@ class Engine:
                                       int(n_endpoints), int(max_healthy_same_endpoint), r.ctypes.data if n else None, n,
                                       int(apply), out.ctypes.data if n else None, C.byref(total)))
         return out, total.value
+
+    # ---- metrics ledger
+    def metrics_enable(self, on: bool = True):
+        """pm_metrics_enable: on = an empty ledger (again: empties it); off releases it"""
+        check(lib().pm_metrics_enable(self._h, int(on)))
+
+    def metrics_ingest(self, beats, entries, n_series: int):
+        """pm_metrics_ingest: beats (mx_beat_dt) applied in order over entries (mx_entry_dt); every series < n_series"""
+        b = np.ascontiguousarray(beats, dtype=mx_beat_dt)
+        en = np.ascontiguousarray(entries, dtype=mx_entry_dt)
+        check(lib().pm_metrics_ingest(self._h, b.ctypes.data if len(b) else None, len(b), en.ctypes.data if len(en) else None,
+                                      len(en), int(n_series)))
+
+    def metrics_totals(self):
+        """pm_metrics_totals -> (sum float64 [n_series], count uint32 [n_series]): per series over all rows, ascending row"""
+        n = C.c_uint32(0)
+        rc = lib().pm_metrics_totals(self._h, None, None, 0, C.byref(n))
+        if rc != -5:                                           # (PM_ERANGE is the size query's answer)
+            check(rc)
+        s, c = np.zeros(max(n.value, 1), dtype=np.float64), np.zeros(max(n.value, 1), dtype=np.uint32)
+        check(lib().pm_metrics_totals(self._h, s.ctypes.data, c.ctypes.data, len(s), C.byref(n)))
+        return s[:n.value], c[:n.value]
+
+    def metrics_rows(self, rows=None) -> np.ndarray:
+        """pm_metrics_rows -> mx_row_dt [n]: every entry (rows=None: the manual row's, then ascending (worker, series)) or the
+        entries of the named rows in the order named, each with its worker's group id and configuration"""
+        r = _arr(rows, np.uint32) if rows is not None else None
+        if r is not None and not len(r):
+            return np.zeros(0, dtype=mx_row_dt)
+        rp, rn = (r.ctypes.data, len(r)) if r is not None else (None, 0)
+        n = C.c_uint32(0)
+        rc = lib().pm_metrics_rows(self._h, rp, rn, None, 0, C.byref(n))
+        if rc != -5:
+            check(rc)
+        out = np.zeros(max(n.value, 1), dtype=mx_row_dt)
+        check(lib().pm_metrics_rows(self._h, rp, rn, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
 
     # ---- phases
     def compat_masks(self) -> np.ndarray:

@@ -436,6 +436,38 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::optional<std::pair<std::string, uint16_t>> endpoint_of(const Address& address) const;  // (what the tests look at)
   uint64_t last_status_change_ms(const Address& address) const;                               // 0 = None
 
+  // ---- metrics (INTEGRATION.md "Metrics"; gpu_match_metrics.cpp): MetricsStore (store/domains/metrics_store.rs), the heartbeat
+  // route's metric block (api/routes/heartbeat.rs:94-151) and the sync service's list (metrics/sync_service.rs:127-200) over the
+  // engine's metrics ledger.  The plugin interns the reference's hash field "{task_id or "manual"}:{label without ':'}" to a
+  // series, takes the keep-the-maximum flag from the ORIGINAL label ("dashboard-progress", metrics_store.rs:52), queues the
+  // writes and sends them in one pm_metrics_ingest per flush; every read flushes first.  Address::ZERO is the manual row; an
+  // address the node table does not hold is ignored (the route answers such a node before it gets here).
+  struct MetricEntry {  // shared::models::metric::MetricEntry
+    std::string task_id, label;
+    double value = 0.0;
+  };
+  struct SyncedMetric {  // one record_compute_task_gauge call of sync_metrics_from_redis
+    std::string address, task_id, task_name, label;
+    double value = 0.0;
+    std::optional<std::string> group_id, group_config_name;
+  };
+  using MetricsByName = std::map<std::string, double>;
+  using MetricsByTask = std::map<std::string, MetricsByName>;
+  void enable_metrics();  // pm_metrics_enable(on = 1): an empty ledger; the queue and the interner start over
+  void beat_metrics(const Address& address, const std::vector<MetricEntry>& entries);   // heartbeat.rs:94-151 (Some(metrics))
+  void store_metrics(const Address& address, const std::vector<MetricEntry>& entries);  // metrics_store.rs:25-75
+  void store_manual_metric(const std::string& label, double value);                     // :77-89
+  void delete_metric(const std::string& task_id, const std::string& label, const Address& address);  // :91-109
+  void clear_metrics(const Address& address);  // the clean-up of an Ejected / Banned node (status_update/mod.rs:314-343)
+  void flush_metrics();
+  MetricsByName aggregate_metrics_for_all_tasks();                          // :176-202, rolled up in ascending series order
+  MetricsByName aggregate_metrics_for_task(const std::string& task_id);     // :143-174
+  MetricsByTask metrics_for_node(const Address& address);                   // :111-131
+  std::map<std::string, std::map<std::string, MetricsByName>> all_metrics();  // :204-240: task -> name -> address -> value
+  // sync_service.rs:127-200: every entry with its task's name ("unknown" where the map has none) and its node's group
+  std::vector<SyncedMetric> synced_metrics(const std::map<std::string, std::string>& task_names);
+  size_t queued_metric_beats() const;  // (what the tests look at)
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -532,6 +564,19 @@ class GpuMatchPlugin : public SchedulerPlugin {
   void note_stamp_locked(uint32_t row, uint64_t ms);
   uint32_t intern_endpoint_locked(const std::string& ip, uint16_t port);
   void fit_endpoints_locked();
+  // metrics (gpu_match_metrics.cpp): the queue and the interner under metrics_mu_ (LOCK ORDER: nodes, metrics, the engine)
+  struct MetricsQueue {
+    std::vector<pm_mx_beat> beats;
+    std::vector<pm_mx_entry> entries;
+    std::unordered_map<std::string, uint32_t> series;                 // field -> series
+    std::vector<std::pair<std::string, std::string>> keys;            // series -> (task id or "manual", cleaned label)
+  };
+  mutable std::mutex metrics_mu_;
+  MetricsQueue metrics_;
+  uint32_t metric_series_locked(const std::string& task_id, const std::string& label);
+  void queue_metrics(const Address& address, uint32_t kind, const std::vector<MetricEntry>& entries);
+  void flush_metrics_locked();
+  std::vector<pm_mx_row> metric_rows_locked(const uint32_t* rows, uint32_t n);
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

@@ -167,6 +167,27 @@ int32_t pmx_beat(pmx_plugin*, const char* address, uint64_t now_ms);
 int32_t pmx_sweep_statuses(pmx_plugin*, uint64_t now_ms, const char* const* out_of_pool, uint32_t n_out_of_pool, char* out,
                            size_t cap, size_t* needed);
 
+/* ---- metrics (pm_plugin_metrics_c.cpp): GpuMatchPlugin::enable_metrics / beat_metrics / store_metrics / store_manual_metric /
+ * delete_metric / clear_metrics / flush_metrics and the reads.  A beat's entries come as three parallel arrays (task id, label,
+ * value); address "0x000...0" is the manual row.  The writes queue; pmx_flush_metrics and every read send the queue in one ingest.
+ * The texts, values as C's "%a" (every bit): pmx_aggregate_metrics (task_id NULL = all tasks) "<label>\t<sum>" per label in label
+ * order; pmx_metrics_for_node "<task id>\t<label>\t<value>"; pmx_synced_metrics "<address>\t<task id>\t<task name>\t<label>\t
+ * <value>\t<group id or ->\t<configuration name or ->" per entry, the manual row's first, then ascending (row, series), the task
+ * names from the two parallel arrays ("unknown" where they have none). */
+int32_t pmx_enable_metrics(pmx_plugin*);
+int32_t pmx_beat_metrics(pmx_plugin*, const char* address, const char* const* task_ids, const char* const* labels,
+                         const double* values, uint32_t n);
+int32_t pmx_store_metrics(pmx_plugin*, const char* address, const char* const* task_ids, const char* const* labels,
+                          const double* values, uint32_t n);
+int32_t pmx_store_manual_metric(pmx_plugin*, const char* label, double value);
+int32_t pmx_delete_metric(pmx_plugin*, const char* task_id, const char* label, const char* address);
+int32_t pmx_clear_metrics(pmx_plugin*, const char* address);
+int32_t pmx_flush_metrics(pmx_plugin*);
+int32_t pmx_aggregate_metrics(pmx_plugin*, const char* task_id, char* out, size_t cap, size_t* needed);
+int32_t pmx_metrics_for_node(pmx_plugin*, const char* address, char* out, size_t cap, size_t* needed);
+int32_t pmx_synced_metrics(pmx_plugin*, const char* const* task_ids, const char* const* task_names, uint32_t n_tasks, char* out,
+                           size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

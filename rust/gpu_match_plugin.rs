@@ -257,6 +257,43 @@ pub struct pm_live_row {
     pub counter: u32,
 }
 
+/// pm_mx_beat / pm_mx_entry / pm_mx_row (include/pm_engine.h): the metrics ledger's batch and its listing
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_mx_beat {
+    pub row: u32,
+    pub kind: u32,
+    pub first: u32,
+    pub n: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_mx_entry {
+    pub series: u32,
+    pub flags: u32,
+    pub value: f64,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_mx_row {
+    pub row: u32,
+    pub series: u32,
+    pub value: f64,
+    pub group_id: u64,
+    pub config: u32,
+    pub _pad: u32,
+}
+
+/// PM_MX_MANUAL, PM_MX_ROW_MAX, PM_MXB_*, PM_MXF_MAX
+pub const MX_MANUAL: u32 = 0xFFFF_FFFF;
+pub const MX_ROW_MAX: u32 = 1024;
+pub const MXB_REPLACE: u32 = 0;
+pub const MXB_MERGE: u32 = 1;
+pub const MXB_DELETE: u32 = 2;
+pub const MXF_MAX: u32 = 1;
+
 /// PM_NS_* (NodeStatus, models/node.rs:75-85, in its order), PM_LIVE_TTL_MS, PM_LIVE_GIVE_UP
 pub const NS_DISCOVERED: u8 = 0;
 pub const NS_WAITING: u8 = 1;
@@ -468,6 +505,11 @@ extern "C" {
     fn pm_discovery_sync(e: *mut c_void, now_ms: u64, row_endpoint: *const u32, n_endpoints: u32, max_healthy_same_endpoint: u32,
                          rows: *const pm_disc_row, n_rows: u32, apply: u32, out: *mut pm_disc_result,
                          n_updates_total: *mut u32) -> i32;
+    fn pm_metrics_enable(e: *mut c_void, on: u32) -> i32;
+    fn pm_metrics_ingest(e: *mut c_void, beats: *const pm_mx_beat, n_beats: u32, entries: *const pm_mx_entry, n_entries: u32,
+                         n_series: u32) -> i32;
+    fn pm_metrics_totals(e: *mut c_void, sum: *mut f64, count: *mut u32, cap: u32, n_series: *mut u32) -> i32;
+    fn pm_metrics_rows(e: *mut c_void, rows: *const u32, n: u32, out: *mut pm_mx_row, cap: u32, n_out: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -598,6 +640,27 @@ struct NodeTable {
     stamps: Vec<u64>,
 }
 
+/// the metrics writes queued since the last flush, and the interner: field "{task_id or "manual"}:{label without ':'}" -> series
+#[derive(Default)]
+struct MetricsQueue {
+    beats: Vec<pm_mx_beat>,
+    entries: Vec<pm_mx_entry>,
+    series: HashMap<String, u32>,
+    keys: Vec<(String, String)>,   // series -> (task id or "manual", cleaned label)
+}
+
+/// one record_compute_task_gauge call of sync_metrics_from_redis (gpu_match_metrics.cpp's SyncedMetric)
+#[derive(Default, Debug, Clone)]
+pub struct SyncedMetric {
+    pub address: String,
+    pub task_id: String,
+    pub task_name: String,
+    pub label: String,
+    pub value: f64,
+    pub group_id: Option<String>,
+    pub group_config_name: Option<String>,
+}
+
 pub struct GpuMatchPlugin {
     engine: *mut c_void,
     templates: Vec<NodeGroupConfiguration>,     // caller order: the engine's configuration index
@@ -612,6 +675,8 @@ pub struct GpuMatchPlugin {
     req_models: Vec<CString>,       // requirement model strings, one per pm_gpu_alt_row.model_row
     nodes: parking_lot::RwLock<NodeTable>,
     tasks: parking_lot::RwLock<Vec<Task>>,   // get_all_tasks order: the engine reports positions in this Vec
+    /// the metrics ledger's queue and interner (LOCK ORDER: nodes, metrics, the engine)
+    metrics: parking_lot::Mutex<MetricsQueue>,
     /// `upload:<node>:<group>:*` key count (scheduler_impl.rs:130-153): stays with the Redis store
     upload_counter: Box<dyn Fn(&Address, &str) -> usize + Send + Sync>,
     /// as in NodeGroupsPlugin (mod.rs:107, 124): the plugins told about every group created / destroyed
@@ -780,6 +845,7 @@ impl GpuMatchPlugin {
                               dist_rank: AtomicU32::new(0),
                               config_names: templates.iter().map(|t| t.name.clone()).collect(),
                               req_models: Vec::new(), nodes: Default::default(), tasks: Default::default(),
+                              metrics: Default::default(),
                               upload_counter, webhook_plugins, republish_on_insert: false,
                               nodes_synced: AtomicBool::new(false), tasks_synced: AtomicBool::new(false),
                               ticked: AtomicBool::new(false), multi_gpu: false };
@@ -1889,6 +1955,212 @@ impl GpuMatchPlugin {
         }
         drop(guard);
         if any_dead { self.emit_group_webhooks()?; }       // whole groups were dissolved (status_update_impl.rs:16-29)
+        Ok(out)
+    }
+
+    // ---- metrics (INTEGRATION.md "Metrics"): MetricsStore (store/domains/metrics_store.rs), the heartbeat route's metric block
+    // (api/routes/heartbeat.rs:94-151) and the sync service's list (metrics/sync_service.rs:127-200) over the engine's metrics
+    // ledger.  The writes queue; flush_metrics sends the queue in one pm_metrics_ingest, every read flushes first.  Address::ZERO
+    // is the manual row; an address the node table does not hold is ignored.
+
+    /// pm_metrics_enable(on = 1): an empty ledger; the queue and the interner start over
+    pub fn enable_metrics(&self) -> Result<()> {
+        let _t = self.nodes.read();           // (LOCK ORDER: nodes, metrics, the engine)
+        let mut q = self.metrics.lock();
+        check(unsafe { pm_metrics_enable(self.engine, 1) })?;
+        *q = MetricsQueue::default();
+        Ok(())
+    }
+
+    fn metric_row(t: &NodeTable, address: &Address) -> Option<u32> {
+        if *address == Address::ZERO { return Some(MX_MANUAL); }
+        t.index.get(address).copied()
+    }
+
+    /// the series of "{task_id or "manual"}:{label without ':'}" (metrics_store.rs:43-49); a new field gets the next number
+    fn metric_series(q: &mut MetricsQueue, task_id: &str, label: &str) -> u32 {
+        let task = if task_id.is_empty() { "manual" } else { task_id };
+        let cleaned = label.replace(':', "");
+        let next = q.keys.len() as u32;
+        let s = *q.series.entry(format!("{task}:{cleaned}")).or_insert(next);
+        if s == next { q.keys.push((task.to_string(), cleaned)); }
+        s
+    }
+
+    fn queue_metrics(&self, address: &Address, kind: u32, entries: &[(String, String, f64)]) {
+        let t = self.nodes.read();
+        let Some(row) = Self::metric_row(&t, address) else { return };
+        let mut q = self.metrics.lock();
+        let first = q.entries.len() as u32;
+        q.beats.push(pm_mx_beat { row, kind, first, n: entries.len() as u32 });
+        for (task_id, label, value) in entries {
+            // the rule is the ORIGINAL label's (metrics_store.rs:52)
+            let flags = if label.contains("dashboard-progress") { MXF_MAX } else { 0 };
+            let series = Self::metric_series(&mut q, task_id, label);
+            q.entries.push(pm_mx_entry { series, flags, value: *value });
+        }
+    }
+
+    /// heartbeat.rs:94-151 with Some(metrics): an empty list empties the row
+    pub fn beat_metrics(&self, address: &Address, entries: &[(String, String, f64)]) {
+        self.queue_metrics(address, MXB_REPLACE, entries)
+    }
+
+    /// metrics_store.rs:25-75
+    pub fn store_metrics(&self, address: &Address, entries: &[(String, String, f64)]) {
+        if entries.is_empty() { return; }     // :34-36
+        self.queue_metrics(address, MXB_MERGE, entries)
+    }
+
+    /// :77-89
+    pub fn store_manual_metric(&self, label: &str, value: f64) {
+        self.store_metrics(&Address::ZERO, &[(String::new(), label.to_string(), value)])
+    }
+
+    /// :91-109 (the key is "{task_id}:{cleaned}" as given: no "manual" for an empty task id); a field nobody stored is in no row
+    pub fn delete_metric(&self, task_id: &str, label: &str, address: &Address) {
+        let t = self.nodes.read();
+        let Some(row) = Self::metric_row(&t, address) else { return };
+        let mut q = self.metrics.lock();
+        let Some(&series) = q.series.get(&format!("{task_id}:{}", label.replace(':', ""))) else { return };
+        let first = q.entries.len() as u32;
+        q.beats.push(pm_mx_beat { row, kind: MXB_DELETE, first, n: 1 });
+        q.entries.push(pm_mx_entry { series, flags: 0, value: 0.0 });
+    }
+
+    /// the clean-up of an Ejected / Banned node (status_update/mod.rs:314-343); the sweep empties Dead rows itself
+    pub fn clear_metrics(&self, address: &Address) {
+        self.queue_metrics(address, MXB_REPLACE, &[])
+    }
+
+    fn flush_metrics_locked(&self, q: &mut MetricsQueue) -> Result<()> {
+        if q.beats.is_empty() { return Ok(()); }
+        let n_series = (q.keys.len() as u32).max(1);
+        let rc = unsafe { pm_metrics_ingest(self.engine, q.beats.as_ptr(), q.beats.len() as u32,
+                                            if q.entries.is_empty() { std::ptr::null() } else { q.entries.as_ptr() },
+                                            q.entries.len() as u32, n_series) };
+        q.beats.clear();                      // (a refused batch is dropped, not sent again and again)
+        q.entries.clear();
+        check(rc)
+    }
+
+    pub fn flush_metrics(&self) -> Result<()> {
+        let _t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)
+    }
+
+    fn metric_totals(&self) -> Result<(Vec<f64>, Vec<u32>)> {
+        let mut n = 0u32;
+        let rc = unsafe { pm_metrics_totals(self.engine, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n) };
+        if rc != PM_ERANGE { check(rc)?; }
+        let mut sum = vec![0f64; n.max(1) as usize];
+        let mut count = vec![0u32; n.max(1) as usize];
+        check(unsafe { pm_metrics_totals(self.engine, sum.as_mut_ptr(), count.as_mut_ptr(), sum.len() as u32, &mut n) })?;
+        sum.truncate(n as usize);
+        count.truncate(n as usize);
+        Ok((sum, count))
+    }
+
+    fn metric_rows(&self, t: &NodeTable, q: &MetricsQueue, rows: Option<&[u32]>) -> Result<Vec<pm_mx_row>> {
+        let (ptr, n) = rows.map_or((std::ptr::null(), 0u32), |r| (r.as_ptr(), r.len() as u32));
+        let mut have = 0u32;
+        let rc = unsafe { pm_metrics_rows(self.engine, ptr, n, std::ptr::null_mut(), 0, &mut have) };
+        if rc != PM_ERANGE { check(rc)?; }
+        let mut out = vec![pm_mx_row::default(); have.max(1) as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_metrics_rows(self.engine, ptr, n, out.as_mut_ptr(), out.len() as u32, &mut got) })?;
+        if got as usize > out.len() { return Err(anyhow!("metrics: the listing grew between two calls")); }
+        out.truncate(got as usize);
+        for r in &out {
+            if r.series as usize >= q.keys.len() || (r.row != MX_MANUAL && r.row as usize >= t.rows.len()) {
+                return Err(anyhow!("metrics: the engine lists an entry the plugin does not know"));
+            }
+        }
+        Ok(out)
+    }
+
+    /// get_aggregate_metrics_for_all_tasks (:176-202): the series' totals rolled up to label names, ascending series order
+    pub fn aggregate_metrics_for_all_tasks(&self) -> Result<HashMap<String, f64>> {
+        let _t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)?;
+        let (sum, count) = self.metric_totals()?;
+        let mut out: HashMap<String, f64> = HashMap::new();
+        for s in 0..sum.len().min(q.keys.len()) {
+            if count[s] != 0 { *out.entry(q.keys[s].1.clone()).or_insert(0.0) += sum[s]; }    // :196
+        }
+        Ok(out)
+    }
+
+    /// get_aggregate_metrics_for_task (:143-174)
+    pub fn aggregate_metrics_for_task(&self, task_id: &str) -> Result<HashMap<String, f64>> {
+        let _t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)?;
+        let (sum, count) = self.metric_totals()?;
+        let mut out: HashMap<String, f64> = HashMap::new();
+        for s in 0..sum.len().min(q.keys.len()) {
+            if count[s] != 0 && q.keys[s].0 == task_id { *out.entry(q.keys[s].1.clone()).or_insert(0.0) += sum[s]; }   // :166-167
+        }
+        Ok(out)
+    }
+
+    /// get_metrics_for_node (:111-131): task -> name -> value
+    pub fn metrics_for_node(&self, address: &Address) -> Result<HashMap<String, HashMap<String, f64>>> {
+        let t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)?;
+        let mut out: HashMap<String, HashMap<String, f64>> = HashMap::new();
+        let Some(row) = Self::metric_row(&t, address) else { return Ok(out) };
+        for r in self.metric_rows(&t, &q, Some(&[row]))? {
+            let (task, name) = &q.keys[r.series as usize];
+            out.entry(task.clone()).or_default().insert(name.clone(), r.value);
+        }
+        Ok(out)
+    }
+
+    /// get_all_metrics (:204-240): task -> name -> address -> value
+    pub fn all_metrics(&self) -> Result<HashMap<String, HashMap<String, HashMap<String, f64>>>> {
+        let t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)?;
+        let mut out: HashMap<String, HashMap<String, HashMap<String, f64>>> = HashMap::new();
+        for r in self.metric_rows(&t, &q, None)? {
+            let address = if r.row == MX_MANUAL { Address::ZERO.to_string() } else { t.address_strings[r.row as usize].clone() };
+            let (task, name) = &q.keys[r.series as usize];
+            out.entry(task.clone()).or_default().entry(name.clone()).or_default().insert(address, r.value);
+        }
+        Ok(out)
+    }
+
+    /// sync_metrics_from_redis' list (sync_service.rs:127-200): every entry with its task's name ("unknown" where the map has
+    /// none) and its node's group id and configuration name, joined by the engine
+    pub fn synced_metrics(&self, task_names: &HashMap<String, String>) -> Result<Vec<SyncedMetric>> {
+        let t = self.nodes.read();
+        let mut q = self.metrics.lock();
+        self.flush_metrics_locked(&mut q)?;
+        let mut out = Vec::new();
+        for r in self.metric_rows(&t, &q, None)? {
+            let (task, name) = &q.keys[r.series as usize];
+            let mut m = SyncedMetric {
+                address: if r.row == MX_MANUAL { Address::ZERO.to_string() } else { t.address_strings[r.row as usize].clone() },
+                task_id: task.clone(),
+                task_name: task_names.get(task).cloned().unwrap_or_else(|| "unknown".to_string()),   // :172-175
+                label: name.clone(),
+                value: r.value,
+                group_id: None,
+                group_config_name: None,
+            };
+            if r.group_id != PM_NONE as u64 {                                                        // :179-182
+                let Some(cfg) = self.config_names.get(r.config as usize) else {
+                    return Err(anyhow!("metrics: the engine names a configuration the plugin has not"));
+                };
+                m.group_id = Some(format!("{:x}", r.group_id));
+                m.group_config_name = Some(cfg.clone());
+            }
+            out.push(m);
+        }
         Ok(out)
     }
 

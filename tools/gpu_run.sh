@@ -26,6 +26,9 @@
 #                            -> r18_liveness.txt (copy it to profiles/)
 #   discovery[:<args>]       tools/discovery_probe.py [W] [--bench DIR]: pm_discovery_sync at W rows (100000), three shapes, beside each
 #                            the sequential D x W loop on one host thread -> r19_discovery.txt (copy it to profiles/)
+#   metrics[:<args>]         tools/metrics_probe.py [W] [E] [--bench DIR]: pm_metrics_ingest / _totals / _rows at W rows (100000) x E
+#                            series a row (8), beside each the same call as an unordered_map per node on one host thread
+#                            -> r20_metrics.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -147,6 +150,9 @@ PY
     discovery)
       timeout -k 10 300 python tools/discovery_probe.py $arg --out "$out/r19_discovery.txt" > "$out/${n}_discovery.log" 2>&1; echo "discovery rc=$?"
       tail -12 "$out/${n}_discovery.log" ;;
+    metrics)
+      timeout -k 10 300 python tools/metrics_probe.py $arg --out "$out/r20_metrics.txt" > "$out/${n}_metrics.log" 2>&1; echo "metrics rc=$?"
+      tail -12 "$out/${n}_metrics.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
