@@ -90,6 +90,11 @@ int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t
  * mode 2 (in, n unused): out[8] = PM_A_CHORD_MIN, PM_A_MAX_SAFE, the three certificate bands, the three slot widths. */
 int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out);
 
+/* What every engine of this process holds from the HIP runtime right now: out[0] = device bytes, out[1] = pinned host bytes,
+ * out[2] = events and streams.  Counted where an allocation is made or given back, not per call: an engine that is destroyed
+ * returns all three to what they were before it was created (tests/test_gpu_lifetime.py). */
+void pm_debug_live_allocations(uint64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

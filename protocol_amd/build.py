@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(HERE, "libpm_engine.so")
 SOURCES = ["pm_kernels.hip", "pm_engine.cpp", "pm_host.cpp"]
-HEADERS = ["pm_device.h", "pm_internal.h", "pm_members.h", "pm_measure.inc", "pm_validate.inc", "pm_propose.inc",
+HEADERS = ["pm_device.h", "pm_internal.h", "pm_members.h", "pm_owned.h", "pm_measure.inc", "pm_validate.inc", "pm_propose.inc",
            "pm_prep.inc", "pm_carve_kernel.inc", "pm_stream.inc", "pm_report.inc", "pm_spread.inc", "pm_near.inc", "pm_probe.inc", "pm_changes.inc", "pm_liveness.inc", "pm_discovery.inc", "pm_metrics.inc", "pm_launch.inc",
            "pm_engine_types.inc", "pm_engine_state.inc", "pm_engine_groups.inc", "pm_engine_carve.inc", "pm_engine_match.inc",
            "pm_engine_merge.inc", "pm_engine_workers.inc", "pm_engine_tasks.inc", "pm_engine_api.inc", "pm_engine_adopt.inc",

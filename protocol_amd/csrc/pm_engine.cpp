@@ -32,6 +32,7 @@
 #include "pm_engine.h"
 #include "pm_internal.h"
 #include "pm_members.h"
+#include "pm_owned.h"
 
 namespace pm {
 
@@ -61,13 +62,10 @@ struct FormRun;
 #include "pm_engine_state.inc"
 
 namespace pm {
+static int32_t changes_publish(pm_engine* e);  // pm_engine_changes.inc; publish_end (pm_engine_match.inc) calls it
 
 #include "pm_engine_groups.inc"
 #include "pm_engine_carve.inc"
-#include "pm_engine_changes.inc"
-#include "pm_engine_discovery.inc"
-#include "pm_engine_metrics.inc"
-#include "pm_engine_liveness.inc"
 #include "pm_engine_match.inc"
 #include "pm_engine_merge.inc"
 }  // namespace pm
@@ -106,7 +104,7 @@ int32_t pm_engine_create(const pm_engine_config* cfg, pm_engine** out) {
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return set_error(PM_ENODEV, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
   HIPCHK(carve_kernels_init());  // (per device; idempotent)
-  pm_engine* e = new (std::nothrow) pm_engine();
+  std::unique_ptr<pm_engine> e(new (std::nothrow) pm_engine());
   if (!e) return set_error(PM_ENOMEM, "out of host memory");
   e->cfg = *cfg;
   e->id_rng = cfg->group_id_seed;
@@ -147,26 +145,14 @@ int32_t pm_engine_create(const pm_engine_config* cfg, pm_engine** out) {
       e->n_cus = uint32_t(cus);
   }
   // (an engine owns ONE stream: K engines in a process take K of the HIP runtime's hardware queues)
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete e;
-    return set_error(PM_ENODEV, "hipStreamCreate failed");
-  }
-  e->stream_owned = e->stream;
+  if (e->stream_owned.create(hipStreamNonBlocking) != hipSuccess) return set_error(PM_ENODEV, "hipStreamCreate failed");
+  e->stream = e->stream_owned;
   for (auto& ev : e->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      delete e;
-      return set_error(PM_ENODEV, "hipEventCreate failed");
-    }
+    if (ev.create() != hipSuccess) return set_error(PM_ENODEV, "hipEventCreate failed");
   for (auto& ev : e->kev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      delete e;
-      return set_error(PM_ENODEV, "hipEventCreate failed");
-    }
-  if (hipEventCreateWithFlags(&e->ev_groups, hipEventDisableTiming) != hipSuccess) {
-    delete e;
-    return set_error(PM_ENODEV, "hipEventCreate failed");
-  }
-  *out = e;
+    if (ev.create() != hipSuccess) return set_error(PM_ENODEV, "hipEventCreate failed");
+  if (e->ev_groups.create(hipEventDisableTiming) != hipSuccess) return set_error(PM_ENODEV, "hipEventCreate failed");
+  *out = e.release();
   return PM_OK;
 }
 
@@ -174,61 +160,7 @@ void pm_engine_destroy(pm_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->cfg.device);
   (void)hipStreamSynchronize(e->stream);
-  e->d_cfgs.release(); e->d_alts.release(); e->d_model_bits.release();
-  e->d_flags.release(); e->d_gpu_count.release(); e->d_gpu_mem.release(); e->d_gpu_cls.release();
-  e->d_cpu_cores.release(); e->d_ram.release(); e->d_storage.release(); e->d_addr_rank.release();
-  e->d_lat.release(); e->d_lon.release(); e->d_coslat.release(); e->d_compat.release();
-  e->d_ux.release(); e->d_uy.release(); e->d_uz.release();
-  for (int k = 0; k < 3; ++k) { e->d_c_u[k].release(); e->d_cc_u[k].release(); }
-  e->d_tmask.release(); e->d_tplanes.release(); e->d_created.release(); e->d_tlive.release(); e->d_tprefix.release();
-  e->d_first_c.release(); e->d_count_c.release(); e->d_tdel.release();
-  e->d_group_of.release(); e->d_g_cfg.release(); e->d_g_n.release(); e->d_g_off.release();
-  e->d_g_task.release(); e->d_g_task_next.release(); e->d_members.release(); e->d_by_rank.release();
-  e->d_rank_in_group.release(); e->d_g_id.release();
-  e->d_order.release(); e->d_c_lat.release(); e->d_c_lon.release(); e->d_c_cos.release();
-  e->d_cc_lat.release(); e->d_cc_lon.release(); e->d_cc_cos.release(); e->d_slot_pos.release(); e->d_slot_wid.release();
-  e->d_site.release(); e->d_c_site.release(); e->d_cc_site.release(); e->d_prop.release(); e->d_seed_map.release(); e->d_seed_prefix.release(); e->d_seed_slots.release(); e->d_prep_block_counts.release(); e->d_prep_counts.release();
-  e->d_c_compat.release(); e->d_keys.release(); e->d_bits.release(); e->d_status.release(); e->d_carve_args.release();
-  e->d_m_cfg.release(); e->d_m_n.release(); e->d_m_off.release(); e->d_m_members.release();
-  e->d_cfgbits.release(); e->d_stream_sq.release(); e->d_stream_row_lo.release(); e->d_stream_row_hi.release();
-  e->d_stream_ctl.release(); e->d_stream_trace.release();
-  e->d_sel.release(); e->d_wplanes.release(); e->d_sel_perm.release();
-  e->d_first.release(); e->d_count.release(); e->d_rank.release(); e->d_chosen.release(); e->d_perm.release();
-  e->d_table.release(); e->d_task_col.release(); e->d_shard.release(); e->d_own_rows.release(); e->d_xrow.release();
-  e->d_sel_own.release(); e->d_table_x.release(); e->d_row_stage.release(); if (e->h_row_pin) (void)hipHostFree(e->h_row_pin); if (e->ev_row_stage) (void)hipEventDestroy(e->ev_row_stage); e->d_nb_idx.release(); e->d_nb_val.release();
-  if (e->h_gstage) (void)hipHostFree(e->h_gstage);
-  if (e->h_status) (void)hipHostFree(e->h_status);
-  for (int k = 0; k < 2; ++k) {
-    if (e->h_delta_pin[k]) (void)hipHostFree(e->h_delta_pin[k]);
-    e->d_delta[k].release();
-  }
-  if (e->h_gtask_pinned) (void)hipHostFree(e->h_gtask_pinned);
-  if (e->ev_groups) (void)hipEventDestroy(e->ev_groups);
-  for (PubTable& t : e->pub)
-    if (t.words.load()) (void)hipHostFree(t.words.load());
-  for (uint64_t* q : e->pub_retired) (void)hipHostFree(q);
-  for (auto& ev : e->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto& ev : e->kev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (hipEvent_t x : e->prop_ev) (void)hipEventDestroy(x);
-  if (e->stream_owned) (void)hipStreamDestroy(e->stream_owned);
-  e->d_cell_cnt.release(); e->d_cell_start.release(); e->d_pos_cell.release(); e->d_pos_rank.release();
-  e->d_cs_of_pos.release(); e->d_cs_slot.release(); e->d_cs_site.release();
-  for (auto& u : e->d_cs_u) u.release();
-  e->d_c_pack.release();
-  e->d_cs_pack.release();
-  e->d_desc.release(); e->d_snap.release(); e->d_ikeys.release(); e->d_umask.release(); e->d_ivals.release();
-  e->d_rep_rows.release(); e->d_rep_why.release(); e->d_rep_flags.release(); e->d_rep_live.release(); e->d_rep_g.release();
-  e->d_rep_tprefix.release(); e->d_rep_cnt.release(); e->d_rep_task.release(); e->d_rep_gof.release();
-  e->d_spr_idx.release(); e->d_spr_rows.release(); e->d_spr_acc.release();
-  e->d_near_q.release(); e->d_near_out.release();
-  e->d_probe_in.release(); e->d_probe_out.release();
-  changes_release(e);
-  liveness_release(e);
-  metrics_release(e);
-  delete e->form;
-  delete e;
+  delete e;  // (every member gives back what it holds: pm_engine_state.inc)
 }
 
 int32_t pm_set_configs(pm_engine* e, const pm_config_row* cfgs, uint32_t n_cfgs, const pm_gpu_alt_row* alts,
@@ -292,18 +224,16 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_spread.inc"
 #include "pm_engine_near.inc"
 #include "pm_engine_probe.inc"
-#define PM_CHANGES_ABI
+}  // extern "C"
+
+// the optional ledgers: each file holds its helpers (namespace pm) and, behind them, its entry points (extern "C").  Liveness
+// calls the metrics hook, and discovery asks liveness's guard: hence the order.
 #include "pm_engine_changes.inc"
-#undef PM_CHANGES_ABI
-#define PM_LIVENESS_ABI
-#include "pm_engine_liveness.inc"
-#undef PM_LIVENESS_ABI
-#define PM_DISCOVERY_ABI
-#include "pm_engine_discovery.inc"
-#undef PM_DISCOVERY_ABI
-#define PM_METRICS_ABI
 #include "pm_engine_metrics.inc"
-#undef PM_METRICS_ABI
+#include "pm_engine_liveness.inc"
+#include "pm_engine_discovery.inc"
+
+extern "C" {
 #include "pm_engine_tick.inc"
 #include "pm_engine_dist.inc"
 #include "pm_engine_debug.inc"

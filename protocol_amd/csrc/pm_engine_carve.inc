@@ -493,23 +493,16 @@ static int32_t form_setup_args(pm_engine* e, FormRun* r) {
     a.g_task_out = e->d_g_task.p;
     r->stage_cap = std::max<uint32_t>(r->n_bound, 1u);  // (a group holds at least one of the rows no group holds yet)
     const size_t need = size_t(4) * r->stage_cap;
-    if (e->h_gstage_cap < need) {
-      HIPCHK(hipStreamSynchronize(e->stream));  // (nothing in flight may still write the old buffer)
-      if (e->h_gstage) (void)hipHostFree(e->h_gstage);
-      e->h_gstage = nullptr;
-      e->h_gstage_cap = 0;
-      const size_t cap = std::max<size_t>(need, size_t(4) * std::max<uint32_t>(e->W, 1));
-      HIPCHK(hipHostMalloc((void**)&e->h_gstage, cap * sizeof(uint32_t)));
-      e->h_gstage_cap = cap;
-    }
-    if (!e->h_status) HIPCHK(hipHostMalloc((void**)&e->h_status, sizeof(CarveStatus)));
+    if (e->h_gstage.cap < need) HIPCHK(hipStreamSynchronize(e->stream));  // (nothing in flight may still write the old buffer)
+    HIPCHK(e->h_gstage.ensure(need, std::max<size_t>(need, size_t(4) * std::max<uint32_t>(e->W, 1))));
+    HIPCHK(e->h_status.ensure(1, 1));
     a.stage_cap_g = a.stage_cap_m = r->stage_cap;
-    a.stage_cfg = e->h_gstage;
-    a.stage_n = e->h_gstage + r->stage_cap;
-    a.stage_off = e->h_gstage + size_t(2) * r->stage_cap;
-    a.stage_mem = e->h_gstage + size_t(3) * r->stage_cap;
-    a.h_status = e->h_status;
-    e->h_status->state = 0xFFFFFFFFu;  // (not yet written by this carve)
+    a.stage_cfg = e->h_gstage.p;
+    a.stage_n = e->h_gstage.p + r->stage_cap;
+    a.stage_off = e->h_gstage.p + size_t(2) * r->stage_cap;
+    a.stage_mem = e->h_gstage.p + size_t(3) * r->stage_cap;
+    a.h_status = e->h_status.p;
+    e->h_status.p->state = 0xFFFFFFFFu;  // (not yet written by this carve)
   }
   a.n_avail = uint32_t(r->avail.size());
   for (size_t i = 0; i < r->avail.size(); ++i) {
@@ -538,9 +531,9 @@ static int32_t launch_propose_timed(pm_engine* e, const CarveArgs* d_args, uint3
     return PM_OK;
   }
   while (e->prop_ev.size() < e->prop_ev_used + 2) {
-    hipEvent_t x = nullptr;
-    HIPCHK(hipEventCreate(&x));
-    e->prop_ev.push_back(x);
+    Event x;
+    HIPCHK(x.create());
+    e->prop_ev.push_back(std::move(x));
   }
   HIPCHK(hipEventRecord(e->prop_ev[e->prop_ev_used], s));
   launch_carve_propose(d_args, n_bound, s);
@@ -656,22 +649,15 @@ static int32_t form_finish(pm_engine* e, FormRun* r, uint32_t* n_formed, bool de
     // batch pipeline — they are copied and filled in here.
     const bool staged = r->stream && !r->rearmed && ng <= r->stage_cap && nm <= r->stage_cap;
     if (staged) {
-      e->ab_cfg_p = e->h_gstage;
-      e->ab_n_p = e->h_gstage + r->stage_cap;
-      e->ab_off_p = e->h_gstage + size_t(2) * r->stage_cap;
-      e->ab_mem_p = e->h_gstage + size_t(3) * r->stage_cap;
+      e->ab_cfg_p = e->h_gstage.p;
+      e->ab_n_p = e->h_gstage.p + r->stage_cap;
+      e->ab_off_p = e->h_gstage.p + size_t(2) * r->stage_cap;
+      e->ab_mem_p = e->h_gstage.p + size_t(3) * r->stage_cap;
       if (!have_event) HIPCHK(hipEventRecord(e->ev_groups, e->stream));
     } else {
       const size_t need = size_t(3) * ng + nm;
-      if (e->h_gstage_cap < need) {
-        if (e->h_gstage) (void)hipHostFree(e->h_gstage);
-        e->h_gstage = nullptr;
-        e->h_gstage_cap = 0;
-        const size_t cap = std::max<size_t>(need, size_t(4) * std::max<uint32_t>(e->W, 1));
-        HIPCHK(hipHostMalloc((void**)&e->h_gstage, cap * sizeof(uint32_t)));
-        e->h_gstage_cap = cap;
-      }
-      uint32_t* st_cfg = e->h_gstage;
+      HIPCHK(e->h_gstage.ensure(need, std::max<size_t>(need, size_t(4) * std::max<uint32_t>(e->W, 1))));
+      uint32_t* st_cfg = e->h_gstage.p;
       HIPCHK(hipMemcpyAsync(st_cfg, e->d_g_cfg.p + g0, size_t(ng) * 4, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipMemcpyAsync(st_cfg + ng, e->d_g_n.p + g0, size_t(ng) * 4, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipMemcpyAsync(st_cfg + 2 * size_t(ng), e->d_g_off.p + g0, size_t(ng) * 4, hipMemcpyDeviceToHost, e->stream));

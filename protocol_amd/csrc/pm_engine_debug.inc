@@ -141,13 +141,10 @@ int32_t pm_debug_hbm_triad(pm_engine* e, uint64_t n_doubles, uint32_t reps, doub
   if (!e || !gb_per_s || !n_doubles) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(hipSetDevice(e->cfg.device));
-  double *a = nullptr, *b = nullptr, *c = nullptr;
-  HIPCHK(hipMalloc((void**)&a, n_doubles * 8));
-  if (hipMalloc((void**)&b, n_doubles * 8) != hipSuccess || hipMalloc((void**)&c, n_doubles * 8) != hipSuccess) {
-    (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    return set_error(PM_ENOMEM, "triad buffers");
-  }
+  DevBuf<double> d_a, d_b, d_c;  // (freed on every way out)
+  HIPCHK(d_a.ensure(n_doubles));
+  if (d_b.ensure(n_doubles) != hipSuccess || d_c.ensure(n_doubles) != hipSuccess) return set_error(PM_ENOMEM, "triad buffers");
+  double *const a = d_a.p, *const b = d_b.p, *const c = d_c.p;
   (void)hipMemsetAsync(b, 0, n_doubles * 8, e->stream);
   (void)hipMemsetAsync(c, 0, n_doubles * 8, e->stream);
   float best = 1e30f;
@@ -160,9 +157,6 @@ int32_t pm_debug_hbm_triad(pm_engine* e, uint64_t n_doubles, uint32_t reps, doub
     (void)hipEventElapsedTime(&ms, e->kev[0], e->kev[1]);
     if (r > 0 && ms < best) best = ms;
   }
-  (void)hipFree(a);
-  (void)hipFree(b);
-  (void)hipFree(c);
   *gb_per_s = double(n_doubles) * 24.0 / (double(best) * 1e-3) / 1e9;
   return PM_OK;
 }
@@ -177,26 +171,19 @@ int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(hipSetDevice(e->cfg.device));
   const size_t nk = size_t(n_waves) * n_per_wave, ns = size_t(1) << slot_bits;
-  uint64_t *d_k = nullptr, *d_rows = nullptr;
-  uint32_t *d_s = nullptr, *d_m = nullptr;
-  int32_t rc = PM_OK;
-  if (hipMalloc((void**)&d_k, nk * 8) != hipSuccess || hipMalloc((void**)&d_rows, size_t(n_waves) * 64 * 8) != hipSuccess ||
-      hipMalloc((void**)&d_s, ns * 4) != hipSuccess || hipMalloc((void**)&d_m, 8) != hipSuccess) {
-    rc = set_error(PM_ENOMEM, "row network test buffers");
-  } else {
-    (void)hipMemcpyAsync(d_k, keys, nk * 8, hipMemcpyHostToDevice, e->stream);
-    (void)hipMemcpyAsync(d_s, sites, ns * 4, hipMemcpyHostToDevice, e->stream);
-    (void)hipMemsetAsync(d_m, 0, 8, e->stream);
-    launch_row_network_test(d_k, d_s, n_waves, n_per_wave, slot_bits, ulps, upto, d_rows, d_m, e->stream);
-    (void)hipMemcpyAsync(rows_out, d_rows, size_t(n_waves) * 64 * 8, hipMemcpyDeviceToHost, e->stream);
-    (void)hipMemcpyAsync(mismatches, d_m, 8, hipMemcpyDeviceToHost, e->stream);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) rc = set_error(PM_ENODEV, "row network test");
-  }
-  if (d_k) (void)hipFree(d_k);
-  if (d_rows) (void)hipFree(d_rows);
-  if (d_s) (void)hipFree(d_s);
-  if (d_m) (void)hipFree(d_m);
-  return rc;
+  DevBuf<uint64_t> d_k, d_rows;
+  DevBuf<uint32_t> d_s, d_m;
+  if (d_k.ensure(nk) != hipSuccess || d_rows.ensure(size_t(n_waves) * 64) != hipSuccess || d_s.ensure(ns) != hipSuccess ||
+      d_m.ensure(2) != hipSuccess)
+    return set_error(PM_ENOMEM, "row network test buffers");
+  (void)hipMemcpyAsync(d_k.p, keys, nk * 8, hipMemcpyHostToDevice, e->stream);
+  (void)hipMemcpyAsync(d_s.p, sites, ns * 4, hipMemcpyHostToDevice, e->stream);
+  (void)hipMemsetAsync(d_m.p, 0, 8, e->stream);
+  launch_row_network_test(d_k.p, d_s.p, n_waves, n_per_wave, slot_bits, ulps, upto, d_rows.p, d_m.p, e->stream);
+  (void)hipMemcpyAsync(rows_out, d_rows.p, size_t(n_waves) * 64 * 8, hipMemcpyDeviceToHost, e->stream);
+  (void)hipMemcpyAsync(mismatches, d_m.p, 8, hipMemcpyDeviceToHost, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return set_error(PM_ENODEV, "row network test");
+  return PM_OK;
 }
 
 // debug (include/pm_engine_debug.h): the distance key of n pairs by geo_kernel and the carve's own device functions
@@ -212,24 +199,18 @@ int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint3
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(hipSetDevice(e->cfg.device));
   const size_t n_in = mode == 0u ? size_t(5) * n : n, n_out = mode == 0u ? size_t(PM_DK_WORDS) * n : n;
-  double *d_in = nullptr, *d_geo = nullptr, *d_out = nullptr;
-  int32_t rc = PM_OK;
-  if (hipMalloc((void**)&d_in, n_in * 8) != hipSuccess || hipMalloc((void**)&d_out, n_out * 8) != hipSuccess ||
-      (mode == 0u && hipMalloc((void**)&d_geo, size_t(8) * n * 8) != hipSuccess)) {
-    rc = set_error(PM_ENOMEM, "distance key test buffers");
-  } else {
-    (void)hipMemcpyAsync(d_in, in, n_in * 8, hipMemcpyHostToDevice, e->stream);
-    if (mode == 0u)  // cos(lat), ux, uy, uz of the 2n points, by the kernel that makes the worker table's columns
-      launch_geo(d_in, d_in + size_t(2) * n, d_geo, d_geo + size_t(2) * n, d_geo + size_t(4) * n, d_geo + size_t(6) * n, 2u * n,
-                 e->stream);
-    launch_distance_key_test(d_in, d_geo, n, mode, d_out, e->stream);
-    (void)hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, e->stream);
-    if (hipStreamSynchronize(e->stream) != hipSuccess) rc = set_error(PM_ENODEV, "distance key test");
-  }
-  if (d_in) (void)hipFree(d_in);
-  if (d_geo) (void)hipFree(d_geo);
-  if (d_out) (void)hipFree(d_out);
-  return rc;
+  DevBuf<double> b_in, b_geo, b_out;
+  if (b_in.ensure(n_in) != hipSuccess || b_out.ensure(n_out) != hipSuccess || (mode == 0u && b_geo.ensure(size_t(8) * n) != hipSuccess))
+    return set_error(PM_ENOMEM, "distance key test buffers");
+  double *const d_in = b_in.p, *const d_geo = b_geo.p, *const d_out = b_out.p;
+  (void)hipMemcpyAsync(d_in, in, n_in * 8, hipMemcpyHostToDevice, e->stream);
+  if (mode == 0u)  // cos(lat), ux, uy, uz of the 2n points, by the kernel that makes the worker table's columns
+    launch_geo(d_in, d_in + size_t(2) * n, d_geo, d_geo + size_t(2) * n, d_geo + size_t(4) * n, d_geo + size_t(6) * n, 2u * n,
+               e->stream);
+  launch_distance_key_test(d_in, d_geo, n, mode, d_out, e->stream);
+  (void)hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return set_error(PM_ENODEV, "distance key test");
+  return PM_OK;
 }
 
 #ifdef PM_ROW_BENCH
@@ -255,29 +236,28 @@ extern "C" int32_t pm_debug_row_bench(pm_engine* e, uint32_t ci, uint32_t kth, u
         break;
       }
   if (seed == PM_NONE) return set_error(PM_EINVAL, "fewer candidates than that");
-  unsigned long long *d_ones = nullptr, *d_out = nullptr;
-  CarveArgs* d_h = nullptr;
+  DevBuf<unsigned long long> d_ones, d_out;
+  DevBuf<CarveArgs> d_h;
+  if (d_ones.ensure(h.bits_stride) != hipSuccess || d_out.ensure(8) != hipSuccess || d_h.ensure(1) != hipSuccess)
+    return set_error(PM_ENOMEM, "row bench buffers");
   int32_t rc = PM_OK;
-  if (hipMalloc((void**)&d_ones, h.bits_stride * 8) != hipSuccess || hipMalloc((void**)&d_out, 64) != hipSuccess ||
-      hipMalloc((void**)&d_h, sizeof(h)) != hipSuccess) {
-    rc = set_error(PM_ENOMEM, "row bench buffers");
-  } else {
-    (void)hipMemset(d_ones, 0xFF, h.bits_stride * 8);
-    (void)hipMemset(d_out, 0, 64);
-    h.bits_scratch = (uint64_t*)d_ones;
-    (void)hipMemcpy(d_h, &h, sizeof(h), hipMemcpyHostToDevice);
-    if (launch_row_bench(d_h, seed, ci, reps, mode, d_out, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
-      rc = set_error(PM_ENODEV, "row bench");
-    else
-      (void)hipMemcpy(out, d_out, 64, hipMemcpyDeviceToHost);
-    out[7] = seed;
-  }
-  if (d_ones) (void)hipFree(d_ones);
-  if (d_out) (void)hipFree(d_out);
-  if (d_h) (void)hipFree(d_h);
+  (void)hipMemset(d_ones.p, 0xFF, h.bits_stride * 8);
+  (void)hipMemset(d_out.p, 0, 64);
+  h.bits_scratch = (uint64_t*)d_ones.p;
+  (void)hipMemcpy(d_h.p, &h, sizeof(h), hipMemcpyHostToDevice);
+  if (launch_row_bench(d_h.p, seed, ci, reps, mode, d_out.p, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
+    rc = set_error(PM_ENODEV, "row bench");
+  else
+    (void)hipMemcpy(out, d_out.p, 64, hipMemcpyDeviceToHost);
+  out[7] = seed;
   return rc;
 }
 #endif
+
+// debug (include/pm_engine_debug.h): what the owning types of pm_owned.h hold in this process right now
+void pm_debug_live_allocations(uint64_t out[3]) {
+  for (int k = 0; k < 3; ++k) out[k] = g_live_allocs[k].load(std::memory_order_relaxed);
+}
 
 int32_t pm_last_stats(pm_engine* e, pm_stats* stats) {
   if (!e || !stats) return set_error(PM_EINVAL, "null argument");

@@ -1,20 +1,12 @@
-// pm_engine_discovery.inc — part of pm_engine.cpp (one translation unit; included in place): the discovery sync: its scratch
-// buffers (inside namespace pm, in front of pm_engine_liveness.inc: they are released with the ledger) — and, inside
-// extern "C" (PM_DISCOVERY_ABI), C ABI: pm_discovery_sync (kernels in pm_discovery.inc).
+// pm_engine_discovery.inc — part of pm_engine.cpp (one translation unit; included in place): the discovery sync, C ABI:
+// pm_discovery_sync (kernels in pm_discovery.inc).  Its scratch (struct Discovery) is released with the liveness ledger
+// (liveness_release).  Included at file scope, behind pm_engine_liveness.inc.
 //
 // Everything a kernel indexes with is checked here first, on the host, in one pass over the rows and one over the endpoint
 // column: a failing call has then touched neither the device nor the ledger.  The inputs travel as one staged copy (the rows,
 // behind them the column), the results as one copy back, behind one stream synchronisation; an applying call builds its update
 // list from those results on the host.
-#ifndef PM_DISCOVERY_ABI
-
-static void discovery_release(pm_engine* e) {
-  e->d_disc_in.release(); e->d_disc_work.release(); e->d_disc_events.release(); e->d_disc_out.release();
-  e->h_disc_in.clear(); e->h_disc_out.clear(); e->h_disc_seen.clear();
-  e->disc_epoch = 0;
-}
-
-#else  // PM_DISCOVERY_ABI
+extern "C" {
 
 int32_t pm_discovery_sync(pm_engine* e, uint64_t now_ms, const uint32_t* row_endpoint, uint32_t n_endpoints,
                           uint32_t max_healthy_same_endpoint, const pm_disc_row* rows, uint32_t n_rows, uint32_t apply,
@@ -38,15 +30,15 @@ int32_t pm_discovery_sync(pm_engine* e, uint64_t now_ms, const uint32_t* row_end
   }
   for (uint32_t w = 0; w < W; ++w)
     if (row_endpoint[w] != PM_EP_NONE && row_endpoint[w] >= E) return set_error(PM_ERANGE, "endpoint column: id out of range");
-  if (e->h_disc_seen.size() != W || e->disc_epoch == 0xFFFFFFFFu) {  // (a stamp of an earlier table, or of 2^32 calls ago)
-    e->h_disc_seen.assign(W, 0u);
-    e->disc_epoch = 0;
+  if (e->disc.h_seen.size() != W || e->disc.epoch == 0xFFFFFFFFu) {  // (a stamp of an earlier table, or of 2^32 calls ago)
+    e->disc.h_seen.assign(W, 0u);
+    e->disc.epoch = 0;
   }
-  const uint32_t epoch = ++e->disc_epoch;
+  const uint32_t epoch = ++e->disc.epoch;
   for (uint32_t j = 0; j < D; ++j) {
     if (rows[j].row == PM_DISC_NEW) continue;
-    if (e->h_disc_seen[rows[j].row] == epoch) return set_error(PM_EINVAL, "a table row listed twice");
-    e->h_disc_seen[rows[j].row] = epoch;
+    if (e->disc.h_seen[rows[j].row] == epoch) return set_error(PM_EINVAL, "a table row listed twice");
+    e->disc.h_seen[rows[j].row] = epoch;
   }
   HIPCHK(hipSetDevice(e->cfg.device));
   if ((rc = liveness_prepare(e))) return rc;
@@ -55,17 +47,17 @@ int32_t pm_discovery_sync(pm_engine* e, uint64_t now_ms, const uint32_t* row_end
 
   static_assert(sizeof(pm_disc_row) == 32 && sizeof(pm_disc_result) == 16, "the layouts the kernels read and write");
   const size_t row_words = size_t(D) * 4, col_words = (size_t(W) + 1) / 2;  // (u64 words)
-  std::vector<uint64_t>& in = e->h_disc_in;
+  std::vector<uint64_t>& in = e->disc.h_in;
   in.resize(row_words + col_words);
   std::memcpy(in.data(), rows, size_t(D) * sizeof(pm_disc_row));
   if (W) std::memcpy(in.data() + row_words, row_endpoint, size_t(W) * sizeof(uint32_t));
   const size_t zeroed = 3 * size_t(E) + 1;
-  HIPCHK(e->d_disc_in.ensure(in.size()));
-  HIPCHK(e->d_disc_work.ensure(size_t(W) + zeroed + E));
-  HIPCHK(e->d_disc_events.ensure(2 * size_t(D)));
-  HIPCHK(e->d_disc_out.ensure(D));
-  HIPCHK(hipMemcpyAsync(e->d_disc_in.p, in.data(), in.size() * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-  uint32_t* const work = e->d_disc_work.p;
+  HIPCHK(e->disc.in.ensure(in.size()));
+  HIPCHK(e->disc.work.ensure(size_t(W) + zeroed + E));
+  HIPCHK(e->disc.events.ensure(2 * size_t(D)));
+  HIPCHK(e->disc.out.ensure(D));
+  HIPCHK(hipMemcpyAsync(e->disc.in.p, in.data(), in.size() * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+  uint32_t* const work = e->disc.work.p;
   if (W) HIPCHK(hipMemsetAsync(work, 0xFF, size_t(W) * sizeof(uint32_t), e->stream));  // (PM_DISC_NEW: unlisted)
   HIPCHK(hipMemsetAsync(work + W, 0, zeroed * sizeof(uint32_t), e->stream));
   DiscArgs a{};
@@ -74,23 +66,23 @@ int32_t pm_discovery_sync(pm_engine* e, uint64_t now_ms, const uint32_t* row_end
   a.E = E;
   a.max_same = max_healthy_same_endpoint;
   a.now_ms = now_ms;
-  a.rows = reinterpret_cast<const pm_disc_row*>(e->d_disc_in.p);
-  a.row_endpoint = reinterpret_cast<const uint32_t*>(e->d_disc_in.p + row_words);
-  a.status = e->d_live_status.p;
+  a.rows = reinterpret_cast<const pm_disc_row*>(e->disc.in.p);
+  a.row_endpoint = reinterpret_cast<const uint32_t*>(e->disc.in.p + row_words);
+  a.status = e->live.status.p;
   a.pos_of_row = work;
   a.base = work + W;
   a.ev_cnt = a.base + E;
   a.ev_fill = a.ev_cnt + E;
   a.cursor = a.ev_fill + E;
   a.ev_off = a.cursor + 1;
-  a.events = e->d_disc_events.p;
-  a.out = e->d_disc_out.p;
+  a.events = e->disc.events.p;
+  a.out = e->disc.out.p;
   launch_discovery_sync(a, e->stream);
   HIPCHK(hipGetLastError());
-  e->h_disc_out.resize(D);
-  HIPCHK(hipMemcpyAsync(e->h_disc_out.data(), e->d_disc_out.p, size_t(D) * sizeof(pm_disc_result), hipMemcpyDeviceToHost, e->stream));
+  e->disc.h_out.resize(D);
+  HIPCHK(hipMemcpyAsync(e->disc.h_out.data(), e->disc.out.p, size_t(D) * sizeof(pm_disc_result), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
-  const std::vector<pm_disc_result>& res = e->h_disc_out;
+  const std::vector<pm_disc_result>& res = e->disc.h_out;
   if (out) std::copy(res.begin(), res.end(), out);
   size_t total = 0;
   for (uint32_t j = 0; j < D; ++j) {
@@ -123,4 +115,4 @@ int32_t pm_discovery_sync(pm_engine* e, uint64_t now_ms, const uint32_t* row_end
   return worker_status_many_locked(e, workers.data(), flags_new.data(), dead.data(), uint32_t(workers.size()));
 }
 
-#endif
+}  // extern "C"

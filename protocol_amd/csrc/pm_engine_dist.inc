@@ -30,8 +30,7 @@ int32_t pm_set_stream(pm_engine* e, void* hip_stream) {
 }
 
 static void dist_abort(pm_engine* e) {
-  delete e->form;
-  e->form = nullptr;
+  e->form.reset();
   e->dist_phase = 0;
 }
 
@@ -41,9 +40,9 @@ int32_t pm_dist_configure(pm_engine* e, uint32_t rank, uint32_t world, const uin
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(hipSetDevice(e->cfg.device));
   if (e->dist_phase != 0) return set_error(PM_ESTATE, "a stepwise tick is in progress");
-  if (world > 1 && e->chg_on) return set_error(PM_ESTATE, "the assignment change feed is on: it does not cover multi-GPU engines");
-  if (world > 1 && e->live_on) return set_error(PM_ESTATE, "liveness is on: it does not cover multi-GPU engines");
-  if (world > 1 && e->mx_on) return set_error(PM_ESTATE, "the metrics ledger is on: it does not cover multi-GPU engines");
+  if (world > 1 && e->chg.on) return set_error(PM_ESTATE, "the assignment change feed is on: it does not cover multi-GPU engines");
+  if (world > 1 && e->live.on) return set_error(PM_ESTATE, "liveness is on: it does not cover multi-GPU engines");
+  if (world > 1 && e->mx.on) return set_error(PM_ESTATE, "the metrics ledger is on: it does not cover multi-GPU engines");
   if (world > 1 && !e->have_workers) return set_error(PM_ESTATE, "workers must be uploaded first");
   if (world > 1 && e->W && !shard_of_worker) return set_error(PM_EINVAL, "null shard column");
   e->dist_rank = world > 1 ? rank : 0;
@@ -91,12 +90,12 @@ int32_t pm_dist_tick_begin(pm_engine* e) {
   int32_t rc = ensure_compat(e);
   if (rc) return rc;
   HIPCHK(hipEventRecord(e->ev[1], e->stream));
-  e->form = new (std::nothrow) FormRun();
+  e->form.reset(new (std::nothrow) FormRun());
   if (!e->form) return set_error(PM_ENOMEM, "out of host memory");
   // The carve is REPLICATED: every rank runs the whole of it — the streaming launch, as on one GPU — and ends with the
   // identical groups and ids, because the result does not depend on how the launch went (which rows arrived when), only
   // on the reference's rule: nothing is exchanged until the published table (DESIGN.md section 7).
-  rc = form_begin(e, e->form);
+  rc = form_begin(e, e->form.get());
   if (rc) {
     dist_abort(e);
     return rc;
@@ -110,7 +109,7 @@ int32_t pm_dist_carve_wait(pm_engine* e) {
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(hipSetDevice(e->cfg.device));
   if (e->dist_phase != 1) return set_error(PM_ESTATE, "pm_dist_tick_begin first");
-  FormRun* r = e->form;
+  FormRun* r = e->form.get();
   if (!r->nothing) {
     int32_t rc = run_form_wait(e, *r);
     if (rc) {
@@ -132,9 +131,8 @@ int32_t pm_dist_match_begin(pm_engine* e, pm_dist_xfer* x) {
   HIPCHK(hipSetDevice(e->cfg.device));
   if (e->dist_phase != 2) return set_error(PM_ESTATE, "the carve is not finished (pm_dist_carve_wait first)");
   std::memset(x, 0, sizeof(*x));
-  int32_t rc = form_finish(e, e->form, &e->dist_n_formed, /*defer_absorb=*/true);
-  delete e->form;
-  e->form = nullptr;
+  int32_t rc = form_finish(e, e->form.get(), &e->dist_n_formed, /*defer_absorb=*/true);
+  e->form.reset();
   if (rc == PM_OK) {
     HIPCHK(hipEventRecord(e->ev[2], e->stream));
     rc = run_merge(e, &e->dist_n_merged);

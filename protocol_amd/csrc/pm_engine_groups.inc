@@ -33,7 +33,7 @@ static void reset_groups_locked(pm_engine* e) {
   // against the new list.
   e->groups_epoch++;
   pub_clear(e);
-  e->chg_resync = true;  // (the id stream may repeat: the change feed's remembered ids prove nothing)
+  e->chg.resync = true;  // (the id stream may repeat: the change feed's remembered ids prove nothing)
 }
 
 // dissolve_group (mod.rs:1423-1487).  A status storm dissolves hundreds of groups per tick; removing each from
@@ -82,14 +82,7 @@ static void compact_groups(pm_engine* e) {
 // up once per tick, in front of it)
 static int32_t delta_stage(pm_engine* e, int which, size_t n) {
   HIPCHK(hipStreamSynchronize(e->stream));  // (nothing in flight may still read the staging: an idle stream answers at once)
-  if (e->h_delta_cap[which] < n) {
-    if (e->h_delta_pin[which]) (void)hipHostFree(e->h_delta_pin[which]);
-    e->h_delta_pin[which] = nullptr;
-    e->h_delta_cap[which] = 0;
-    const size_t cap = n + n / 2 + 4096;
-    HIPCHK(hipHostMalloc((void**)&e->h_delta_pin[which], cap * sizeof(uint32_t)));
-    e->h_delta_cap[which] = cap;
-  }
+  HIPCHK(e->h_delta_pin[which].ensure(n, n + n / 2 + 4096));
   HIPCHK(e->d_delta[which].ensure(n));
   return PM_OK;
 }
@@ -112,8 +105,8 @@ static int32_t push_groups(pm_engine* e) {
       const size_t n = e->delta_free.size();
       int32_t rc = delta_stage(e, 0, n);
       if (rc) return rc;
-      std::memcpy(e->h_delta_pin[0], e->delta_free.data(), n * 4);
-      HIPCHK(hipMemcpyAsync(e->d_delta[0].p, e->h_delta_pin[0], n * 4, hipMemcpyHostToDevice, e->stream));
+      std::memcpy(e->h_delta_pin[0].p, e->delta_free.data(), n * 4);
+      HIPCHK(hipMemcpyAsync(e->d_delta[0].p, e->h_delta_pin[0].p, n * 4, hipMemcpyHostToDevice, e->stream));
       launch_scatter_const(reinterpret_cast<uint32_t*>(e->d_group_of.p), e->d_delta[0].p, uint32_t(n), 0xFFFFFFFFu, e->stream);
       HIPCHK(hipGetLastError());
     }
@@ -184,10 +177,10 @@ static int32_t sync_flags(pm_engine* e) {
       int32_t rc = delta_stage(e, 1, 2 * n);
       if (rc) return rc;
       for (size_t k = 0; k < n; ++k) {
-        e->h_delta_pin[1][2 * k] = e->delta_flags[k];
-        e->h_delta_pin[1][2 * k + 1] = e->h_flags[e->delta_flags[k]];
+        e->h_delta_pin[1].p[2 * k] = e->delta_flags[k];
+        e->h_delta_pin[1].p[2 * k + 1] = e->h_flags[e->delta_flags[k]];
       }
-      HIPCHK(hipMemcpyAsync(e->d_delta[1].p, e->h_delta_pin[1], n * 8, hipMemcpyHostToDevice, e->stream));
+      HIPCHK(hipMemcpyAsync(e->d_delta[1].p, e->h_delta_pin[1].p, n * 8, hipMemcpyHostToDevice, e->stream));
       launch_scatter_pairs(e->d_flags.p, e->d_delta[1].p, uint32_t(n), e->stream);
       HIPCHK(hipGetLastError());
     }

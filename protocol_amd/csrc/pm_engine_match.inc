@@ -189,14 +189,16 @@ static int32_t pub_buffer(pm_engine* e, PubTable& t, uint32_t rows, uint64_t** o
   uint64_t* words = t.words.load(std::memory_order_relaxed);
   if (t.cap_rows < rows || !words) {
     const size_t cap = std::max<size_t>(size_t(rows) + rows / 8 + 64, 64);
-    uint64_t* nw = nullptr;
-    if (hipHostMalloc((void**)&nw, cap * 32) != hipSuccess || !nw)
+    PinBuf<uint64_t> nb;
+    if (nb.ensure(cap * 4, cap * 4) != hipSuccess || !nb.p)
       return set_error(PM_ENOMEM, "out of pinned host memory for the published table");
+    uint64_t* const nw = nb.p;
     std::memset(nw, 0, cap * 32);
     const uint64_t s0 = t.seq.load(std::memory_order_relaxed);
     t.seq.store(s0 + 1, std::memory_order_relaxed);  // odd while the pointer changes
     std::atomic_thread_fence(std::memory_order_release);
-    if (words) e->pub_retired.push_back(words);
+    if (words) e->pub_retired.push_back(std::move(t.own));
+    t.own = std::move(nb);
     words = nw;
     t.cap_rows = cap;
     t.words.store(nw, std::memory_order_relaxed);
@@ -355,14 +357,7 @@ static void publish_abandon(pm_engine* e, const PubRun& pr) {
 static int32_t publish_begin(pm_engine* e, PubRun* pr, size_t G, bool direct = false) {
   e->claim_h_table = nullptr;
   e->claim_h_gtask = nullptr;
-  if (e->h_gtask_cap < G) {
-    if (e->h_gtask_pinned) (void)hipHostFree(e->h_gtask_pinned);
-    e->h_gtask_pinned = nullptr;
-    e->h_gtask_cap = 0;
-    const size_t cap = std::max<size_t>(G, std::max<uint32_t>(e->W, 1));
-    HIPCHK(hipHostMalloc((void**)&e->h_gtask_pinned, cap * sizeof(uint32_t)));
-    e->h_gtask_cap = cap;
-  }
+  HIPCHK(e->h_gtask_pinned.ensure(G, std::max<size_t>(G, std::max<uint32_t>(e->W, 1))));
   const int cur = e->pub_cur.load(std::memory_order_relaxed);
   const int nx = cur < 0 ? 0 : (cur ^ 1);
   PubTable& t = e->pub[nx];
@@ -380,13 +375,13 @@ static int32_t publish_begin(pm_engine* e, PubRun* pr, size_t G, bool direct = f
   pr->G = G;
   if (direct) {
     e->claim_h_table = reinterpret_cast<pm_assignment*>(words);
-    e->claim_h_gtask = e->h_gtask_pinned;
+    e->claim_h_gtask = e->h_gtask_pinned.p;
     return PM_OK;
   }
   hipError_t herr = hipSuccess;
   if (e->W) herr = hipMemcpyAsync(words, e->d_table.p, sizeof(pm_assignment) * e->W, hipMemcpyDeviceToHost, e->stream);
   if (herr == hipSuccess && G)
-    herr = hipMemcpyAsync(e->h_gtask_pinned, e->d_g_task_next.p, G * 4, hipMemcpyDeviceToHost, e->stream);
+    herr = hipMemcpyAsync(e->h_gtask_pinned.p, e->d_g_task_next.p, G * 4, hipMemcpyDeviceToHost, e->stream);
   if (herr != hipSuccess) {
     publish_abandon(e, *pr);
     HIPCHK(herr);
@@ -406,7 +401,7 @@ static int32_t publish_end(pm_engine* e, const PubRun& pr) {
     publish_abandon(e, pr);
     return set_error(PM_ESTATE, "publish: the host group list and the device group arrays disagree");
   }
-  const uint32_t* g_task = e->h_gtask_pinned;
+  const uint32_t* g_task = e->h_gtask_pinned.p;
   t.n.store(e->W, std::memory_order_relaxed);
   t.task_shift.store(0, std::memory_order_relaxed);
   t.cleared.store(0, std::memory_order_relaxed);
@@ -420,7 +415,7 @@ static int32_t publish_end(pm_engine* e, const PubRun& pr) {
     e->groups[g].task_uid = g_task[g] == PM_NONE ? 0 : (e->tasks_have_uid ? e->h_tuid[g_task[g]] : task_position(e, g_task[g]));
   }
   std::swap(e->d_g_task, e->d_g_task_next);
-  if (e->chg_on) return changes_publish(e);  // (the change feed: this table against the one before it, queued, not waited for)
+  if (e->chg.on) return changes_publish(e);  // (the change feed: this table against the one before it, queued, not waited for)
   return PM_OK;
 }
 

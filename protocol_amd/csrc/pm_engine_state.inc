@@ -1,11 +1,93 @@
 // pm_engine_state.inc — part of pm_engine.cpp (one translation unit; included in place): struct pm_engine: every table, mirror and scratch buffer of one engine.
+//
+// Every buffer, event and stream below is held by an owning type of pm_owned.h: `delete e` gives them all back, and a new
+// member costs its declaration and nothing else.
+
+// ---- assignment change feed (pm_engine_changes.inc): remembered identities, pending bits and rows of the workers [0, W);
+// everything behind W reads zero.  The drain's scratch: per-word prefix, the list, its count in pinned memory.
+struct ChangeFeed {
+  bool on = false;
+  bool resync = false;       // the remembered identities are meaningless: the next publish lists every row
+  bool resync_flag = false;  // ... and did: the next successful drain returns PM_CHANGES_RESYNC
+  bool list_valid = false;   // rows / n are the pending marks as they are now
+  uint32_t W = 0, n = 0;
+  DevBuf<ChangeIdent> ident;
+  DevBuf<uint8_t> what;
+  DevBuf<uint64_t> bitmap;
+  DevBuf<uint32_t> prefix;
+  DevBuf<pm_change_row> rows;
+  PinBuf<uint32_t> h_count;
+};
+
+// ---- liveness (pm_engine_liveness.inc): the ledger (status byte, unhealthy counter) of the workers [0, W); rows behind W hold
+// nothing yet (the init step writes them from the host's flags when the next liveness call sees them).  The last sweep's list:
+// bitmap, old-status side bytes, per-word prefix, the rows; its count and the census in pinned memory.
+struct Liveness {
+  bool on = false;
+  bool reinit = false;     // the row identities are gone (an upload that dropped the groups): initialise every row again
+  bool rows_host = false;  // h_rows holds the last sweep's list (an apply sweep brought it over)
+  uint32_t m = 0;          // missing_heartbeat_threshold
+  uint32_t W = 0, n = 0;
+  DevBuf<uint8_t> status, old;
+  DevBuf<uint32_t> counter;
+  DevBuf<uint64_t> bitmap;
+  DevBuf<uint32_t> prefix;
+  DevBuf<pm_live_row> rows;
+  DevBuf<uint32_t> census;  // PM_NS_N words
+  DevBuf<uint64_t> beat;    // the sweep's inputs: the beat column, behind it the pool bits
+  DevBuf<uint32_t> stage;   // set / get / init: indices, counters, packed status bytes
+  std::vector<pm_live_row> h_rows;
+  std::vector<uint32_t> h_stage;
+  PinBuf<uint32_t> h_count;  // [0] listed rows, [1, 1 + PM_NS_N) census
+};
+
+// ---- discovery sync (pm_engine_discovery.inc): scratch of one pm_discovery_sync, released with the liveness ledger
+struct Discovery {
+  DevBuf<uint64_t> in;      // the staged inputs: the rows (32 bytes each), behind them the endpoint column
+  DevBuf<uint32_t> work;    // pos_of_row [W] | base, ev_cnt, ev_fill [E each], cursor [1] | ev_off [E]
+  DevBuf<uint64_t> events;  // [2 n_rows]
+  DevBuf<pm_disc_result> out;
+  std::vector<uint64_t> h_in;
+  std::vector<pm_disc_result> h_out;
+  std::vector<uint32_t> h_seen;  // [W] the call (epoch) that last listed the row: a row listed twice
+  uint32_t epoch = 0;
+};
+
+// ---- metrics ledger (pm_engine_metrics.inc): a CSR over the internal rows [0, R) — 0 the manual row, w + 1 worker w — in two
+// buffers (cur is the table, the other one the next ingest's target); N its entries.  Rows behind R hold nothing yet: the next
+// metrics call extends the offsets.
+struct Metrics {
+  bool on = false;
+  bool reinit = false;        // an upload dropped the row identities: every worker row is emptied by the next metrics call
+  bool totals_valid = false;  // h_sum / h_cnt are the totals of the table as it stands
+  uint32_t cur = 0, R = 0, N = 0, n_series = 0;
+  DevBuf<uint32_t> off[2], ser[2];
+  DevBuf<double> val[2];
+  DevBuf<uint32_t> new_n;     // [R] a rebuild's row lengths (| PM_MX_TOUCHED)
+  DevBuf<uint32_t> stage;     // an ingest's touched rows (3 columns); a listing's rows, lengths and offsets
+  DevBuf<pm_mx_beat> beats;
+  DevBuf<pm_mx_entry> entries;
+  DevBuf<uint32_t> flag;      // [1] the count pass's "a row would pass the bound"
+  DevBuf<uint32_t> sort_ser[2], hist, hist_scan, cnt, gcfg;
+  DevBuf<double> sort_val[2], sum;
+  DevBuf<int32_t> gof;        // the join's inputs: the host's group_of, the groups' ids and configurations by slot
+  DevBuf<uint64_t> gid;
+  DevBuf<pm_mx_row> out;
+  PinBuf<uint32_t> h_pin;     // [0] a scan's total, [1] the bound flag, [2] the liveness hook's "a row was emptied"
+  std::vector<double> h_sum;
+  std::vector<uint32_t> h_cnt, h_stage;
+  std::vector<pm_mx_beat> h_beats;
+  std::vector<uint64_t> h_gid;
+  std::vector<uint32_t> h_gcfg;
+};
+
 struct pm_engine {
+  Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
-  hipStream_t stream = nullptr;        // the stream every kernel and copy of this engine goes to
-  hipStream_t stream_owned = nullptr;  // created with the engine; `stream` unless pm_set_stream handed one in
+  hipStream_t stream = nullptr;  // the stream every kernel and copy of this engine goes to: stream_owned unless pm_set_stream handed one in
   bool own_stream = true;
-  hipEvent_t ev[6]{};
-  hipEvent_t kev[6]{};  // kernel-only brackets: compat, carve, sweep
+  Event ev[6];
+  Event kev[6];  // kernel-only brackets: compat, carve, sweep
   hipEvent_t k_carve_begin = nullptr;  // the event in front of the carve's kernels: kev[2], or an event the caller has behind the compat sweep anyway (one barrier packet less)
   hipEvent_t k_compat_end = nullptr;  // the event behind this tick's compat kernel: kev[1], or the phase event handed to ensure_compat
   bool one_event_behind_carve = false;  // this tick's ev[2] stands for kev[3] and ev[3] too (pm_tick's queued-ahead path)
@@ -67,9 +149,8 @@ struct pm_engine {
   std::vector<uint32_t> site_pop;
   bool site_bits_dirty = false;
   DevBuf<unsigned char> d_row_stage;  // packed rows of pm_update_workers / pm_append_workers
-  unsigned char* h_row_pin = nullptr;  // ... and their pinned host staging (the copy is asynchronous: nothing waits for it)
-  size_t h_row_pin_cap = 0;
-  hipEvent_t ev_row_stage = nullptr;  // behind the last scatter that read the staging: asked (hipEventQuery) before the next one writes it
+  PinBuf<unsigned char> h_row_pin;    // ... and their pinned host staging (the copy is asynchronous: nothing waits for it)
+  Event ev_row_stage;  // behind the last scatter that read the staging: asked (hipEventQuery) before the next one writes it
 
   // ---- task table
   // The table lives in a fixed-capacity index space [0, t_cap) and is filled from the TOP: the used part is
@@ -116,8 +197,7 @@ struct pm_engine {
   // ... and of the flags column: rows whose flags changed since the last upload, while flags_delta_ok
   bool flags_delta_ok = false;
   std::vector<uint32_t> delta_flags;
-  uint32_t* h_delta_pin[2] = {nullptr, nullptr};  // pinned staging: [0] freed workers (indices), [1] flags ({index, value} pairs)
-  size_t h_delta_cap[2] = {0, 0};
+  PinBuf<uint32_t> h_delta_pin[2];  // pinned staging: [0] freed workers (indices), [1] flags ({index, value} pairs)
   DevBuf<uint32_t> d_delta[2];
   DevBuf<int32_t> d_group_of;
   DevBuf<uint32_t> d_g_cfg, d_g_n, d_g_off, d_g_task, d_g_task_next, d_members, d_by_rank, d_rank_in_group;
@@ -168,15 +248,13 @@ struct pm_engine {
   std::unordered_map<uint64_t, uint32_t> slot_of_id;    // pub_patch: group id -> slot under numbering slot_of_id_epoch
   uint64_t slot_of_id_epoch = ~0ull;
   // pinned staging for the group records a carve appended (absorbed into the host list by absorb_groups)
-  uint32_t* h_gstage = nullptr;
-  size_t h_gstage_cap = 0;
+  PinBuf<uint32_t> h_gstage;
   const uint32_t *ab_cfg_p = nullptr, *ab_n_p = nullptr, *ab_off_p = nullptr, *ab_mem_p = nullptr;  // the staged records absorb_groups reads
-  CarveStatus* h_status = nullptr;  // pinned: carve_finish_kernel mirrors the status block here (streaming carve)
-  hipEvent_t ev_groups = nullptr;
+  PinBuf<CarveStatus> h_status;  // pinned: carve_finish_kernel mirrors the status block here (streaming carve)
+  Event ev_groups;
   bool absorb_pending = false;
   uint32_t ab_g0 = 0, ab_g1 = 0, ab_m0 = 0, ab_m1 = 0, ab_solo = 0;
-  uint32_t* h_gtask_pinned = nullptr;
-  size_t h_gtask_cap = 0;
+  PinBuf<uint32_t> h_gtask_pinned;
   // set by publish_open for the run_match behind it: the claim writes the snapshot buffer and the task words itself
   pm_assignment* claim_h_table = nullptr;
   uint32_t* claim_h_gtask = nullptr;
@@ -185,7 +263,7 @@ struct pm_engine {
 
   PubTable pub[2];
   std::atomic<int> pub_cur{-1};
-  std::vector<uint64_t*> pub_retired;
+  std::vector<PinBuf<uint64_t>> pub_retired;  // replaced snapshot buffers: a reader may still hold one, so they live as long as the engine
   pm_stats last_stats{};
 
   // ---- diagnostics scratch (pm_engine_report.inc): the reports read the engine's tables and write only these
@@ -206,20 +284,6 @@ struct pm_engine {
   std::vector<uint32_t> h_probe_in;
   std::vector<uint64_t> h_probe_out;
 
-  // ---- assignment change feed (pm_engine_changes.inc): remembered identities, pending bits and rows of the workers [0, chg_W);
-  // everything behind chg_W reads zero.  The drain's scratch: per-word prefix, the list, its count in pinned memory.
-  bool chg_on = false;
-  bool chg_resync = false;       // the remembered identities are meaningless: the next publish lists every row
-  bool chg_resync_flag = false;  // ... and did: the next successful drain returns PM_CHANGES_RESYNC
-  bool chg_list_valid = false;   // d_chg_rows / chg_n are the pending marks as they are now
-  uint32_t chg_W = 0, chg_n = 0;
-  DevBuf<ChangeIdent> d_chg_ident;
-  DevBuf<uint8_t> d_chg_what;
-  DevBuf<uint64_t> d_chg_bitmap;
-  DevBuf<uint32_t> d_chg_prefix;
-  DevBuf<pm_change_row> d_chg_rows;
-  uint32_t* h_chg_count = nullptr;
-
   // ---- multi-GPU (pm_dist_*): this engine is rank `dist_rank` of `dist_world`, every rank holds the whole swarm
   uint32_t dist_rank = 0, dist_world = 1;
   std::vector<uint8_t> h_shard;        // owner rank of every worker
@@ -229,70 +293,19 @@ struct pm_engine {
   DevBuf<uint32_t> d_own_rows, d_xrow; // d_xrow[w] = shard * cap_t + index within the shard
   DevBuf<uint64_t> d_sel_own;
   DevBuf<pm_assignment> d_table_x;     // [world][cap_t] exchange buffer of published rows
-  pm::FormRun* form = nullptr;         // carve in progress (stepwise tick)
+  std::unique_ptr<pm::FormRun> form;   // carve in progress (stepwise tick)
   int dist_phase = 0;                  // 0 idle, 1 carving, 2 carve done, 3 match queued
   uint32_t dist_n_formed = 0, dist_n_merged = 0;
   uint32_t tick_host_resolved = 0, tick_carve_launches = 0, tick_carve_steps = 0;
   uint32_t tick_props = 0;
   uint64_t tick_prop_keys = 0;
   float k_ms_propose = 0;
-  std::vector<hipEvent_t> prop_ev;  // (start, stop) pairs of the proposer launches of the current poll interval
+  std::vector<Event> prop_ev;  // (start, stop) pairs of the proposer launches of the current poll interval
   size_t prop_ev_used = 0;
 
-  // ---- liveness (pm_engine_liveness.inc; behind everything else, so that every member above keeps its place): the ledger
-  // (status byte, unhealthy counter) of the workers [0, live_W); rows behind live_W hold nothing yet (the init step writes
-  // them from the host's flags when the next liveness call sees them).  The last sweep's list: bitmap, old-status side bytes,
-  // per-word prefix, the rows; its count and the census in pinned memory.
-  bool live_on = false;
-  bool live_reinit = false;     // the row identities are gone (an upload that dropped the groups): initialise every row again
-  bool live_rows_host = false;  // h_live_rows holds the last sweep's list (an apply sweep brought it over)
-  uint32_t live_m = 0;          // missing_heartbeat_threshold
-  uint32_t live_W = 0, live_n = 0;
-  DevBuf<uint8_t> d_live_status, d_live_old;
-  DevBuf<uint32_t> d_live_counter;
-  DevBuf<uint64_t> d_live_bitmap;
-  DevBuf<uint32_t> d_live_prefix;
-  DevBuf<pm_live_row> d_live_rows;
-  DevBuf<uint32_t> d_live_census;  // PM_NS_N words
-  DevBuf<uint64_t> d_live_beat;    // the sweep's inputs: the beat column, behind it the pool bits
-  DevBuf<uint32_t> d_live_stage;   // set / get / init: indices, counters, packed status bytes
-  std::vector<pm_live_row> h_live_rows;
-  std::vector<uint32_t> h_live_stage;
-  uint32_t* h_live_count = nullptr;  // [0] listed rows, [1, 1 + PM_NS_N) census
-
-  // ---- discovery sync (pm_engine_discovery.inc): scratch of one pm_discovery_sync, released with the ledger
-  DevBuf<uint64_t> d_disc_in;      // the staged inputs: the rows (32 bytes each), behind them the endpoint column
-  DevBuf<uint32_t> d_disc_work;    // pos_of_row [W] | base, ev_cnt, ev_fill [E each], cursor [1] | ev_off [E]
-  DevBuf<uint64_t> d_disc_events;  // [2 n_rows]
-  DevBuf<pm_disc_result> d_disc_out;
-  std::vector<uint64_t> h_disc_in;
-  std::vector<pm_disc_result> h_disc_out;
-  std::vector<uint32_t> h_disc_seen;  // [W] the call (disc_epoch) that last listed the row: a row listed twice
-  uint32_t disc_epoch = 0;
-
-  // ---- metrics ledger (pm_engine_metrics.inc): a CSR over the internal rows [0, mx_R) — 0 the manual row, w + 1 worker w —
-  // in two buffers (mx_cur is the table, the other one the next ingest's target); mx_N its entries.  Rows behind mx_R hold
-  // nothing yet: the next metrics call extends the offsets.
-  bool mx_on = false;
-  bool mx_reinit = false;        // an upload dropped the row identities: every worker row is emptied by the next metrics call
-  bool mx_totals_valid = false;  // h_mx_sum / h_mx_cnt are the totals of the table as it stands
-  uint32_t mx_cur = 0, mx_R = 0, mx_N = 0, mx_n_series = 0;
-  DevBuf<uint32_t> d_mx_off[2], d_mx_ser[2];
-  DevBuf<double> d_mx_val[2];
-  DevBuf<uint32_t> d_mx_new_n;     // [R] a rebuild's row lengths (| PM_MX_TOUCHED)
-  DevBuf<uint32_t> d_mx_stage;     // an ingest's touched rows (3 columns); a listing's rows, lengths and offsets
-  DevBuf<pm_mx_beat> d_mx_beats;
-  DevBuf<pm_mx_entry> d_mx_entries;
-  DevBuf<uint32_t> d_mx_flag;      // [1] the count pass's "a row would pass the bound"
-  DevBuf<uint32_t> d_mx_sort_ser[2], d_mx_hist, d_mx_hist_scan, d_mx_cnt, d_mx_gcfg;
-  DevBuf<double> d_mx_sort_val[2], d_mx_sum;
-  DevBuf<int32_t> d_mx_gof;        // the join's inputs: the host's group_of, the groups' ids and configurations by slot
-  DevBuf<uint64_t> d_mx_gid;
-  DevBuf<pm_mx_row> d_mx_out;
-  uint32_t* h_mx_pin = nullptr;    // pinned: [0] a scan's total, [1] the bound flag, [2] the liveness hook's "a row was emptied"
-  std::vector<double> h_mx_sum;
-  std::vector<uint32_t> h_mx_cnt, h_mx_stage;
-  std::vector<pm_mx_beat> h_mx_beats;
-  std::vector<uint64_t> h_mx_gid;
-  std::vector<uint32_t> h_mx_gcfg;
+  // ---- the optional ledgers (the structs above): switched off by assigning a fresh one
+  ChangeFeed chg;
+  Liveness live;
+  Discovery disc;
+  Metrics mx;
 };

@@ -69,7 +69,7 @@ static int32_t tasks_rebuild(pm_engine* e, uint32_t cap) {
   for (Group& g : e->groups)  // (a standing group's task is live: a deleted task dissolves the groups that held it)
     if (g.task != PM_NONE) g.task = remap(g.task);
   e->groups_dirty = true, e->groups_delta_ok = false;  // the device's claims are handles: the list goes up whole
-  e->chg_resync = true;  // (the change feed remembers handles too)
+  e->chg.resync = true;  // (the change feed remembers handles too)
   if (e->uid_map_valid)
     for (auto& kv : e->uid_to_u) kv.second = remap(kv.second);
   rc = tasks_push_range(e, new_lo, cap);
@@ -115,7 +115,7 @@ int32_t pm_upload_tasks(pm_engine* e, const pm_task_soa* t) {
   e->T = n;
   e->t_dead = 0;
   e->h_tprefix_valid = false;
-  e->chg_resync = true;  // (handles are dealt afresh: the change feed's remembered tasks name nothing)
+  e->chg.resync = true;  // (handles are dealt afresh: the change feed's remembered tasks name nothing)
   rc = tasks_push_range(e, clear_from, cap);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));  // pageable sources

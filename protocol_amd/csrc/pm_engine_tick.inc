@@ -127,7 +127,7 @@ int32_t pm_tick(pm_engine* e, pm_stats* stats) {
       return set_error(PM_ENODEV, "tick: the stream failed");
     }
     host_mark("tick: carve through");
-    const CarveStatus& hs = *e->h_status;
+    const CarveStatus& hs = *e->h_status.p;
     size_t solo = hs.n_solo;
     for (const Group& g : e->groups) solo += g.members.size() == 1 && !g.dead;
     const bool fits = hs.n_groups >= r.g0 && hs.n_groups - r.g0 <= r.stage_cap && hs.n_members >= r.m0 &&

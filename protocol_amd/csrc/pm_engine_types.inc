@@ -1,45 +1,4 @@
-// pm_engine_types.inc — part of pm_engine.cpp (one translation unit; included in place): DevBuf, Group, PubTable (inside namespace pm).
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  // capacity for n elements, keeping the first `keep` (device-to-device copy on `s` when the buffer moves)
-  hipError_t grow_keep(size_t n, size_t keep, hipStream_t s) {
-    if (n <= cap) return hipSuccess;
-    size_t want = n + n / 4 + 64;
-    T* q = nullptr;
-    hipError_t e = hipMalloc((void**)&q, want * sizeof(T));
-    if (e != hipSuccess) return e;
-    if (p && keep) {
-      e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);  // the old buffer is freed right below
-      if (e != hipSuccess) {
-        (void)hipFree(q);
-        return e;
-      }
-    }
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = want;
-    return hipSuccess;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
+// pm_engine_types.inc — part of pm_engine.cpp (one translation unit; included in place): SiteMap, Group, PubTable (inside namespace pm; DevBuf and the other owning types: pm_owned.h).
 // coordinates -> site id: an open-addressing table (linear probing, load <= 1/2) of the (lat, lon) bit patterns.  A node table
 // of 100k rows interns a thousand new rows per churn tick: a node-per-entry std::unordered_map spent 80 ns an insertion on
 // its allocations.
@@ -115,6 +74,7 @@ struct Group {
 struct PubTable {
   std::atomic<uint64_t> seq{0};
   std::atomic<uint64_t*> words{nullptr};  // 4 x u64 per row (pm_assignment is 32 bytes, 8-byte aligned)
+  PinBuf<uint64_t> own;                   // ... and their owner: what `words` points to (pub_buffer moves a replaced one to pub_retired)
   std::atomic<uint32_t> n{0};
   std::atomic<uint32_t> task_shift{0};  // added to every task position read from this buffer: tasks inserted in front
                                         // of the list since it was written (pm_tasks_insert_front) move them all alike

@@ -120,8 +120,8 @@ int32_t pm_upload_workers(pm_engine* e, const pm_worker_soa* w, uint32_t keep_gr
   if (rc) return rc;
   e->have_workers = true;
   if (!keep_groups || e->h_group_of.size() > n) {
-    e->live_reinit = true;  // (liveness: the row identities are gone, the next liveness call starts the ledger over)
-    e->mx_reinit = true;    // (metrics: the next metrics call empties every worker row)
+    e->live.reinit = true;  // (liveness: the row identities are gone, the next liveness call starts the ledger over)
+    e->mx.reinit = true;    // (metrics: the next metrics call empties every worker row)
     reset_groups_locked(e);
   } else {
     e->h_group_of.resize(n, -1);  // (rows behind the known ones are new: in no group)
@@ -184,19 +184,12 @@ static int32_t scatter_rows(pm_engine* e, const uint32_t* idx, const pm_worker_s
   // stream answers at once, and a delta arrives between two ticks
   // (asked through an event: the wait on an idle stream was 13 us of an append)
   host_mark("rows: host mirror written");
-  if (!e->ev_row_stage) HIPCHK(hipEventCreateWithFlags(&e->ev_row_stage, hipEventDisableTiming));
+  if (!e->ev_row_stage) HIPCHK(e->ev_row_stage.create(hipEventDisableTiming));
   else if (hipEventQuery(e->ev_row_stage) != hipSuccess) HIPCHK(hipStreamSynchronize(e->stream));
   host_mark("rows: staging free");
-  if (e->h_row_pin_cap < bytes) {
-    if (e->h_row_pin) (void)hipHostFree(e->h_row_pin);
-    e->h_row_pin = nullptr;
-    e->h_row_pin_cap = 0;
-    const size_t want = bytes + bytes / 2 + 4096;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&e->h_row_pin), want, hipHostMallocDefault));
-    e->h_row_pin_cap = want;
-  }
-  double* hd = reinterpret_cast<double*>(e->h_row_pin);
-  uint32_t* hu = reinterpret_cast<uint32_t*>(e->h_row_pin + size_t(n) * 16);
+  HIPCHK(e->h_row_pin.ensure(bytes, bytes + bytes / 2 + 4096));
+  double* hd = reinterpret_cast<double*>(e->h_row_pin.p);
+  uint32_t* hu = reinterpret_cast<uint32_t*>(e->h_row_pin.p + size_t(n) * 16);
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t w = idx[k];
     hd[k] = e->h_lat[w];
@@ -213,7 +206,7 @@ static int32_t scatter_rows(pm_engine* e, const uint32_t* idx, const pm_worker_s
     hu[9 * size_t(n) + k] = e->h_site[w];
   }
   HIPCHK(e->d_row_stage.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(e->d_row_stage.p, e->h_row_pin, bytes, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(e->d_row_stage.p, e->h_row_pin.p, bytes, hipMemcpyHostToDevice, e->stream));
   RowUpdateArgs a{};
   a.n = n;
   a.lat_in = reinterpret_cast<const double*>(e->d_row_stage.p);

@@ -857,6 +857,17 @@ class Engine:
         check(L.pm_debug_delta_pushes(self._h, C.byref(n)))
         return n.value
 
+    @staticmethod
+    def debug_live_allocations() -> tuple:
+        """(device bytes, pinned host bytes, events + streams) the engines of this process hold from the HIP runtime right
+        now (include/pm_engine_debug.h): a destroyed engine gives back all it took"""
+        L = lib()
+        L.pm_debug_live_allocations.argtypes = [C.POINTER(C.c_uint64)]
+        L.pm_debug_live_allocations.restype = None
+        out = (C.c_uint64 * 3)()
+        L.pm_debug_live_allocations(out)
+        return tuple(int(v) for v in out)
+
     def debug_task_space(self) -> dict:
         """the task index space, the group list and the snapshot buffers (include/pm_engine_debug.h: pm_debug_carve_prof
         words 88..96)"""

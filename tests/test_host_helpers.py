@@ -34,14 +34,14 @@ def test_library_exports_every_declared_symbol():
 
 def test_library_exports_every_declared_debug_hook():
     """include/pm_engine_debug.h: the test hooks and counters tests/, tools/ and bench.py call — since the distance-key
-    hook (tests/test_gpu_distance_key.py) thirteen of them.  Not part of the drop-in boundary (the Rust shim binds none of
+    hook (tests/test_gpu_distance_key.py) thirteen of them, with the live-allocation counter fourteen.  Not part of the drop-in boundary (the Rust shim binds none of
     them), but exported by the shipped library, with the declared arity."""
     hdr = open(os.path.join(ROOT, "include", "pm_engine_debug.h")).read()
     protos = _c_prototypes(hdr)
     assert set(protos) == {"pm_debug_carve_prof", "pm_debug_stream_trace", "pm_debug_mem_lists_above", "pm_debug_prune_mode",
                            "pm_debug_hbm_triad", "pm_debug_stream_abort_after", "pm_debug_merge_streamed", "pm_debug_delta_pushes",
                            "pm_debug_row_networks", "pm_debug_row_records", "pm_debug_chain_batches", "pm_debug_park_records",
-                           "pm_debug_distance_keys"}
+                           "pm_debug_distance_keys", "pm_debug_live_allocations"}
     L = E.lib()
     for name in protos:
         assert hasattr(L, name), f"{name} declared in pm_engine_debug.h but not exported"
@@ -389,6 +389,28 @@ def test_member_list_of_a_group_record(tmp_path):
     assert out.returncode == 0 and "members_test ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_owning_types_of_the_engine(tmp_path):
+    """protocol_amd/csrc/pm_owned.h (DevBuf, PinBuf, Event, Stream and the live-allocation counter: what lets `delete e` be the
+    engine's whole teardown) over stubs of the HIP runtime calls — tests/cpp/owned_test.cpp, a stand-alone program built here
+    with g++ (address + UB sanitizers when they link); it links against no HIP library, only the runtime's C header is read."""
+    import shutil
+    import subprocess
+    from protocol_amd import build as B
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    if not os.path.exists(os.path.join(B.ROCM, "include", "hip", "hip_runtime_api.h")):
+        pytest.skip("no HIP runtime header")
+    src = os.path.join(ROOT, "tests", "cpp", "owned_test.cpp")
+    exe = str(tmp_path / "owned_test")
+    base = [gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "protocol_amd", "csrc"),
+            "-isystem", os.path.join(B.ROCM, "include"), src, "-o", exe]
+    if subprocess.run(base + ["-fsanitize=address,undefined"], capture_output=True).returncode != 0:
+        subprocess.check_call(base)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "owned_test ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_product_library_is_the_build_the_gpu_suite_ran_on():
     """profiles/r*_verified_binary.txt (the newest) holds the sha256 of the six sections of libpm_engine.so that carry
     code and data — the gfx950 code object's .text / .rodata / .note, the host's .text / .rodata / .data — as they were
@@ -486,3 +508,36 @@ def test_step_rule_is_written_once():
     outside = val.replace(block, "") + stream
     assert not re.findall(r"%\s*(?:dbg_every|p\.debug_uncertain_every|\w*every\w*)", outside)
     assert len(re.findall(r"%\s*every\b", block)) == 2  # step_forced and the commits in front of it
+
+
+def test_engine_resources_are_taken_and_given_back_in_one_header():
+    """What the engine holds from the HIP runtime — device memory, pinned memory, events, streams — is taken and given back
+    by the owning types of pm_owned.h and nowhere else: no engine file calls the runtime's allocating or freeing functions, so
+    there is no teardown list to keep.  And every file of build.py's HEADERS that pm_engine.cpp includes is included once (no
+    file read twice under a macro).  Text only: nothing is compiled."""
+    import glob
+    from protocol_amd import build as B
+    assert "pm_owned.h" in B.HEADERS
+    calls = re.compile(r"\b(hipMalloc\w*|hipFree\w*|hipHostMalloc|hipHostFree|hipHostAlloc|hipHostRegister|hipHostUnregister|"
+                       r"hipEventCreate\w*|hipEventDestroy|hipStreamCreate\w*|hipStreamDestroy)\s*\(")
+    files = sorted(glob.glob(os.path.join(B.CSRC, "pm_engine*.inc"))) + [os.path.join(B.CSRC, "pm_engine.cpp")]
+    assert len(files) > 20
+    bad = []
+    for f in files:
+        for i, line in enumerate(open(f).read().split("\n")):
+            if calls.search(line):
+                bad.append(f"{os.path.basename(f)}:{i + 1}: {line.strip()}")
+    assert not bad, bad
+    owned = open(os.path.join(B.CSRC, "pm_owned.h")).read()
+    for name in ("hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree", "hipEventCreateWithFlags", "hipEventDestroy",
+                 "hipStreamCreateWithFlags", "hipStreamDestroy"):
+        assert re.search(r"\b" + name + r"\b", owned), name
+    main = open(os.path.join(B.CSRC, "pm_engine.cpp")).read()
+    included = re.findall(r'^\s*#\s*include\s+"([^"]+)"', main, flags=re.M)
+    engine_files = [os.path.basename(f) for f in files[:-1]]
+    for name in engine_files:
+        assert name in B.HEADERS, name
+    for name in B.HEADERS:
+        if name in included or name in engine_files:
+            assert included.count(name) == 1, (name, included.count(name))
+    assert not re.search(r"\bPM_\w+_ABI\b", "".join(open(f).read() for f in files))
