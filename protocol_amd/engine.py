@@ -85,6 +85,7 @@ mx_entry_dt = np.dtype([("series", "<u4"), ("flags", "<u4"), ("value", "<f8")])
 mx_row_dt = np.dtype([("row", "<u4"), ("series", "<u4"), ("value", "<f8"), ("group_id", "<u8"), ("config", "<u4"), ("_pad", "<u4")])
 assert mx_beat_dt.itemsize == 16 and mx_entry_dt.itemsize == 16 and mx_row_dt.itemsize == 32
 MX_MANUAL, MX_ROW_MAX = 0xFFFFFFFF, 1024
+MX_CHUNK = 1024    # PM_MX_CHUNK (csrc/pm_device.h): the entries of one radix chunk of pm_metrics_totals
 MXB_REPLACE, MXB_MERGE, MXB_DELETE = 0, 1, 2
 MXF_MAX = 1
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),

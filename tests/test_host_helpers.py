@@ -510,6 +510,26 @@ def test_step_rule_is_written_once():
     assert len(re.findall(r"%\s*every\b", block)) == 2  # step_forced and the commits in front of it
 
 
+def test_metrics_constants_are_the_device_headers():
+    """The two sizes of the metrics ledger that the Python side and the tests compute with are the kernels' own: MX_ROW_MAX is
+    PM_MX_ROW_MAX (include/pm_engine.h, which pm_device.h includes: the fold's LDS row) and MX_CHUNK is PM_MX_CHUNK
+    (pm_device.h: the radix chunk).  The scan's tile is a literal of mx_scan_kernel — 1024 threads, four words each — which
+    tests/test_gpu_metrics_edges.py names once.  Text only: nothing is compiled."""
+    from protocol_amd import build as B
+    dev = open(os.path.join(B.CSRC, "pm_device.h")).read()
+    assert re.search(r'^\s*#\s*include\s+"pm_engine.h"', dev, flags=re.M)
+    both = dev + open(os.path.join(ROOT, "include", "pm_engine.h")).read()
+    value = lambda name: int(re.search(r"\b" + name + r"\b\s*=?\s*(\d+)u?\b", both).group(1))
+    assert len(re.findall(r"\bPM_MX_ROW_MAX\s+\d", both)) == 1 and len(re.findall(r"\bPM_MX_CHUNK\s*=", dev)) == 1
+    assert E.MX_ROW_MAX == value("PM_MX_ROW_MAX") and E.MX_CHUNK == value("PM_MX_CHUNK")
+    assert E.MX_ROW_MAX % 64 == 0 and E.MX_CHUNK % 64 == 0          # whole 64-slot rounds, in the fold and in the scatter
+    kernels = open(os.path.join(B.CSRC, "pm_metrics.inc")).read()
+    scan = kernels[kernels.index("void mx_scan_kernel("):kernels.index("void mx_copy_kernel(")]
+    assert "base += 4096u" in scan and "tid * 4u" in scan and "__launch_bounds__(1024) void mx_scan_kernel(" in kernels
+    edges = open(os.path.join(ROOT, "tests", "test_gpu_metrics_edges.py")).read()
+    assert re.search(r"^SCAN_TILE = 4096\b.*mx_scan_kernel", edges, flags=re.M) and re.search(r"^CHUNK = E\.MX_CHUNK\b", edges, flags=re.M)
+
+
 def test_engine_resources_are_taken_and_given_back_in_one_header():
     """What the engine holds from the HIP runtime — device memory, pinned memory, events, streams — is taken and given back
     by the owning types of pm_owned.h and nowhere else: no engine file calls the runtime's allocating or freeing functions, so
