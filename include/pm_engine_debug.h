@@ -81,6 +81,15 @@ int32_t pm_debug_park_records(pm_engine* e, unsigned long long* out, uint32_t ca
 int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave,
                               uint32_t slot_bits, uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches);
 
+/* The same rows three ways — (0) the serial insertion, (1) the networks' out-of-line copy, (2) their inline copy, which the
+ * streaming carve's sweep runs — and what near_row_finish makes of each (tests/test_gpu_row_certificates.py holds all of it to a
+ * brute-force reference).  n_waves: a multiple of four, at most 4096; slot_bits: 13 or 18, the widths rows run at.  Per wave w and row r, at [w][r]: rows_out[64] the keys;
+ * track_out[5] = tau, tau_hi, m1, m2, s1; and for K = 1 .. 63, at [K - 1], flags_out = the flags word of
+ * near_row_finish(K, slot_bits, tie_band) and mine_out[64] = the lanes' entries.  mismatches: as above, rows 0 and 1. */
+int32_t pm_debug_row_certificates(pm_engine* e, const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave,
+                                  uint32_t slot_bits, uint64_t ulps, uint32_t upto, double tie_band, uint64_t* rows_out,
+                                  uint64_t* track_out, uint32_t* flags_out, uint64_t* mine_out, uint32_t* mismatches);
+
 /* The carve's distance key through the device functions the carve runs (tests/test_gpu_distance_key.py).  mode 0: in[5n] =
  * lat[2n] (the n first points, then the n second points), lon[2n], slot[n] (integers as f64); geo_kernel gives each point its
  * cos(lat) and unit vector, and per pair out[20n] holds, twenty f64 a pair: sin_band(dlat / 2), sin_band(dlon / 2), cos(lat)

@@ -521,7 +521,9 @@ void launch_triad(const double* b, const double* c, double* a, size_t n, hipStre
 hipError_t launch_row_bench(const CarveArgs* d_args, uint32_t seed, uint32_t ci, uint32_t reps, uint32_t mode, unsigned long long* d_out, hipStream_t s);
 #endif
 void launch_row_network_test(const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave, uint32_t slot_bits,
-                             uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches, hipStream_t s);
+                             uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches, hipStream_t s, double tie_band = 0.0,
+                             uint64_t* cert_rows = nullptr, uint64_t* cert_track = nullptr, uint32_t* cert_flags = nullptr,
+                             uint64_t* cert_mine = nullptr);  // (the cert_* of pm_debug_row_certificates: all four or none)
 // debug (pm_debug_distance_keys): the distance key of n pairs through the carve's device functions; PM_DK_WORDS f64 per pair
 static constexpr uint32_t PM_DK_WORDS = 20;
 void launch_distance_key_test(const double* in, const double* geo, uint32_t n, uint32_t mode, double* out, hipStream_t s);

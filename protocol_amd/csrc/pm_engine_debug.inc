@@ -186,6 +186,37 @@ int32_t pm_debug_row_networks(pm_engine* e, const uint64_t* keys, const uint32_t
   return PM_OK;
 }
 
+// debug (include/pm_engine_debug.h): the same kernel with a third row through the networks' inline copy, and everything the three
+// rows hold and near_row_finish says about them at every K, for the caller's own reference (tests/test_gpu_row_certificates.py)
+int32_t pm_debug_row_certificates(pm_engine* e, const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave,
+                                  uint32_t slot_bits, uint64_t ulps, uint32_t upto, double tie_band, uint64_t* rows_out,
+                                  uint64_t* track_out, uint32_t* flags_out, uint64_t* mine_out, uint32_t* mismatches) {
+  if (!e || !keys || !sites || !rows_out || !track_out || !flags_out || !mine_out || !mismatches || !n_waves || (n_waves & 3u) ||
+      n_waves > 4096u || !n_per_wave || (slot_bits != PM_CARVE_SLOT_BITS && slot_bits != PM_CARVE_SLOT_BITS_BIG))
+    return set_error(PM_EINVAL, "row certificates: null argument, not 4 .. 4096 waves in fours, or a slot width rows do not run at");
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(hipSetDevice(e->cfg.device));
+  const size_t nk = size_t(n_waves) * n_per_wave, ns = size_t(1) << slot_bits, nr = size_t(n_waves) * 3;
+  DevBuf<uint64_t> d_k, d_rows, d_cr, d_ct, d_cm;
+  DevBuf<uint32_t> d_s, d_m, d_cf;
+  if (d_k.ensure(nk) != hipSuccess || d_rows.ensure(size_t(n_waves) * 64) != hipSuccess || d_s.ensure(ns) != hipSuccess ||
+      d_m.ensure(2) != hipSuccess || d_cr.ensure(nr * 64) != hipSuccess || d_ct.ensure(nr * 5) != hipSuccess ||
+      d_cf.ensure(nr * PM_PROP_KMAX) != hipSuccess || d_cm.ensure(nr * PM_PROP_KMAX * 64) != hipSuccess)
+    return set_error(PM_ENOMEM, "row certificate test buffers");
+  (void)hipMemcpyAsync(d_k.p, keys, nk * 8, hipMemcpyHostToDevice, e->stream);
+  (void)hipMemcpyAsync(d_s.p, sites, ns * 4, hipMemcpyHostToDevice, e->stream);
+  (void)hipMemsetAsync(d_m.p, 0, 8, e->stream);
+  launch_row_network_test(d_k.p, d_s.p, n_waves, n_per_wave, slot_bits, ulps, upto, d_rows.p, d_m.p, e->stream, tie_band, d_cr.p, d_ct.p,
+                          d_cf.p, d_cm.p);
+  (void)hipMemcpyAsync(rows_out, d_cr.p, nr * 64 * 8, hipMemcpyDeviceToHost, e->stream);
+  (void)hipMemcpyAsync(track_out, d_ct.p, nr * 5 * 8, hipMemcpyDeviceToHost, e->stream);
+  (void)hipMemcpyAsync(flags_out, d_cf.p, nr * PM_PROP_KMAX * 4, hipMemcpyDeviceToHost, e->stream);
+  (void)hipMemcpyAsync(mine_out, d_cm.p, nr * PM_PROP_KMAX * 64 * 8, hipMemcpyDeviceToHost, e->stream);
+  (void)hipMemcpyAsync(mismatches, d_m.p, 8, hipMemcpyDeviceToHost, e->stream);
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return set_error(PM_ENODEV, "row certificate test");
+  return PM_OK;
+}
+
 // debug (include/pm_engine_debug.h): the distance key of n pairs by geo_kernel and the carve's own device functions
 int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out) {
   if (!e || !out || mode > 2u) return set_error(PM_EINVAL, "null argument");

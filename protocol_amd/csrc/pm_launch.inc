@@ -13,9 +13,10 @@ void launch_triad(const double* b, const double* c, double* a, size_t n, hipStre
   hipLaunchKernelGGL(triad_kernel, dim3(256 * 32), dim3(256), 0, s, b, c, a, n);
 }
 void launch_row_network_test(const uint64_t* keys, const uint32_t* sites, uint32_t n_waves, uint32_t n_per_wave, uint32_t slot_bits,
-                             uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches, hipStream_t s) {
+                             uint64_t ulps, uint32_t upto, uint64_t* rows_out, uint32_t* mismatches, hipStream_t s, double tie_band,
+                             uint64_t* cert_rows, uint64_t* cert_track, uint32_t* cert_flags, uint64_t* cert_mine) {
   hipLaunchKernelGGL(row_network_test_kernel, dim3(n_waves / 4u), dim3(256), 0, s, keys, sites, n_per_wave, slot_bits, ulps, upto, rows_out,
-                     mismatches);
+                     mismatches, tie_band, RowCertOut{cert_rows, cert_track, cert_flags, cert_mine});
 }
 void launch_distance_key_test(const double* in, const double* geo, uint32_t n, uint32_t mode, double* out, hipStream_t s) {
   if (n == 0) return;

@@ -960,16 +960,49 @@ __device__ __noinline__ uint32_t carve_prop_limit(const CarveArgs& p, BlockRed& 
 }
 
 
+// debug (pm_debug_row_certificates): what a finished row is and what near_row_finish makes of it, for the host to hold to a
+// reference of its own.  Per wave and row: the 64 keys; tau, tau_hi, m1, m2, s1; and for every K = 1 .. PM_PROP_KMAX the flags
+// word and the lanes' entries.  `p` is all zeros but the site table: near_row_finish reads nothing else of it.
+// The slot width reaches near_row_finish and the networks' inline copy as the product's kernels hand it over — one of the two
+// constants rows run at (row_cert_sb; the entry point refuses any other) — and not as a free kernel argument: the compiler
+// carries an argument's range into a function all of whose callers agree on it, and with a third caller that knows nothing of
+// the width carve_stream_kernel and carve_propose_kernel came out as other code, with more registers spilled.  With this the two
+// have the parent's instructions (the propose kernel up to register numbers).
+__device__ __forceinline__ uint32_t row_cert_sb(uint32_t SB) { return SB > PM_CARVE_SLOT_BITS ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS; }
+struct RowCertOut {
+  uint64_t* rows;   // [n_waves][3][64]
+  uint64_t* track;  // [n_waves][3][5]
+  uint32_t* flags;  // [n_waves][3][PM_PROP_KMAX]
+  uint64_t* mine;   // [n_waves][3][PM_PROP_KMAX][64]
+};
+__device__ __noinline__ void row_cert_emit(const NearRow q, const uint32_t* sites, uint32_t SB, double tie_band, uint32_t lane, size_t at,
+                                           const RowCertOut o) {
+  CarveArgs p = {};
+  p.cc_site = const_cast<uint32_t*>(sites);
+  o.rows[at * 64u + lane] = q.key;
+  if (lane < 5u) o.track[at * 5u + lane] = lane == 0u ? q.tau : lane == 1u ? q.tau_hi : lane == 2u ? q.m1 : lane == 3u ? q.m2 : (uint64_t)q.s1;
+#pragma unroll 1
+  for (uint32_t K = 1u; K <= PM_PROP_KMAX; ++K) {
+    uint64_t mine;
+    const uint32_t meta = near_row_finish(p, q, true, K, row_cert_sb(SB), tie_band, lane, &mine);
+    o.mine[(at * PM_PROP_KMAX + (K - 1u)) * 64u + lane] = mine;
+    if (lane == 0u) o.flags[at * PM_PROP_KMAX + (K - 1u)] = meta;
+  }
+}
 // debug (pm_debug_row_networks): one wave per block builds the row of its n_per_wave keys twice — stride by stride
 // through the insertion, and four strides at a time through the networks for the first `upto` keys — and compares the
 // registers lane by lane and what the trackers answer at the end (for every site the last entry could have).  rows_out
-// gets the second row (the host compares it with a sort of its own).
+// gets the second row (the host compares it with a sort of its own).  With `cert` (pm_debug_row_certificates) a third row goes
+// through the networks' inline copy, as the streaming carve's sweep has it, and all three are written out (row_cert_emit).
 __global__ __launch_bounds__(256) void row_network_test_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ sites,
                                                               uint32_t n_per_wave, uint32_t SB, uint64_t ulps, uint32_t upto,
-                                                              uint64_t* __restrict__ rows_out, uint32_t* __restrict__ mismatches) {
+                                                              uint64_t* __restrict__ rows_out, uint32_t* __restrict__ mismatches,
+                                                              double tie_band, RowCertOut cert) {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, w = blockIdx.x * 4u + wave;  // (n_waves is a multiple of four)
   const uint64_t* kw = keys + (size_t)w * n_per_wave;
   NearRow a = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu}, b = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
+  NearRow c = {~0ull, ~0ull, ~0ull, ~0ull, ~0ull, 0xFFFFFFFFu};
+  const bool with_cert = cert.rows != nullptr;  // (the same for every wave of the launch)
   __shared__ uint64_t pack_lds[4u * NET_PACK_KEYS];  // (side by side, as in the row-making workgroups)
   const LaneNet ln = lane_net(lane, pack_lds + wave * NET_PACK_KEYS);
   const auto cs = G(sites);
@@ -991,6 +1024,19 @@ __global__ __launch_bounds__(256) void row_network_test_kernel(const uint64_t* _
 #pragma unroll
       for (uint32_t v = 0; v < 4u; ++v) near_row_offer(b, kk[v], ss[v], cs, SB, ulps);
     }
+    if (with_cert) {
+      if (k0 < upto) {
+        near_row_offer_bulk<4u, true>(c, kk, ss, sites, row_cert_sb(SB), ulps, ln);
+      } else {
+#pragma unroll
+        for (uint32_t v = 0; v < 4u; ++v) near_row_offer(c, kk[v], ss[v], cs, SB, ulps);
+      }
+    }
+  }
+  if (with_cert) {
+    row_cert_emit(a, sites, SB, tie_band, lane, (size_t)w * 3u, cert);
+    row_cert_emit(b, sites, SB, tie_band, lane, (size_t)w * 3u + 1u, cert);
+    row_cert_emit(c, sites, SB, tie_band, lane, (size_t)w * 3u + 2u, cert);
   }
   uint32_t bad = __ballot(a.key != b.key) ? 1u : 0u;
   if (a.tau != b.tau || a.tau_hi != b.tau_hi) bad |= 2u;

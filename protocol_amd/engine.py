@@ -86,6 +86,15 @@ mx_row_dt = np.dtype([("row", "<u4"), ("series", "<u4"), ("value", "<f8"), ("gro
 assert mx_beat_dt.itemsize == 16 and mx_entry_dt.itemsize == 16 and mx_row_dt.itemsize == 32
 MX_MANUAL, MX_ROW_MAX = 0xFFFFFFFF, 1024
 MX_CHUNK = 1024    # PM_MX_CHUNK (csrc/pm_device.h): the entries of one radix chunk of pm_metrics_totals
+# neighbour rows (csrc/pm_device.h, csrc/pm_propose.inc; tests/test_host_helpers.py holds each to the source): the flags word of
+# near_row_finish, the two geometries rows run at (slot bits, certificate band, window), the regimes of near_row_bulk4_body
+ROW_SAFE, ROW_TAIL_CLEAR, ROW_CLEAN, ROW_TAIL_OK, ROW_COMPLETE = 1 << 27, 1 << 28, 1 << 29, 1 << 30, 1 << 31
+PROP_KMAX = 63
+A_MAX_SAFE = 1.0 - 1.0 / 1048576.0
+ROW_SLOT_BITS, ROW_SLOT_BITS_BIG = 13, 18
+TIE_BAND, TIE_BAND_BIG = 2.0 ** -36, 2.0 ** -31
+WINDOW_ULPS, WINDOW_ULPS_BIG = 1 << 20, 1 << 25
+NET_SERIAL_MAX, NET_PACK_KEYS = 16, 128
 MXB_REPLACE, MXB_MERGE, MXB_DELETE = 0, 1, 2
 MXF_MAX = 1
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
@@ -897,6 +906,32 @@ class Engine:
         check(L.pm_debug_row_networks(self._h, keys.ctypes.data, sites.ctypes.data, n_waves, n_per_wave, slot_bits, ulps, upto,
                                       rows.ctypes.data, mism))
         return int(mism[0]), int(mism[1]), rows
+
+    def debug_row_certificates(self, keys, sites, n_per_wave: int, slot_bits: int, ulps: int, upto: int, tie_band: float) -> dict:
+        """test hook (include/pm_engine_debug.h): three rows per wave from keys[n_waves * n_per_wave] — by the insertion, by the
+        networks out of line and by their inline copy — and near_row_finish of each at every K = 1 .. PROP_KMAX ->
+        rows u64[n_waves, 3, 64], tau / tau_hi / m1 / m2 u64[n_waves, 3], s1 u32[n_waves, 3], flags u32[n_waves, 3, PROP_KMAX],
+        mine u64[n_waves, 3, PROP_KMAX, 64], mismatch (bits, rows that differ) of the first two as debug_row_networks has them"""
+        import numpy as np
+        L = lib()
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        sites = np.ascontiguousarray(sites, dtype=np.uint32)
+        assert keys.size % n_per_wave == 0 and sites.size == 1 << slot_bits
+        n_waves = keys.size // n_per_wave
+        rows = np.zeros((n_waves, 3, 64), dtype=np.uint64)
+        track = np.zeros((n_waves, 3, 5), dtype=np.uint64)
+        flags = np.zeros((n_waves, 3, PROP_KMAX), dtype=np.uint32)
+        mine = np.zeros((n_waves, 3, PROP_KMAX, 64), dtype=np.uint64)
+        mism = (C.c_uint32 * 2)()
+        L.pm_debug_row_certificates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint32)]
+        L.pm_debug_row_certificates.restype = C.c_int32
+        check(L.pm_debug_row_certificates(self._h, keys.ctypes.data, sites.ctypes.data, n_waves, n_per_wave, slot_bits, ulps, upto,
+                                          tie_band, rows.ctypes.data, track.ctypes.data, flags.ctypes.data, mine.ctypes.data, mism))
+        return {"rows": rows, "tau": track[:, :, 0].copy(), "tau_hi": track[:, :, 1].copy(), "m1": track[:, :, 2].copy(),
+                "m2": track[:, :, 3].copy(), "s1": track[:, :, 4].astype(np.uint32), "flags": flags, "mine": mine,
+                "mismatch": (int(mism[0]), int(mism[1]))}
 
     def debug_distance_keys(self, lat1, lon1, lat2, lon2, slots=None):
         """test hook (include/pm_engine_debug.h): the carve's distance key of the pairs (lat1, lon1) - (lat2, lon2) through the

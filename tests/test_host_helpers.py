@@ -34,14 +34,15 @@ def test_library_exports_every_declared_symbol():
 
 def test_library_exports_every_declared_debug_hook():
     """include/pm_engine_debug.h: the test hooks and counters tests/, tools/ and bench.py call — since the distance-key
-    hook (tests/test_gpu_distance_key.py) thirteen of them, with the live-allocation counter fourteen.  Not part of the drop-in boundary (the Rust shim binds none of
+    hook (tests/test_gpu_distance_key.py) thirteen of them, with the live-allocation counter fourteen, with the row
+    certificates' hook (tests/test_gpu_row_certificates.py) fifteen.  Not part of the drop-in boundary (the Rust shim binds none of
     them), but exported by the shipped library, with the declared arity."""
     hdr = open(os.path.join(ROOT, "include", "pm_engine_debug.h")).read()
     protos = _c_prototypes(hdr)
     assert set(protos) == {"pm_debug_carve_prof", "pm_debug_stream_trace", "pm_debug_mem_lists_above", "pm_debug_prune_mode",
                            "pm_debug_hbm_triad", "pm_debug_stream_abort_after", "pm_debug_merge_streamed", "pm_debug_delta_pushes",
                            "pm_debug_row_networks", "pm_debug_row_records", "pm_debug_chain_batches", "pm_debug_park_records",
-                           "pm_debug_distance_keys", "pm_debug_live_allocations"}
+                           "pm_debug_distance_keys", "pm_debug_live_allocations", "pm_debug_row_certificates"}
     L = E.lib()
     for name in protos:
         assert hasattr(L, name), f"{name} declared in pm_engine_debug.h but not exported"
@@ -528,6 +529,43 @@ def test_metrics_constants_are_the_device_headers():
     assert "base += 4096u" in scan and "tid * 4u" in scan and "__launch_bounds__(1024) void mx_scan_kernel(" in kernels
     edges = open(os.path.join(ROOT, "tests", "test_gpu_metrics_edges.py")).read()
     assert re.search(r"^SCAN_TILE = 4096\b.*mx_scan_kernel", edges, flags=re.M) and re.search(r"^CHUNK = E\.MX_CHUNK\b", edges, flags=re.M)
+
+
+def test_row_constants_are_the_device_sources():
+    """What tests/near_row_cases.py and tests/test_gpu_row_certificates.py compute with — the bits of a row's flags word, the
+    longest row, the antipode bound, the two geometries rows run at (slot bits, certificate band, window) and the regime edges of
+    near_row_bulk4_body — are the constants of pm_device.h and pm_propose.inc.  Text only: nothing is compiled."""
+    from protocol_amd import build as B
+    dev = open(os.path.join(B.CSRC, "pm_device.h")).read()
+    prop = open(os.path.join(B.CSRC, "pm_propose.inc")).read()
+
+    def rhs(name, text=dev):
+        found = re.findall(r"^static constexpr \w+ " + name + r" = ([^;]+);", text, flags=re.M)
+        assert len(found) == 1, (name, found)
+        return found[0].strip()
+
+    for name, want in (("SAFE", E.ROW_SAFE), ("TAIL_CLEAR", E.ROW_TAIL_CLEAR), ("CLEAN", E.ROW_CLEAN), ("TAIL_OK", E.ROW_TAIL_OK),
+                       ("COMPLETE", E.ROW_COMPLETE)):
+        m = re.fullmatch(r"1u << (\d+)", rhs("PM_ROW_" + name))
+        assert m and 1 << int(m.group(1)) == want, name
+    assert int(rhs("PM_PROP_KMAX")) == E.PROP_KMAX == 63
+    assert rhs("PM_A_MAX_SAFE") == "1.0 - 1.0 / 1048576.0" and E.A_MAX_SAFE == 1.0 - 1.0 / 1048576.0
+    assert (int(rhs("PM_CARVE_SLOT_BITS")), int(rhs("PM_CARVE_SLOT_BITS_BIG"))) == (E.ROW_SLOT_BITS, E.ROW_SLOT_BITS_BIG)
+    for name, want in (("PM_TIE_BAND", E.TIE_BAND), ("PM_TIE_BAND_BIG", E.TIE_BAND_BIG)):
+        m = re.fullmatch(r"1\.0 / (\d+)\.0", rhs(name))
+        assert m and 1.0 / int(m.group(1)) == want, name
+    # the window and the geometry's pick, in carve_propose_kernel: big lists 2^25, small ones 2^20
+    m = re.findall(r"const uint64_t WINDOW_ULPS = n_list > PM_CARVE_SLOTS \? \(1ull << (\d+)\) : \(1ull << (\d+)\);", prop)
+    assert len(m) == 1 and (1 << int(m[0][0]), 1 << int(m[0][1])) == (E.WINDOW_ULPS_BIG, E.WINDOW_ULPS)
+    assert "const uint32_t SB = n_list > PM_CARVE_SLOTS ? PM_CARVE_SLOT_BITS_BIG : PM_CARVE_SLOT_BITS;" in prop
+    assert "const double TIE_BAND = n_list > PM_CARVE_SLOTS ? PM_TIE_BAND_BIG : PM_TIE_BAND;" in prop
+    m = re.findall(r"^#define NET_SERIAL_MAX (\d+)u\b", prop, flags=re.M)
+    assert len(m) == 1 and int(m[0]) == E.NET_SERIAL_MAX
+    m = re.findall(r"^#define NET_PACK_KEYS (\d+)u\b", prop, flags=re.M)
+    assert len(m) == 1 and int(m[0]) == E.NET_PACK_KEYS
+    body = prop[prop.index("NearRow near_row_bulk4_body("):prop.index("NearRow near_row_bulk4(")]
+    for piece in ("if (n_ent <= NET_SERIAL_MAX)", "else if (n_ent <= NET_PACK_KEYS)", "if (n_ent <= 64u)"):
+        assert piece in body, piece
 
 
 def test_engine_resources_are_taken_and_given_back_in_one_header():
