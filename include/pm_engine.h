@@ -231,6 +231,11 @@ int32_t pm_upload_tasks(pm_engine*, const pm_task_soa* tasks);
  *                          they fall into, and every claimed task keeps its binding.
  *   pm_tasks_delete        on_task_deleted (mod.rs:1245-1325) by task id (needs pm_task_soa.uid): the rows leave
  *                          the list, groups that had claimed one of them are dissolved; unknown ids are ignored.
+ *                          An id named twice in one call counts once.
+ * DUPLICATE IDS.  Ids are the caller's and are not checked for uniqueness.  Where two live rows carry the same id, the id
+ * names the FIRST of them in list order — the newer one — everywhere: pm_tasks_delete removes that row and only it
+ * (the next call with the id removes the next one), and pm_upload_tasks re-binds a claim to the first row of the new list
+ * with the claimed id.  Neither depends on which calls came before.
  * Task indices reported by the engine (pm_assignment.task, pm_group.task, pm_match*, pm_newest_task) are always
  * positions in the caller's CURRENT list: after an insertion of n rows every older task's index is n higher,
  * after a deletion the later ones move up — exactly as in the caller's own Vec<Task>.  That includes the table

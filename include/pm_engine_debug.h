@@ -51,6 +51,13 @@ int32_t pm_debug_merge_streamed(pm_engine* e, uint32_t* n);
  * pm_get_groups, pm_dissolve_group and the merge pass compact the list: the tick after them uploads it whole. */
 int32_t pm_debug_delta_pushes(pm_engine* e, uint32_t* n);
 
+/* Read-only: the way the last per-task call (pm_match_per_task, pm_match_per_task_device) took.  From 200,000 swept rows on
+ * (t_cap - t_lo: tombstones count), below 64 configurations and with sweep_variant 0, the call counts the distinct masks of
+ * the live tasks — restricted to the installed configurations, the empty mask left out — and sweeps once per distinct mask
+ * while there are at most 65,536 of them; otherwise one row per task.  *distinct_masks = that count (0 when the call did
+ * not count), *interned = 1 when it swept per distinct mask.  tests/test_gpu_task_table_edges.py holds both edges to it. */
+int32_t pm_debug_per_task_path(pm_engine* e, uint32_t* distinct_masks, uint32_t* interned);
+
 /* Test hook / experiment: when the proposers walk the spatial index instead of sweeping the whole candidate list —
  * 0 never, 1 when it pays (default), 2 whenever the carve has an index, 3 = 2 with every seed forced through the
  * whole-list fallback.  (PM_PRUNE_MODE in the environment sets the default of new engines.) */

@@ -363,6 +363,7 @@ static int32_t run_match_per_task(pm_engine* e) {
   constexpr uint32_t H = 1u << 17, CAP_U = 1u << 16;
   bool per_mask = R >= 200000u && n_planes < 64u && variant != 1;
   uint32_t n_u = 0;
+  e->pt_distinct = 0;
   if (per_mask) {
     const uint64_t valid = (1ull << n_planes) - 1ull;
     HIPCHK(e->d_ikeys.ensure(H));
@@ -375,6 +376,7 @@ static int32_t run_match_per_task(pm_engine* e) {
     HIPCHK(hipMemcpyAsync(h, counter, 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     n_u = h[0];
+    e->pt_distinct = n_u;
     if (h[1] || n_u > CAP_U) per_mask = false;
     if (per_mask) {
       rc = ensure_sweep_outputs(e, std::max<uint32_t>(n_u, 1));
@@ -385,6 +387,7 @@ static int32_t run_match_per_task(pm_engine* e) {
                                 e->t_cap, e->d_tlive.p, e->d_tprefix.p, e->d_first_c.p, e->d_count_c.p, e->stream);
     }
   }
+  e->pt_interned = per_mask;
   if (!per_mask) {
     launch_pair_sweep(variant, e->d_tmask.p + e->t_lo, R, cols, e->d_wplanes.p, 0, e->W, uint32_t((size_t(e->W) + 63) / 64),
                       n_planes, e->d_first.p, e->d_count.p, e->stream);

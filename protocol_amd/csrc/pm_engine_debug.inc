@@ -116,6 +116,17 @@ int32_t pm_debug_delta_pushes(pm_engine* e, uint32_t* n) {
   return PM_OK;
 }
 
+// debug (include/pm_engine_debug.h): which way the last per-task call (pm_match_per_task, pm_match_per_task_device) took —
+// the distinct valid masks it counted (0: fewer than 200,000 rows, 64 configurations or sweep_variant 1: it did not count)
+// and whether it swept once per distinct mask
+int32_t pm_debug_per_task_path(pm_engine* e, uint32_t* distinct_masks, uint32_t* interned) {
+  if (!e || !distinct_masks || !interned) return set_error(PM_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  *distinct_masks = e->pt_distinct;
+  *interned = e->pt_interned ? 1u : 0u;
+  return PM_OK;
+}
+
 // debug (include/pm_engine_debug.h): when the proposer walks the spatial index instead of sweeping the whole candidate list —
 // 0 never, 1 when it pays (default), 2 whenever the carve has one (built for any swarm of 64+ positions),
 // 3 = 2 with every seed sent through the whole-list fallback

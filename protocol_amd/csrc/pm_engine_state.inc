@@ -102,6 +102,8 @@ struct pm_engine {
   uint32_t debug_mem_above = 0;  // pm_debug_mem_lists_above
   uint32_t debug_abort_after = 0;  // pm_debug_stream_abort_after
   uint32_t delta_pushes = 0;       // push_groups calls that went up as a delta (since creation)
+  uint32_t pt_distinct = 0;        // pm_debug_per_task_path: distinct valid masks the last per-task call counted (0: it did not count)
+  bool pt_interned = false;        // ... and whether it swept once per distinct mask
   uint32_t merge_streamed = 0;     // merge configurations whose selections went through the streaming carve (since creation)
   uint32_t merge_stream_min = 512; // PM_MERGE_STREAM_MIN: compatible solo groups from which a merge configuration does (tests: 8)
   uint32_t prune_mode = 1;       // pm_debug_prune_mode / PM_PRUNE_MODE: CarveArgs::prune_mode
@@ -172,6 +174,7 @@ struct pm_engine {
   bool tasks_have_uid = false;
   std::unordered_map<uint64_t, uint32_t> uid_to_u;  // built on the first pm_tasks_delete
   bool uid_map_valid = false;
+  bool uid_dup = false;  // some id is carried by two live rows (seen when the map was built, or by an insertion since)
   uint32_t cfg_app_count[PM_MAX_CONFIGS]{};         // live tasks applicable per configuration (merge path)
   bool cfg_app_valid = false;
   DevBuf<uint64_t> d_tmask, d_tplanes, d_tlive;

@@ -30,8 +30,8 @@ static int32_t tasks_push_range(pm_engine* e, uint32_t u0, uint32_t u1) {
   return PM_OK;
 }
 
-// Tombstones a rebuild leaves standing inside the swept range [t_lo, t_cap) beyond the live count: more than
-// T + PM_TASK_DEAD_SLACK of them and the next delta rebuilds the index space (tasks_rebuild).
+// Tombstones that may stand inside the swept range [t_lo, t_cap) beyond the live count: a delete that leaves more than
+// T + PM_TASK_DEAD_SLACK of them rebuilds the index space before it returns (tasks_rebuild).
 static constexpr uint32_t PM_TASK_DEAD_SLACK = 4096;
 
 // A fresh index space of capacity `cap` holding the LIVE rows only, in list order, at its top: the regrowth (the table
@@ -96,6 +96,7 @@ int32_t pm_upload_tasks(pm_engine* e, const pm_task_soa* t) {
   e->tasks_have_uid = t->uid != nullptr;
   e->uid_to_u.clear();
   e->uid_map_valid = false;
+  e->uid_dup = false;
   e->cfg_app_valid = false;
   int32_t rc;
   if (e->t_cap < n + 64u || uint64_t(e->t_cap) > uint64_t(n) * 8 + (1u << 20) || had_uid != e->tasks_have_uid) {
@@ -224,21 +225,16 @@ static int32_t tasks_insert_front_locked(pm_engine* e, const pm_task_soa* t) {
     int32_t rc = tasks_rebuild(e, task_capacity_for(e->T + n));
     if (rc) return rc;
     e->t_regrowths++;
-  } else if (e->t_dead > e->T + PM_TASK_DEAD_SLACK) {  // room enough, but the swept range is mostly tombstones
-    int32_t rc = tasks_rebuild(e, e->t_cap);
-    if (rc) return rc;
-    e->t_compactions++;
   }
+  // (no compaction here: every upload, delete and rebuild leaves t_dead <= T + PM_TASK_DEAD_SLACK, and an insertion only
+  // raises T — pm_tasks_delete is the one place the bound can be crossed)
   if (e->tasks_have_uid && e->h_tuid.size() != e->t_cap) e->h_tuid.assign(e->t_cap, 0);
   const uint32_t lo = e->t_lo - n;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t u = lo + i;
     e->h_tmask[u] = t->topo_mask[i];
     e->h_created[u] = t->created_at[i];
-    if (t->uid) {
-      e->h_tuid[u] = t->uid[i];
-      if (e->uid_map_valid) e->uid_to_u.emplace(t->uid[i], u);
-    }
+    if (t->uid) e->h_tuid[u] = t->uid[i];
     e->h_tlive[u >> 6] |= 1ull << (u & 63u);
     if (e->cfg_app_valid) {
       uint64_t m = t->topo_mask[i];
@@ -247,6 +243,13 @@ static int32_t tasks_insert_front_locked(pm_engine* e, const pm_task_soa* t) {
         m &= m - 1;
       }
     }
+  }
+  if (t->uid && e->uid_map_valid) {
+    // an id names the FIRST row in list order that carries it (include/pm_engine.h): the new rows stand in front of every
+    // older one, and among themselves the earlier one wins (descending: it is written last)
+    const size_t before = e->uid_to_u.size();
+    for (uint32_t i = n; i-- > 0;) e->uid_to_u[t->uid[i]] = lo + i;
+    if (e->uid_to_u.size() != before + n) e->uid_dup = true;
   }
   {
     int32_t rcp = tasks_push_range(e, lo, e->t_lo);
@@ -282,6 +285,7 @@ int32_t pm_tasks_delete(pm_engine* e, const uint64_t* uids, uint32_t n, uint32_t
     for (uint32_t u = e->t_cap; u-- > e->t_lo;)  // descending: the first occurrence in list order wins
       if ((e->h_tlive[u >> 6] >> (u & 63u)) & 1ull) e->uid_to_u[e->h_tuid[u]] = u;
     e->uid_map_valid = true;
+    e->uid_dup = e->uid_to_u.size() != e->T;
   }
   // what is to go (nothing is changed yet: everything that can fail comes before the first mutation, so that the
   // host mirror and the device table cannot drift apart on an error return)
@@ -323,6 +327,7 @@ int32_t pm_tasks_delete(pm_engine* e, const uint64_t* uids, uint32_t n, uint32_t
     if (!gr.dead && gr.task != PM_NONE && std::binary_search(slots.begin(), slots.end(), gr.task))
       dissolve_locked(e, uint32_t(g));
   }
+  if (e->uid_dup) e->uid_map_valid = false;  // (an id some other row carries too names that row now: the map is built anew)
   e->T -= uint32_t(slots.size());
   e->t_dead += uint32_t(slots.size());
   while (e->t_lo < e->t_cap && !((e->h_tlive[e->t_lo >> 6] >> (e->t_lo & 63u)) & 1ull)) {  // dead rows in front

@@ -867,6 +867,16 @@ class Engine:
         check(L.pm_debug_delta_pushes(self._h, C.byref(n)))
         return n.value
 
+    def debug_per_task_path(self) -> tuple:
+        """(distinct valid masks the last match_per_task counted — 0 when it did not count —, whether it swept once per
+        distinct mask) (include/pm_engine_debug.h)"""
+        L = lib()
+        L.pm_debug_per_task_path.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pm_debug_per_task_path.restype = C.c_int32
+        n, interned = C.c_uint32(0), C.c_uint32(0)
+        check(L.pm_debug_per_task_path(self._h, C.byref(n), C.byref(interned)))
+        return n.value, bool(interned.value)
+
     @staticmethod
     def debug_live_allocations() -> tuple:
         """(device bytes, pinned host bytes, events + streams) the engines of this process hold from the HIP runtime right

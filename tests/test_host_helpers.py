@@ -35,14 +35,16 @@ def test_library_exports_every_declared_symbol():
 def test_library_exports_every_declared_debug_hook():
     """include/pm_engine_debug.h: the test hooks and counters tests/, tools/ and bench.py call — since the distance-key
     hook (tests/test_gpu_distance_key.py) thirteen of them, with the live-allocation counter fourteen, with the row
-    certificates' hook (tests/test_gpu_row_certificates.py) fifteen.  Not part of the drop-in boundary (the Rust shim binds none of
+    certificates' hook (tests/test_gpu_row_certificates.py) fifteen, with the per-task path's read-out
+    (tests/test_gpu_task_table_edges.py) sixteen.  Not part of the drop-in boundary (the Rust shim binds none of
     them), but exported by the shipped library, with the declared arity."""
     hdr = open(os.path.join(ROOT, "include", "pm_engine_debug.h")).read()
     protos = _c_prototypes(hdr)
     assert set(protos) == {"pm_debug_carve_prof", "pm_debug_stream_trace", "pm_debug_mem_lists_above", "pm_debug_prune_mode",
                            "pm_debug_hbm_triad", "pm_debug_stream_abort_after", "pm_debug_merge_streamed", "pm_debug_delta_pushes",
                            "pm_debug_row_networks", "pm_debug_row_records", "pm_debug_chain_batches", "pm_debug_park_records",
-                           "pm_debug_distance_keys", "pm_debug_live_allocations", "pm_debug_row_certificates"}
+                           "pm_debug_distance_keys", "pm_debug_live_allocations", "pm_debug_row_certificates",
+                           "pm_debug_per_task_path"}
     L = E.lib()
     for name in protos:
         assert hasattr(L, name), f"{name} declared in pm_engine_debug.h but not exported"
