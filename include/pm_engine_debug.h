@@ -103,8 +103,60 @@ int32_t pm_debug_row_certificates(pm_engine* e, const uint64_t* keys, const uint
  * and ux, uy, uz of the first point, the same of the second, hav_a, prox_a, 1 if prox_a took the chord form (else 0),
  * candidate_key's unpacked key (its f64 bits), then pack_key(prox_a, slot) at the 13, 18 and 21 slot bits of the library, and
  * pack_key(hav_a, slot) at the same three widths (f64 bits; the slot taken modulo the width).  mode 1: out[n] = sin_band(in[n]).
- * mode 2 (in, n unused): out[8] = PM_A_CHORD_MIN, PM_A_MAX_SAFE, the three certificate bands, the three slot widths. */
+ * mode 2 (in, n unused): out[8] = PM_A_CHORD_MIN, PM_A_MAX_SAFE, the three certificate bands, the three slot widths.
+ * mode 3: mode 0's input and kernel, but out[n] = candidate_key's unpacked key alone (word 13 of each record: the host copies
+ * that column out of the device's records, a twentieth of the transfer — tests/test_gpu_first_batch.py asks for millions of
+ * pairs). */
 int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out);
+
+/* The first batch of a formation on the batch pipeline (carve_variant 3), as the device holds it: pm_debug_first_batch_arm arms
+ * a snapshot for the engine's NEXT formation (pm_form_groups, pm_tick); behind that formation's first propose launch — the list
+ * preparation, the spatial index and the neighbour rows are all still in HBM, the validation launch not yet queued — the host
+ * copies the parts below out in stream order into memory the engine owns, and the carve runs on as always (no kernel reads or
+ * writes anything for this; unarmed the cost is one host-side branch).  An engine of another carve_variant refuses with
+ * PM_ESTATE: the streaming carve keeps its rows in a ring for microseconds and has no such moment.
+ * pm_debug_first_batch_get copies part `part` to out (cap_bytes) and returns its size in *n_bytes; out = NULL asks for the size
+ * alone; PM_ESTATE when no snapshot was taken since the last arm (the formation had nothing to carve, or took another path:
+ * the arm ends with that formation either way and is not carried to a later one).  A snapshot stands until the next arm.
+ * Lengths: n = n_eligible, n_list, n_seeds, g = the carve's cell_g (the index parts are empty when it is 0), n_indexed. */
+enum {
+  PM_FB_HEAD = 0,    /* u32[PM_FB_HEAD_WORDS]: BatchDesc {planned, ci0, total_available, valid, none, ci, n_list, prop_k, prop_limit,
+                        n_seeds, cell_g}; CarveStatus {n_eligible, cell_g, n_indexed, prune_fallbacks, pruned_batches, n_props,
+                        prop_keys lo, hi}; the index scan's ticket word; CarveArgs::prune_mode; 0, 0, 0 */
+  PM_FB_ORDER,       /* u32[n]   per position of the eligible list: the worker row */
+  PM_FB_C_SITE,      /* u32[n] */
+  PM_FB_C_UX,        /* f64[n] */
+  PM_FB_C_UY,
+  PM_FB_C_UZ,
+  PM_FB_C_LAT,
+  PM_FB_C_LON,
+  PM_FB_C_COS,
+  PM_FB_C_COMPAT,    /* u64[n] */
+  PM_FB_LOC_G,       /* u64[ceil(n / 64)]  positions with a location */
+  PM_FB_ALIVE_SNAP,  /* u64[ceil(n / 64)]  positions no group held when the list was prepared */
+  PM_FB_SLOT_WID,    /* u32[n_list]  per slot of the prepared list: the worker row */
+  PM_FB_SLOT_POS,    /* u32[n_list]  its position | has a location << 31 */
+  PM_FB_CC_SITE,     /* u32[n_list] */
+  PM_FB_SLOT_ALIVE,  /* u64[ceil(n_list / 64)] */
+  PM_FB_SLOT_LOC,    /* u64[ceil(n_list / 64)] */
+  PM_FB_SEED_MAP,    /* u64[ceil(prop_limit / 64)] */
+  PM_FB_SEED_PREFIX, /* u32[ceil(prop_limit / 64)] */
+  PM_FB_SEED_SLOTS,  /* u32[n_seeds] */
+  PM_FB_PROP,        /* u64[n_seeds][PM_PROP_ROW = 96]: the flags word, 63 keys; from word 64 on 64 x u32: the flags, 63 slots */
+  PM_FB_CELL_START,  /* u32[g^3 + 1] */
+  PM_FB_CELL_CNT,    /* u32[g^3] */
+  PM_FB_POS_CELL,    /* u32[n] */
+  PM_FB_CS_OF_POS,   /* u32[n] */
+  PM_FB_CS_SLOT,     /* u32[n_indexed] */
+  PM_FB_CS_SITE,     /* u32[n_indexed] */
+  PM_FB_CS_UX,       /* f64[n_indexed] */
+  PM_FB_CS_UY,
+  PM_FB_CS_UZ,
+  PM_FB_PARTS
+};
+#define PM_FB_HEAD_WORDS 24
+int32_t pm_debug_first_batch_arm(pm_engine* e);
+int32_t pm_debug_first_batch_get(pm_engine* e, uint32_t part, void* out, uint64_t cap_bytes, uint64_t* n_bytes);
 
 /* What every engine of this process holds from the HIP runtime right now: out[0] = device bytes, out[1] = pinned host bytes,
  * out[2] = events and streams.  Counted where an allocation is made or given back, not per call: an engine that is destroyed

@@ -544,13 +544,85 @@ static int32_t launch_propose_timed(pm_engine* e, const CarveArgs* d_args, uint3
 
 // (propose, validate) pairs: one per configuration plus one per re-proposal round; launches queued behind a
 // finished carve return immediately
+static int32_t first_batch_snapshot(pm_engine* e, const FormRun* r);
+
 static int32_t form_queue_pairs(pm_engine* e, FormRun* r, uint32_t count) {
   for (uint32_t k = 0; k < count; ++k) {
     int32_t rc = launch_propose_timed(e, e->d_carve_args.p, r->n_bound, e->stream);
     if (rc) return rc;
+    if (e->fb_armed) {  // (pm_debug_first_batch_arm: the first batch as it stands in HBM, before the validator takes it)
+      rc = first_batch_snapshot(e, r);
+      if (rc) return rc;
+    }
     HIPCHK(launch_carve(e->d_carve_args.p, CARVE_F_RUN | CARVE_F_PROPS | CARVE_F_EXTPREP, 0, r->lds, e->stream));
     e->tick_carve_launches += 2u + launch_carve_prep(e->d_carve_args.p, r->n_bound, e->stream);  // the next candidate list
   }
+  return PM_OK;
+}
+
+// debug (pm_debug_first_batch_arm): behind the first propose launch of a formation on the batch pipeline everything the
+// preparation, the index kernels and the proposer wrote is still in HBM — the validation launch is queued behind this.  The
+// status and the batch's description come first (they size the rest: the host queues blindly and knows neither list length),
+// then every part in stream order, into host memory the engine owns.  Nothing on the device is touched.
+static int32_t first_batch_snapshot(pm_engine* e, const FormRun* r) {
+  e->fb_armed = false;
+  e->fb_taken = false;
+  e->fb_part.assign(PM_FB_PARTS, {});
+  const CarveArgs& a = r->a;
+  CarveStatus st;
+  BatchDesc d;
+  uint32_t scan_ticket = 0;
+  HIPCHK(hipMemcpyAsync(&st, e->d_status.p, sizeof(st), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(&d, e->d_desc.p, sizeof(d), hipMemcpyDeviceToHost, e->stream));
+  if (a.cell_start) HIPCHK(hipMemcpyAsync(&scan_ticket, a.cell_start + PM_CELL_TABLE + 320, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const bool listed = d.planned && d.valid;
+  const size_t n = st.n_eligible, nw = (n + 63) / 64;
+  const size_t nl = listed ? d.n_list : 0, lw = (nl + 63) / 64, ns = listed ? d.n_seeds : 0;
+  const size_t sw = listed && d.prop_k ? (size_t(d.prop_limit) + 63) / 64 : 0;
+  const size_t g3 = a.cell_start ? size_t(st.cell_g) * st.cell_g * st.cell_g : 0, ni = g3 ? st.n_indexed : 0;
+  if (n > e->d_order.cap || nl > e->d_slot_wid.cap || ns > PM_PROP_MAX_SEEDS + 64u || ni > n || g3 + 1 > PM_CELL_TABLE)
+    return set_error(PM_ESTATE, "first batch snapshot: the device's counts exceed the buffers");
+  const uint32_t head[PM_FB_HEAD_WORDS] = {d.planned, d.ci0, d.total_available, d.valid, d.none, d.ci, d.n_list, d.prop_k,
+                                           d.prop_limit, d.n_seeds, d.cell_g, st.n_eligible, st.cell_g, st.n_indexed,
+                                           st.prune_fallbacks, st.pruned_batches, st.n_props, uint32_t(st.prop_keys),
+                                           uint32_t(st.prop_keys >> 32), scan_ticket, a.prune_mode, 0, 0, 0};
+  e->fb_part[PM_FB_HEAD].assign((const unsigned char*)head, (const unsigned char*)head + sizeof(head));
+  auto take = [&](uint32_t part, const void* src, size_t bytes) -> hipError_t {
+    e->fb_part[part].resize(bytes);
+    return bytes && src ? hipMemcpyAsync(e->fb_part[part].data(), src, bytes, hipMemcpyDeviceToHost, e->stream) : hipSuccess;
+  };
+  HIPCHK(take(PM_FB_ORDER, a.order, n * 4));
+  HIPCHK(take(PM_FB_C_SITE, a.c_site, n * 4));
+  HIPCHK(take(PM_FB_C_UX, a.c_ux, n * 8));
+  HIPCHK(take(PM_FB_C_UY, a.c_uy, n * 8));
+  HIPCHK(take(PM_FB_C_UZ, a.c_uz, n * 8));
+  HIPCHK(take(PM_FB_C_LAT, a.c_lat, n * 8));
+  HIPCHK(take(PM_FB_C_LON, a.c_lon, n * 8));
+  HIPCHK(take(PM_FB_C_COS, a.c_cos, n * 8));
+  HIPCHK(take(PM_FB_C_COMPAT, a.c_compat, n * 8));
+  HIPCHK(take(PM_FB_LOC_G, a.loc_g, nw * 8));
+  HIPCHK(take(PM_FB_ALIVE_SNAP, a.alive_snap, nw * 8));
+  HIPCHK(take(PM_FB_SLOT_WID, a.slot_wid, nl * 4));
+  HIPCHK(take(PM_FB_SLOT_POS, a.slot_pos, nl * 4));
+  HIPCHK(take(PM_FB_CC_SITE, a.cc_site, nl * 4));
+  HIPCHK(take(PM_FB_SLOT_ALIVE, a.bits_scratch, lw * 8));
+  HIPCHK(take(PM_FB_SLOT_LOC, a.bits_scratch + a.bits_stride, lw * 8));
+  HIPCHK(take(PM_FB_SEED_MAP, a.seed_map, sw * 8));
+  HIPCHK(take(PM_FB_SEED_PREFIX, a.seed_prefix, sw * 4));
+  HIPCHK(take(PM_FB_SEED_SLOTS, a.seed_slots, ns * 4));
+  HIPCHK(take(PM_FB_PROP, a.prop, ns * PM_PROP_ROW * 8));
+  HIPCHK(take(PM_FB_CELL_START, a.cell_start, g3 ? (g3 + 1) * 4 : 0));
+  HIPCHK(take(PM_FB_CELL_CNT, a.cell_cnt, g3 * 4));
+  HIPCHK(take(PM_FB_POS_CELL, a.pos_cell, g3 ? n * 4 : 0));
+  HIPCHK(take(PM_FB_CS_OF_POS, a.cs_of_pos, g3 ? n * 4 : 0));
+  HIPCHK(take(PM_FB_CS_SLOT, a.cs_slot, ni * 4));
+  HIPCHK(take(PM_FB_CS_SITE, a.cs_site, ni * 4));
+  HIPCHK(take(PM_FB_CS_UX, a.cs_ux, ni * 8));
+  HIPCHK(take(PM_FB_CS_UY, a.cs_uy, ni * 8));
+  HIPCHK(take(PM_FB_CS_UZ, a.cs_uz, ni * 8));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->fb_taken = true;
   return PM_OK;
 }
 
@@ -607,6 +679,7 @@ static int32_t form_poll(pm_engine* e, FormRun* r) {
 // have_event: ev_groups has been recorded behind the carve already (and waited for)
 static int32_t form_finish(pm_engine* e, FormRun* r, uint32_t* n_formed, bool defer_absorb, bool have_event = false) {
   if (n_formed) *n_formed = 0;
+  e->fb_armed = false;  // (pm_debug_first_batch_arm is for ONE formation: one that had no propose launch leaves no snapshot and no arm)
   if (r->nothing) return PM_OK;
   const CarveStatus& st = r->st;
   e->tick_fast_steps += st.fast_steps;

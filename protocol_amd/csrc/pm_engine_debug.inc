@@ -230,7 +230,9 @@ int32_t pm_debug_row_certificates(pm_engine* e, const uint64_t* keys, const uint
 
 // debug (include/pm_engine_debug.h): the distance key of n pairs by geo_kernel and the carve's own device functions
 int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint32_t mode, double* out) {
-  if (!e || !out || mode > 2u) return set_error(PM_EINVAL, "null argument");
+  if (!e || !out || mode > 3u) return set_error(PM_EINVAL, "null argument");
+  const bool key_only = mode == 3u;  // (the same launch as mode 0; one column of its records comes back)
+  if (key_only) mode = 0u;
   if (mode == 2u) {
     const double c[8] = {PM_A_CHORD_MIN, PM_A_MAX_SAFE, PM_TIE_BAND, PM_TIE_BAND_BIG, PM_TIE_BAND_MEM,
                          double(PM_CARVE_SLOT_BITS), double(PM_CARVE_SLOT_BITS_BIG), double(PM_CARVE_SLOT_BITS_MEM)};
@@ -250,8 +252,35 @@ int32_t pm_debug_distance_keys(pm_engine* e, const double* in, uint32_t n, uint3
     launch_geo(d_in, d_in + size_t(2) * n, d_geo, d_geo + size_t(2) * n, d_geo + size_t(4) * n, d_geo + size_t(6) * n, 2u * n,
                e->stream);
   launch_distance_key_test(d_in, d_geo, n, mode, d_out, e->stream);
-  (void)hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, e->stream);
+  if (key_only)  // word 13 of every record: n rows of one f64, PM_DK_WORDS f64 apart
+    (void)hipMemcpy2DAsync(out, 8, d_out + 13, size_t(PM_DK_WORDS) * 8, 8, n, hipMemcpyDeviceToHost, e->stream);
+  else
+    (void)hipMemcpyAsync(out, d_out, n_out * 8, hipMemcpyDeviceToHost, e->stream);
   if (hipStreamSynchronize(e->stream) != hipSuccess) return set_error(PM_ENODEV, "distance key test");
+  return PM_OK;
+}
+
+// debug (include/pm_engine_debug.h): arm a snapshot of the next formation's first batch (form_queue_pairs takes it:
+// first_batch_snapshot, pm_engine_carve.inc); the batch pipeline only
+int32_t pm_debug_first_batch_arm(pm_engine* e) {
+  if (!e) return set_error(PM_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->cfg.carve_variant != 3) return set_error(PM_ESTATE, "first batch snapshot: the batch pipeline (carve_variant 3) only");
+  e->fb_armed = true;
+  e->fb_taken = false;
+  e->fb_part.clear();
+  return PM_OK;
+}
+// ... and one part of it (PM_FB_*): its size, and with `out` its bytes
+int32_t pm_debug_first_batch_get(pm_engine* e, uint32_t part, void* out, uint64_t cap_bytes, uint64_t* n_bytes) {
+  if (!e || !n_bytes || part >= PM_FB_PARTS) return set_error(PM_EINVAL, "first batch snapshot: null argument or no such part");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (!e->fb_taken || e->fb_part.size() != PM_FB_PARTS) return set_error(PM_ESTATE, "first batch snapshot: none taken");
+  const std::vector<unsigned char>& p = e->fb_part[part];
+  *n_bytes = p.size();
+  if (!out) return PM_OK;
+  if (cap_bytes < p.size()) return set_error(PM_ERANGE, "first batch snapshot: buffer too small");
+  if (!p.empty()) std::memcpy(out, p.data(), p.size());
   return PM_OK;
 }
 

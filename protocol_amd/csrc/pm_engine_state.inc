@@ -226,6 +226,10 @@ struct pm_engine {
   // spatial index of a carve's located positions (cell_*_kernel)
   DevBuf<uint32_t> d_cell_cnt, d_cell_start, d_pos_cell, d_pos_rank, d_cs_of_pos, d_cs_slot, d_cs_site;
   DevBuf<double> d_cs_u[3];
+  // pm_debug_first_batch_arm / _get: the host's copies of what the batch pipeline's first preparation and propose launch left in
+  // HBM (form_queue_pairs takes them when armed; PM_FB_* of include/pm_engine_debug.h number the parts)
+  bool fb_armed = false, fb_taken = false;
+  std::vector<std::vector<unsigned char>> fb_part;
   DevBuf<double> d_c_pack, d_cs_pack;  // streaming carve: 32-byte gather records by position / by index entry
   // streaming carve (carve_stream_kernel): per-configuration bitmaps, ticket and row rings, control block, candidate list
   DevBuf<uint64_t> d_cfgbits, d_stream_sq, d_stream_row_lo, d_stream_row_hi, d_stream_trace;

@@ -95,6 +95,17 @@ ROW_SLOT_BITS, ROW_SLOT_BITS_BIG = 13, 18
 TIE_BAND, TIE_BAND_BIG = 2.0 ** -36, 2.0 ** -31
 WINDOW_ULPS, WINDOW_ULPS_BIG = 1 << 20, 1 << 25
 NET_SERIAL_MAX, NET_PACK_KEYS = 16, 128
+# the first batch's snapshot (include/pm_engine_debug.h, PM_FB_*): the words of its head ("" = unused), its parts in order
+PROP_ROW, PROP_SLOTS = 96, 64      # PM_PROP_ROW, PM_PROP_SLOTS: a row's u64 words, the word its 32-bit half begins at
+FB_HEAD = ("planned", "ci0", "total_available", "valid", "none", "ci", "n_list", "prop_k", "prop_limit", "n_seeds", "cell_g",
+           "n_eligible", "index_g", "n_indexed", "prune_fallbacks", "pruned_batches", "n_props", "prop_keys_lo", "prop_keys_hi",
+           "scan_ticket", "prune_mode", "", "", "")
+FB_PARTS = (("head", "<u4"), ("order", "<u4"), ("c_site", "<u4"), ("c_ux", "<f8"), ("c_uy", "<f8"), ("c_uz", "<f8"), ("c_lat", "<f8"),
+            ("c_lon", "<f8"), ("c_cos", "<f8"), ("c_compat", "<u8"), ("loc_g", "<u8"), ("alive_snap", "<u8"), ("slot_wid", "<u4"),
+            ("slot_pos", "<u4"), ("cc_site", "<u4"), ("slot_alive", "<u8"), ("slot_loc", "<u8"), ("seed_map", "<u8"),
+            ("seed_prefix", "<u4"), ("seed_slots", "<u4"), ("prop", "<u8"), ("cell_start", "<u4"), ("cell_cnt", "<u4"),
+            ("pos_cell", "<u4"), ("cs_of_pos", "<u4"), ("cs_slot", "<u4"), ("cs_site", "<u4"), ("cs_ux", "<f8"), ("cs_uy", "<f8"),
+            ("cs_uz", "<f8"))
 MXB_REPLACE, MXB_MERGE, MXB_DELETE = 0, 1, 2
 MXF_MAX = 1
 assignment_dt = np.dtype([("task", "<u4"), ("group_slot", "<u4"), ("group_index", "<u4"), ("group_size", "<u4"),
@@ -965,6 +976,52 @@ class Engine:
                 "cos2": out[:, 6].copy(), "u2": out[:, 7:10].copy(), "hav_a": out[:, 10].copy(), "prox_a": out[:, 11].copy(),
                 "chord": out[:, 12] == 1.0, "candidate_key": out[:, 13].copy(), "packed_prox": bits[:, 14:17].copy(),
                 "packed_hav": bits[:, 17:20].copy()}
+
+    def debug_candidate_keys(self, lat1, lon1, lat2, lon2) -> "np.ndarray":
+        """test hook (pm_debug_distance_keys mode 3): candidate_key's unpacked key of every pair alone, as u64 bit patterns —
+        the kernel of debug_distance_keys, one column of its records copied back"""
+        import numpy as np
+        L = lib()
+        n = len(lat1)
+        inp = np.concatenate([np.asarray(lat1, np.float64), np.asarray(lat2, np.float64), np.asarray(lon1, np.float64),
+                              np.asarray(lon2, np.float64), np.zeros(n)])
+        assert inp.size == 5 * n
+        out = np.zeros(n, dtype=np.uint64)
+        L.pm_debug_distance_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.pm_debug_distance_keys.restype = C.c_int32
+        check(L.pm_debug_distance_keys(self._h, inp.ctypes.data, n, 3, out.ctypes.data))
+        return out
+
+    def debug_first_batch_arm(self):
+        """test hook (include/pm_engine_debug.h): the next formation of this engine (carve_variant 3) leaves a snapshot of its
+        first batch — candidate list, spatial index, neighbour rows — for debug_first_batch()"""
+        L = lib()
+        L.pm_debug_first_batch_arm.argtypes = [C.c_void_p]
+        L.pm_debug_first_batch_arm.restype = C.c_int32
+        check(L.pm_debug_first_batch_arm(self._h))
+
+    def debug_first_batch(self) -> dict:
+        """the armed snapshot: FB_HEAD's words by name, every other part of FB_PARTS as a numpy array of its type (`prop` as
+        u64[n_seeds, 96])"""
+        import numpy as np
+        L = lib()
+        L.pm_debug_first_batch_get.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.pm_debug_first_batch_get.restype = C.c_int32
+        out = {}
+        for part, (name, dt) in enumerate(FB_PARTS):
+            nb = C.c_uint64(0)
+            check(L.pm_debug_first_batch_get(self._h, part, None, 0, C.byref(nb)))
+            a = np.zeros(nb.value // np.dtype(dt).itemsize, dtype=dt)
+            assert a.nbytes == nb.value, (name, nb.value)
+            if a.size:
+                check(L.pm_debug_first_batch_get(self._h, part, a.ctypes.data, a.nbytes, C.byref(nb)))
+            out[name] = a
+        head = out.pop("head")
+        assert head.size == len(FB_HEAD)
+        out.update({k: int(v) for k, v in zip(FB_HEAD, head) if k})
+        out["prop_keys"] = out.pop("prop_keys_lo") | (out.pop("prop_keys_hi") << 32)
+        out["prop"] = out["prop"].reshape(-1, PROP_ROW)
+        return out
 
     def debug_sin_band(self, x):
         """test hook (include/pm_engine_debug.h): the carve's sine, sin_band, on the device at each x"""

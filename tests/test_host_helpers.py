@@ -36,7 +36,8 @@ def test_library_exports_every_declared_debug_hook():
     """include/pm_engine_debug.h: the test hooks and counters tests/, tools/ and bench.py call — since the distance-key
     hook (tests/test_gpu_distance_key.py) thirteen of them, with the live-allocation counter fourteen, with the row
     certificates' hook (tests/test_gpu_row_certificates.py) fifteen, with the per-task path's read-out
-    (tests/test_gpu_task_table_edges.py) sixteen.  Not part of the drop-in boundary (the Rust shim binds none of
+    (tests/test_gpu_task_table_edges.py) sixteen, with the first batch's snapshot (tests/test_gpu_first_batch.py: arm and get)
+    eighteen.  Not part of the drop-in boundary (the Rust shim binds none of
     them), but exported by the shipped library, with the declared arity."""
     hdr = open(os.path.join(ROOT, "include", "pm_engine_debug.h")).read()
     protos = _c_prototypes(hdr)
@@ -44,7 +45,7 @@ def test_library_exports_every_declared_debug_hook():
                            "pm_debug_hbm_triad", "pm_debug_stream_abort_after", "pm_debug_merge_streamed", "pm_debug_delta_pushes",
                            "pm_debug_row_networks", "pm_debug_row_records", "pm_debug_chain_batches", "pm_debug_park_records",
                            "pm_debug_distance_keys", "pm_debug_live_allocations", "pm_debug_row_certificates",
-                           "pm_debug_per_task_path"}
+                           "pm_debug_per_task_path", "pm_debug_first_batch_arm", "pm_debug_first_batch_get"}
     L = E.lib()
     for name in protos:
         assert hasattr(L, name), f"{name} declared in pm_engine_debug.h but not exported"
@@ -568,6 +569,18 @@ def test_row_constants_are_the_device_sources():
     body = prop[prop.index("NearRow near_row_bulk4_body("):prop.index("NearRow near_row_bulk4(")]
     for piece in ("if (n_ent <= NET_SERIAL_MAX)", "else if (n_ent <= NET_PACK_KEYS)", "if (n_ent <= 64u)"):
         assert piece in body, piece
+
+
+def test_first_batch_snapshot_parts_follow_the_header():
+    """engine.py's FB_PARTS / FB_HEAD are include/pm_engine_debug.h's PM_FB_* in the enum's order, and a row's layout pm_device.h's"""
+    hdr = open(os.path.join(ROOT, "include", "pm_engine_debug.h")).read()
+    enum = hdr[hdr.index("PM_FB_HEAD = 0"):hdr.index("PM_FB_PARTS\n")]
+    names = re.findall(r"^\s*PM_FB_([A-Z_]+)\b", re.sub(r"/\*.*?\*/", "", enum, flags=re.S), flags=re.M)
+    assert [n.lower() for n in names] == [n for n, _ in E.FB_PARTS]
+    assert int(re.search(r"#define PM_FB_HEAD_WORDS (\d+)", hdr).group(1)) == len(E.FB_HEAD)
+    dev = open(os.path.join(ROOT, "protocol_amd", "csrc", "pm_device.h")).read()
+    assert int(re.search(r"PM_PROP_ROW = (\d+);", dev).group(1)) == E.PROP_ROW
+    assert int(re.search(r"PM_PROP_SLOTS = (\d+);", dev).group(1)) == E.PROP_SLOTS
 
 
 def test_engine_resources_are_taken_and_given_back_in_one_header():
