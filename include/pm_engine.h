@@ -49,8 +49,9 @@ extern "C" {
                             + pm_probe_configs / pm_config_overlap (probes and configuration overlap),
                             + pm_liveness_enable / _set / _get / _sweep / _transitions (liveness sweep),
                             + pm_discovery_sync (discovery sync),
-                            + pm_metrics_enable / _ingest / _totals / _rows (metrics ledger): compatible additions, the version
-                            stays 3 */
+                            + pm_metrics_enable / _ingest / _totals / _rows (metrics ledger),
+                            + pm_rollout_enable / _ingest / _get / _summary / _tasks / _groups / _workers, pm_host_task_state
+                            (rollout ledger): compatible additions, the version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -839,6 +840,87 @@ int32_t pm_metrics_totals(pm_engine*, double* sum, uint32_t* count, uint32_t cap
 int32_t pm_metrics_rows(pm_engine*, const uint32_t* rows /* NULL = all */, uint32_t n, pm_mx_row* out, uint32_t cap,
                         uint32_t* n_out);
 
+/* ---- rollout ledger (kernels in pm_rollout.inc) -----------------------------------------------------------------------------
+ * What every node REPORTS against what it was GIVEN.  The heartbeat route stores the node's reported task_id and task_state
+ * (api/routes/heartbeat.rs:54-73 -> NodeStore::update_node_task, store/domains/node_store.rs:339-377), and the host reads them
+ * back with a scan over every node: nodes_per_task counts node.task_id (metrics/sync_service.rs:243-267), the task_state gauge
+ * and GET /nodes show the same record.  The engine knows the other side — the task every live group has claimed — so the join
+ * is made here: which groups have every member RUNNING the group's task, which nodes lag, report another task or nothing, how
+ * many report a task that no longer exists.  (pm_task_report.workers_running is the ASSIGNED count; pm_ro_task_row.reporters
+ * is the REPORTED one.  They differ while a rollout is in flight.)  Off by default; with it off nothing of the engine changes.
+ *
+ * THE LEDGER: two device-resident columns per worker row, a u64 id and a state byte (PM_TS_*, or PM_TS_NONE: no report).  The
+ * id is whatever the host derives from the reported task_id text, the same derivation as pm_task_soa.uid; EVERY u64 is a legal
+ * id, absence is carried by the state alone.  pm_rollout_enable(on = 1) creates the columns empty for the rows [0, W) (again:
+ * empties them), on = 0 releases them.  Appended rows start empty; pm_upload_workers(keep_groups = 0) empties every row,
+ * keep_groups = 1 keeps them.  Nothing clears a row when a node dies (the reference does not either: only the heartbeat route
+ * writes these fields), and task uploads, inserts and deletes do not touch the ledger: the reads resolve ids against the task
+ * list as it is at the moment of the call.
+ *
+ * pm_rollout_ingest applies n reports in array order: state < PM_TS_N sets the row to (uid, state), state == PM_TS_NONE clears it
+ * (update_node_task's second arm; uid is ignored).  A worker named more than once ends with its LAST entry, whatever wave or
+ * workgroup handled the earlier ones: a first pass leaves the highest report index per named worker (an integer maximum), a
+ * second one writes where the index matches.  pm_rollout_get reads rows back (a cleared row: uid 0, state PM_TS_NONE).
+ *
+ * THE READS.  A worker's ASSIGNMENT is the claimed task of its live group, as pm_get_groups would report it at this moment (a
+ * pending tick is taken in first, as in pm_metrics_rows); "that id" is the claimed task's pm_task_soa.uid.  An id of all ones
+ * never matches an assignment and always has task = PM_NONE (the claim path treats it as unresolved too).  With duplicate ids
+ * the id names the first live row that carries it, as everywhere in this header.  Every worker has one CLASS:
+ *   PM_RO_IDLE / PM_RO_STRAY       in no group that holds a task: reports nothing / reports a task
+ *   PM_RO_SILENT / PM_RO_OTHER / PM_RO_BEHIND / PM_RO_CONVERGED
+ *                                  its group holds a task: reports nothing / another id / that id in a state other than RUNNING /
+ *                                  that id, RUNNING
+ * pm_rollout_summary: by_class[c] = workers of class c; by_state[s] = rows that report state s, by_state[PM_TS_N] = rows that
+ * report nothing; groups_with_task / groups_converged = live groups that hold a task / whose every member is CONVERGED;
+ * distinct_uids = the rows pm_rollout_tasks would list.
+ * pm_rollout_tasks: one row per distinct id that at least one live group has claimed or at least one row reports, ascending by
+ * uid.  reporters[s] = rows that report the id in state s, whatever their group or status (their sum is the reference's
+ * nodes_per_task); groups / groups_converged = live groups that hold the id / whose every member is CONVERGED; assigned /
+ * converged = the workers of those groups / those of class PM_RO_CONVERGED; task = the id's position in the CURRENT list or
+ * PM_NONE (resolved by the host, for the listed rows only).
+ * pm_rollout_groups: one row per live group that holds a task, in pm_get_groups order (slot = its slot there, task = the
+ * claimed task's position); same[s] = members that report the group's id in state s, other = members that report another id,
+ * silent = members that report nothing: same[0..PM_TS_N) + other + silent == size.
+ * pm_rollout_workers: the workers whose class bit (1u << cls) is in class_mask, ascending by worker index; group_slot = the
+ * worker's slot in pm_get_groups order or PM_NONE; uid / state = its ledger row.
+ * The three lists follow pm_liveness_transitions: *n always, cap < *n or a NULL buffer is PM_ERANGE with nothing copied;
+ * reading consumes nothing.  They are made on the device (a classification pass with per-wave reduced counters, an eight-pass
+ * radix sort of the 64-bit ids — every byte takes part — with a run reduction, ordered compactions); only the count and the n
+ * rows cross to the host.  DETERMINISTIC: integers only, every output is bit-identical from call to call and independent of
+ * the number of workgroups.  Nothing is cached between calls.
+ *
+ * ERRORS.  PM_ESTATE: the ledger is off; a stepwise tick is in progress; dist_world > 1 (and pm_dist_configure(world > 1)
+ * while it is on); no workers uploaded; (the four reads) the task table was uploaded without ids.  PM_EINVAL: a null
+ * argument; a state that is neither < PM_TS_N nor PM_TS_NONE; class_mask == 0 or a bit at or above PM_RO_N.  PM_ERANGE: a
+ * worker index >= W; a list buffer too small.  Everything is checked on the host first: a refused call leaves the ledger as it
+ * was.  No rollout call consumes a pending delta, compacts groups, clears a cache flag or changes what the next tick does. */
+enum { PM_TS_PENDING = 0, PM_TS_PULLING, PM_TS_RUNNING, PM_TS_COMPLETED, PM_TS_FAILED, PM_TS_PAUSED, PM_TS_RESTARTING,
+       PM_TS_UNKNOWN, PM_TS_N = 8 };            /* TaskState, shared/src/models/task.rs:12-22, in its order */
+#define PM_TS_NONE 255u                         /* no report: update_node_task's "clear" arm (node_store.rs:369-372) */
+enum { PM_RO_IDLE = 0,      /* in no group that holds a task, reports nothing */
+       PM_RO_STRAY = 1,     /* in no group that holds a task, reports a task */
+       PM_RO_SILENT = 2,    /* its group holds a task, reports nothing */
+       PM_RO_OTHER = 3,     /* ... reports another id */
+       PM_RO_BEHIND = 4,    /* ... reports that id, state != RUNNING */
+       PM_RO_CONVERGED = 5, /* ... reports that id, RUNNING */
+       PM_RO_N = 6 };
+typedef struct pm_ro_report { uint32_t worker, state; uint64_t uid; } pm_ro_report;            /* 16 B */
+typedef struct pm_ro_summary { uint32_t by_class[PM_RO_N]; uint32_t by_state[PM_TS_N + 1];    /* [PM_TS_N] = no report */
+                               uint32_t groups_with_task, groups_converged, distinct_uids; } pm_ro_summary;
+typedef struct pm_ro_task_row { uint64_t uid; uint32_t task /* position in the CURRENT list, PM_NONE = not in it */;
+                                uint32_t groups, groups_converged, assigned, converged;
+                                uint32_t reporters[PM_TS_N]; uint32_t _pad; } pm_ro_task_row;  /* 64 B */
+typedef struct pm_ro_group_row { uint64_t group_id; uint32_t slot, config, task, size;
+                                 uint32_t same[PM_TS_N]; uint32_t other, silent; } pm_ro_group_row; /* 64 B */
+typedef struct pm_ro_worker_row { uint32_t worker, group_slot; uint64_t uid; uint8_t cls, state; uint16_t _pad; uint32_t _pad2; } pm_ro_worker_row; /* 24 B */
+int32_t pm_rollout_enable(pm_engine*, uint32_t on);
+int32_t pm_rollout_ingest(pm_engine*, const pm_ro_report* reports, uint32_t n);
+int32_t pm_rollout_get(pm_engine*, const uint32_t* idx, uint32_t n, uint64_t* uid, uint8_t* state /* either may be NULL */);
+int32_t pm_rollout_summary(pm_engine*, pm_ro_summary* out);
+int32_t pm_rollout_tasks(pm_engine*, pm_ro_task_row* rows, uint32_t cap, uint32_t* n);
+int32_t pm_rollout_groups(pm_engine*, pm_ro_group_row* rows, uint32_t cap, uint32_t* n);
+int32_t pm_rollout_workers(pm_engine*, uint32_t class_mask, pm_ro_worker_row* rows, uint32_t cap, uint32_t* n);
+
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).
  * task_of_worker[w] = task index or PM_NONE; applicable_count[w] = number of applicable tasks the
@@ -1032,6 +1114,9 @@ int32_t pm_host_volume_vars(const char* in, const char* group_id, char* out, siz
 int32_t pm_host_upload_name_vars(const char* in, const char* group_id, uint32_t group_size, uint32_t group_index,
                                  uint64_t upload_count, char* out, size_t cap, size_t* needed);
 uint32_t pm_host_last_file_idx(const char* total_upload_count);
+/* TaskState::from(&str) (shared/src/models/task.rs:24-37): the eight names exactly as written there, anything else (another
+ * case, surrounding blanks, NULL) is PM_TS_UNKNOWN. */
+uint32_t pm_host_task_state(const char* s);
 
 uint32_t pm_abi_version(void);
 

@@ -252,6 +252,33 @@ struct MxRowsArgs {
   pm_mx_row* out;
 };
 
+// rollout ledger (pm_rollout.inc).  A group slot is an index into the host's list as it stands (tombstones included); what the
+// reads report is RoGroup::slot, the slot pm_get_groups would number it.
+static constexpr uint32_t PM_RO_CHUNK = 1024;             // keys of one radix chunk: fixed, so the sort does not depend on the grid
+static constexpr uint32_t PM_RO_GCNT = PM_TS_N + 2;       // a group's counters: same[PM_TS_N], other, silent
+static constexpr uint32_t PM_RO_CLAIM = 0x80000000u;      // a sorted key's side word: a group's claim (| list slot), else a reporter's state
+static constexpr uint32_t PM_RO_CENSUS = PM_RO_N + PM_TS_N + 2;  // by_class, by_state (+ no report), groups_converged
+struct RoGroup {  // 32 bytes, one per entry of the host's list
+  uint64_t id, uid;   // the group's id; the claimed task's id
+  uint32_t cfg, task;  // configuration; the claimed task's position in the current list, PM_NONE: it holds none
+  uint32_t size;
+  uint32_t slot;      // its slot in pm_get_groups order, PM_NONE: dissolved
+};
+struct RoPrepArgs {
+  uint32_t W, G;
+  const int32_t* group_of;  // [W] host truth, -1 = in no group
+  const RoGroup* g;         // [G]
+  const uint64_t* uid;      // [W] the ledger
+  const uint8_t* state;     // [W]
+  uint8_t* cls;             // [W] out: PM_RO_*
+  uint32_t* g_cnt;          // [G * PM_RO_GCNT] zeroed; out
+  uint32_t* census;         // [PM_RO_CENSUS] zeroed; out
+  uint32_t* flag;           // [W + G] out: row w reports / list entry g is listed
+  const uint32_t* off;      // [W + G + 1] the flags' exclusive scan (the emit pass)
+  uint64_t* key;            // [N] out: the ids of the reporters, behind them those of the claims
+  uint32_t* val;            // [N] out: the state, or PM_RO_CLAIM | list slot
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -514,6 +541,26 @@ void launch_mx_radix_pass(const uint32_t* ser_in, const double* val_in, uint32_t
                           uint32_t* hist_scan, uint32_t* ser_out, double* val_out, hipStream_t s);
 void launch_mx_sums(const uint32_t* ser_sorted, const double* val_sorted, uint32_t N, uint32_t n_series, double* sum,
                     uint32_t* count, hipStream_t s);
+// rollout ledger (pm_rollout.inc)
+void launch_ro_fill(uint64_t* uid, uint8_t* state, uint32_t* last, uint32_t first, uint32_t end, hipStream_t s);
+// the n reports in array order, last entry of a worker wins; `last` [W] is zero before and after
+void launch_ro_ingest(const pm_ro_report* r, uint32_t n, uint32_t* last, uint64_t* uid, uint8_t* state, hipStream_t s);
+void launch_ro_get(const uint32_t* idx, uint32_t n, const uint64_t* uid, const uint8_t* state, uint64_t* out_uid, uint8_t* out_state,
+                   hipStream_t s);
+void launch_ro_classify(const RoPrepArgs& a, hipStream_t s);
+void launch_ro_emit(const RoPrepArgs& a, hipStream_t s);
+// one radix pass over digit (key >> shift) & 255: hist [256][chunks] (digit-major), scanned into `hist_scan`
+void launch_ro_radix_pass(const uint64_t* key_in, const uint32_t* val_in, uint32_t N, uint32_t shift, uint32_t* hist,
+                          uint32_t* hist_scan, uint64_t* key_out, uint32_t* val_out, hipStream_t s);
+void launch_ro_heads(const uint64_t* key, uint32_t N, uint32_t* head, hipStream_t s);
+void launch_ro_starts(const uint32_t* head, const uint32_t* head_off, uint32_t N, uint32_t* start, hipStream_t s);
+// one row per run of equal keys: start [D] the runs' first entries
+void launch_ro_reduce(const uint64_t* key, const uint32_t* val, uint32_t N, const uint32_t* start, uint32_t D, const RoGroup* g,
+                      const uint32_t* g_cnt, pm_ro_task_row* rows, hipStream_t s);
+void launch_ro_group_rows(const RoGroup* g, uint32_t G, const uint32_t* listed, const uint32_t* off, const uint32_t* g_cnt,
+                          pm_ro_group_row* rows, hipStream_t s);
+void launch_ro_worker_flags(const uint8_t* cls, uint32_t W, uint32_t class_mask, uint32_t* flag, hipStream_t s);
+void launch_ro_worker_rows(const RoPrepArgs& a, const uint32_t* flag, const uint32_t* off, pm_ro_worker_row* rows, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -43,6 +43,7 @@ int32_t pm_dist_configure(pm_engine* e, uint32_t rank, uint32_t world, const uin
   if (world > 1 && e->chg.on) return set_error(PM_ESTATE, "the assignment change feed is on: it does not cover multi-GPU engines");
   if (world > 1 && e->live.on) return set_error(PM_ESTATE, "liveness is on: it does not cover multi-GPU engines");
   if (world > 1 && e->mx.on) return set_error(PM_ESTATE, "the metrics ledger is on: it does not cover multi-GPU engines");
+  if (world > 1 && e->ro.on) return set_error(PM_ESTATE, "the rollout ledger is on: it does not cover multi-GPU engines");
   if (world > 1 && !e->have_workers) return set_error(PM_ESTATE, "workers must be uploaded first");
   if (world > 1 && e->W && !shard_of_worker) return set_error(PM_EINVAL, "null shard column");
   e->dist_rank = world > 1 ? rank : 0;

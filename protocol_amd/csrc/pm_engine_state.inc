@@ -81,6 +81,34 @@ struct Metrics {
   std::vector<uint32_t> h_gcfg;
 };
 
+// ---- rollout ledger (pm_engine_rollout.inc): the reported task id and state of the workers [0, W); rows behind W hold nothing
+// yet (the next rollout call fills them empty).  Everything else is scratch of one call: nothing is cached between reads.
+struct Rollout {
+  bool on = false;
+  bool reinit = false;        // an upload dropped the row identities: every row is emptied by the next rollout call
+  uint32_t W = 0;
+  DevBuf<uint64_t> uid;       // [W] the ledger
+  DevBuf<uint8_t> state;
+  DevBuf<uint32_t> last;      // [W] the ingest's highest report index per worker: zero between calls
+  DevBuf<pm_ro_report> reports;
+  DevBuf<uint32_t> idx;       // pm_rollout_get: the indices, ...
+  DevBuf<uint64_t> get_uid;   // ... the gathered ids and states
+  DevBuf<uint8_t> get_state;
+  DevBuf<int32_t> gof;        // the join's other side: the host's group_of, its group list
+  DevBuf<RoGroup> g;
+  DevBuf<uint8_t> cls;        // [W]
+  DevBuf<uint32_t> cnt;       // [G * PM_RO_GCNT] the groups' counters, behind them [PM_RO_CENSUS] the census
+  DevBuf<uint32_t> flag, off;  // [W + G] (+ 1): reports / is listed, and the scan; the lists' flags and offsets
+  DevBuf<uint64_t> key[2];    // the sort's keys and side words, ping-pong
+  DevBuf<uint32_t> val[2], hist, hist_scan, head, head_off, start;
+  DevBuf<pm_ro_task_row> task_rows;
+  DevBuf<pm_ro_group_row> group_rows;
+  DevBuf<pm_ro_worker_row> worker_rows;
+  PinBuf<uint32_t> h_pin;     // [0] a scan's total, [1, 1 + PM_RO_CENSUS) the census
+  std::vector<RoGroup> h_g;
+  std::vector<uint8_t> h_state;
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -315,4 +343,5 @@ struct pm_engine {
   Liveness live;
   Discovery disc;
   Metrics mx;
+  Rollout ro;
 };

@@ -268,6 +268,18 @@ static int32_t tasks_insert_front_locked(pm_engine* e, const pm_task_soa* t) {
   return PM_OK;
 }
 
+// the id map (id -> handle of the first live row in list order that carries it), built when first asked for: pm_tasks_delete,
+// the rollout ledger's task table
+static void ensure_uid_map(pm_engine* e) {
+  if (e->uid_map_valid) return;
+  e->uid_to_u.clear();
+  e->uid_to_u.reserve(size_t(e->T) * 2);
+  for (uint32_t u = e->t_cap; u-- > e->t_lo;)  // descending: the first occurrence in list order wins
+    if ((e->h_tlive[u >> 6] >> (u & 63u)) & 1ull) e->uid_to_u[e->h_tuid[u]] = u;
+  e->uid_map_valid = true;
+  e->uid_dup = e->uid_to_u.size() != e->T;
+}
+
 // on_task_deleted (node_groups/mod.rs:1245-1325): the tasks leave the table (tombstones: nothing moves) and every
 // group that had claimed one of them is dissolved (:1259-1288).  Unknown ids are ignored.
 int32_t pm_tasks_delete(pm_engine* e, const uint64_t* uids, uint32_t n, uint32_t* n_deleted) {
@@ -279,14 +291,7 @@ int32_t pm_tasks_delete(pm_engine* e, const uint64_t* uids, uint32_t n, uint32_t
   if (!e->tasks_have_uid) return set_error(PM_ESTATE, "the task table carries no ids (pm_task_soa.uid)");
   if (e->dist_phase != 0) return set_error(PM_ESTATE, "a stepwise tick is in progress");
   ABSORB_PENDING(e);
-  if (!e->uid_map_valid) {
-    e->uid_to_u.clear();
-    e->uid_to_u.reserve(size_t(e->T) * 2);
-    for (uint32_t u = e->t_cap; u-- > e->t_lo;)  // descending: the first occurrence in list order wins
-      if ((e->h_tlive[u >> 6] >> (u & 63u)) & 1ull) e->uid_to_u[e->h_tuid[u]] = u;
-    e->uid_map_valid = true;
-    e->uid_dup = e->uid_to_u.size() != e->T;
-  }
+  ensure_uid_map(e);
   // what is to go (nothing is changed yet: everything that can fail comes before the first mutation, so that the
   // host mirror and the device table cannot drift apart on an error return)
   std::vector<uint32_t> slots;  // handles of the deleted tasks

@@ -442,6 +442,15 @@ uint32_t pm_host_last_file_idx(const char* total_upload_count) {
   return v ? uint32_t(v - 1) : 0u;  // saturating_sub(1)
 }
 
+uint32_t pm_host_task_state(const char* s) {
+  // TaskState::from(&str), shared/src/models/task.rs:24-37: a match on the exact text, `"UNKNOWN" | &_` for the rest
+  static const char* const names[PM_TS_N] = {"PENDING", "PULLING", "RUNNING", "COMPLETED", "FAILED", "PAUSED", "RESTARTING", "UNKNOWN"};
+  if (!s) return PM_TS_UNKNOWN;
+  for (uint32_t k = 0; k < PM_TS_N; ++k)
+    if (!std::strcmp(s, names[k])) return k;
+  return PM_TS_UNKNOWN;
+}
+
 int32_t pm_host_group_vars(const char* in, const pm_group_vars* v, char* out, size_t cap, size_t* needed) {
   if (!in || !v || !v->next_p2p_address || !v->group_id || !v->total_upload_count)
     return pm::set_error(PM_EINVAL, "null argument");

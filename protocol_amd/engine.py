@@ -85,6 +85,22 @@ mx_entry_dt = np.dtype([("series", "<u4"), ("flags", "<u4"), ("value", "<f8")])
 mx_row_dt = np.dtype([("row", "<u4"), ("series", "<u4"), ("value", "<f8"), ("group_id", "<u8"), ("config", "<u4"), ("_pad", "<u4")])
 assert mx_beat_dt.itemsize == 16 and mx_entry_dt.itemsize == 16 and mx_row_dt.itemsize == 32
 MX_MANUAL, MX_ROW_MAX = 0xFFFFFFFF, 1024
+# pm_ro_* and PM_TS_* / PM_RO_* (include/pm_engine.h): rollout ledger
+ro_report_dt = np.dtype([("worker", "<u4"), ("state", "<u4"), ("uid", "<u8")])
+ro_summary_dt = np.dtype([("by_class", "<u4", (6,)), ("by_state", "<u4", (9,)), ("groups_with_task", "<u4"),
+                          ("groups_converged", "<u4"), ("distinct_uids", "<u4")])
+ro_task_row_dt = np.dtype([("uid", "<u8"), ("task", "<u4"), ("groups", "<u4"), ("groups_converged", "<u4"), ("assigned", "<u4"),
+                           ("converged", "<u4"), ("reporters", "<u4", (8,)), ("_pad", "<u4")])
+ro_group_row_dt = np.dtype([("group_id", "<u8"), ("slot", "<u4"), ("config", "<u4"), ("task", "<u4"), ("size", "<u4"),
+                            ("same", "<u4", (8,)), ("other", "<u4"), ("silent", "<u4")])
+ro_worker_row_dt = np.dtype([("worker", "<u4"), ("group_slot", "<u4"), ("uid", "<u8"), ("cls", "u1"), ("state", "u1"),
+                             ("_pad", "<u2"), ("_pad2", "<u4")])
+assert (ro_report_dt.itemsize, ro_summary_dt.itemsize, ro_task_row_dt.itemsize, ro_group_row_dt.itemsize,
+        ro_worker_row_dt.itemsize) == (16, 72, 64, 64, 24)
+TS_NAMES = ("PENDING", "PULLING", "RUNNING", "COMPLETED", "FAILED", "PAUSED", "RESTARTING", "UNKNOWN")
+TS_RUNNING, TS_UNKNOWN, TS_N, TS_NONE = 2, 7, 8, 255
+RO_IDLE, RO_STRAY, RO_SILENT, RO_OTHER, RO_BEHIND, RO_CONVERGED, RO_N = 0, 1, 2, 3, 4, 5, 6
+RO_CHUNK = 1024    # PM_RO_CHUNK (csrc/pm_device.h): the keys of one radix chunk of the rollout ledger's id sort
 MX_CHUNK = 1024    # PM_MX_CHUNK (csrc/pm_device.h): the entries of one radix chunk of pm_metrics_totals
 # neighbour rows (csrc/pm_device.h, csrc/pm_propose.inc; tests/test_host_helpers.py holds each to the source): the flags word of
 # near_row_finish, the two geometries rows run at (slot bits, certificate band, window), the regimes of near_row_bulk4_body
@@ -181,6 +197,8 @@ EXPORTS = [
     "pm_liveness_enable", "pm_liveness_set", "pm_liveness_get", "pm_liveness_sweep", "pm_liveness_transitions",
     "pm_discovery_sync",
     "pm_metrics_enable", "pm_metrics_ingest", "pm_metrics_totals", "pm_metrics_rows",
+    "pm_rollout_enable", "pm_rollout_ingest", "pm_rollout_get", "pm_rollout_summary", "pm_rollout_tasks", "pm_rollout_groups",
+    "pm_rollout_workers", "pm_host_task_state",
 ]
 
 _lib = None
@@ -267,6 +285,13 @@ def lib() -> C.CDLL:
         L.pm_metrics_ingest.argtypes = [vp, vp, u32, vp, u32, u32]
         L.pm_metrics_totals.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
         L.pm_metrics_rows.argtypes = [vp, vp, u32, vp, u32, C.POINTER(u32)]
+        L.pm_rollout_enable.argtypes = [vp, u32]
+        L.pm_rollout_ingest.argtypes = [vp, vp, u32]
+        L.pm_rollout_get.argtypes = [vp, vp, u32, vp, vp]
+        L.pm_rollout_summary.argtypes = [vp, vp]
+        L.pm_rollout_tasks.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_rollout_groups.argtypes = [vp, vp, u32, C.POINTER(u32)]
+        L.pm_rollout_workers.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -281,10 +306,12 @@ def lib() -> C.CDLL:
         L.pm_host_to_lowercase.argtypes = [C.c_char_p, C.c_char_p, sz, C.POINTER(sz)]
         L.pm_host_last_file_idx.argtypes = [C.c_char_p]
         L.pm_host_last_file_idx.restype = u32
+        L.pm_host_task_state.argtypes = [C.c_char_p]
+        L.pm_host_task_state.restype = u32
         for name in EXPORTS:
             fn = getattr(L, name)
             if name not in ("pm_last_error", "pm_abi_version", "pm_engine_destroy", "pm_engine_config_default",
-                            "pm_host_last_file_idx"):
+                            "pm_host_last_file_idx", "pm_host_task_state"):
                 fn.restype = i32
         _lib = L
     return _lib
@@ -743,6 +770,51 @@ class Engine:
         return out[:n.value]
 
     # ---- phases
+    # ---- rollout ledger
+    def rollout_enable(self, on: bool = True):
+        """pm_rollout_enable: on = empty columns for the rows [0, W) (again: empties them); off releases them"""
+        check(lib().pm_rollout_enable(self._h, int(on)))
+
+    def rollout_ingest(self, reports):
+        """pm_rollout_ingest: reports (ro_report_dt) applied in order; state TS_NONE clears the row; the last entry of a worker wins"""
+        r = np.ascontiguousarray(reports, dtype=ro_report_dt)
+        check(lib().pm_rollout_ingest(self._h, r.ctypes.data if len(r) else None, len(r)))
+
+    def rollout_get(self, idx=None):
+        """pm_rollout_get -> (uid uint64 [n], state uint8 [n]) of the rows idx (None: every row)"""
+        idx = np.arange(self.W, dtype=np.uint32) if idx is None else _arr(idx, np.uint32)
+        uid = np.zeros(len(idx), dtype=np.uint64)
+        st = np.zeros(len(idx), dtype=np.uint8)
+        check(lib().pm_rollout_get(self._h, idx.ctypes.data if len(idx) else None, len(idx), uid.ctypes.data, st.ctypes.data))
+        return uid, st
+
+    def rollout_summary(self) -> np.ndarray:
+        """pm_rollout_summary -> one ro_summary_dt record"""
+        out = np.zeros(1, dtype=ro_summary_dt)
+        check(lib().pm_rollout_summary(self._h, out.ctypes.data))
+        return out[0]
+
+    def _rollout_list(self, call, dt) -> np.ndarray:
+        n = C.c_uint32(0)
+        rc = call(None, 0, C.byref(n))
+        if rc < 0 and rc != -5:  # (PM_ERANGE with *n set: the size query)
+            check(rc)
+        out = np.zeros(max(n.value, 1), dtype=dt)
+        check(call(out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def rollout_tasks(self) -> np.ndarray:
+        """pm_rollout_tasks -> ro_task_row_dt [n]: one row per distinct claimed or reported id, ascending by uid"""
+        return self._rollout_list(lambda p, cap, n: lib().pm_rollout_tasks(self._h, p, cap, n), ro_task_row_dt)
+
+    def rollout_groups(self) -> np.ndarray:
+        """pm_rollout_groups -> ro_group_row_dt [n]: one row per live group that holds a task, in get_groups order"""
+        return self._rollout_list(lambda p, cap, n: lib().pm_rollout_groups(self._h, p, cap, n), ro_group_row_dt)
+
+    def rollout_workers(self, class_mask: int = (1 << RO_N) - 1) -> np.ndarray:
+        """pm_rollout_workers -> ro_worker_row_dt [n]: the workers whose class bit is in class_mask, ascending"""
+        return self._rollout_list(lambda p, cap, n: lib().pm_rollout_workers(self._h, int(class_mask), p, cap, n), ro_worker_row_dt)
+
     def compat_masks(self) -> np.ndarray:
         out = np.zeros(self.W, dtype=np.uint64)
         check(lib().pm_compat_masks(self._h, out.ctypes.data if self.W else None))

@@ -171,3 +171,8 @@ def upload_name_vars(text: str, group_id, group_size: int, group_index: int, upl
 
 def last_file_idx(total_upload_count: str) -> int:
     return int(E.lib().pm_host_last_file_idx(total_upload_count.encode()))
+
+
+def task_state(name) -> int:
+    """TaskState::from(&str) (task.rs:24-37) as PM_TS_*: the eight names exactly, anything else UNKNOWN."""
+    return int(E.lib().pm_host_task_state(None if name is None else name.encode()))

@@ -468,6 +468,45 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::vector<SyncedMetric> synced_metrics(const std::map<std::string, std::string>& task_names);
   size_t queued_metric_beats() const;  // (what the tests look at)
 
+  // ---- rollout (INTEGRATION.md "Rollout"; gpu_match_rollout.cpp): the task fields the heartbeat route stores per node
+  // (api/routes/heartbeat.rs:54-73 -> NodeStore::update_node_task, node_store.rs:339-377) over the engine's rollout ledger, and the
+  // reads that join them with the standing groups.  report_task applies update_node_task's match: both options present set the
+  // report, anything else clears it.  The state goes through pm_host_task_state (TaskState::from); the id is task_uid of the text
+  // when it is a UUID, else a 64-bit FNV-1a of its bytes — A DEVIATION: two texts whose 64-bit ids collide are one id to the
+  // ledger (the reference keys by the text).  The plugin remembers the text of every reported id, so that ids its task list does
+  // not carry (never, or no longer) render with their text; an entry goes when a task report no longer lists the id.  The writes queue
+  // under the plugin's lock and go out in one pm_rollout_ingest per flush; every read flushes first.  An address the node table
+  // does not hold is ignored (the route answers such a node before it gets here).
+  struct NodesPerTask {  // one set_nodes_per_task call of the sync service (metrics/sync_service.rs:258-266)
+    std::string task_id, task_name;  // "unknown" where the task list has no such id
+    uint32_t count = 0;
+  };
+  struct TaskRollout {
+    std::string task_id, task_name;
+    pm_ro_task_row row;
+  };
+  struct GroupRollout {
+    std::string group_id, configuration_name, task_id;
+    pm_ro_group_row row;
+  };
+  struct NodeRollout {
+    std::string address;
+    uint32_t cls = 0, state = PM_TS_NONE;
+    std::optional<std::string> task_id;  // the reported id's text (hex where the plugin has none), nullopt: no report
+  };
+  void enable_rollout();  // pm_rollout_enable(on = 1): empty columns; the queue and the texts start over
+  void report_task(const Address& address, const std::optional<std::string>& task_id, const std::optional<std::string>& task_state);
+  void flush_rollout();
+  std::vector<NodesPerTask> nodes_per_task();  // ascending by the 64-bit id (the reference's order is a HashMap's)
+  pm_ro_summary rollout_summary();
+  std::vector<TaskRollout> task_rollout();
+  std::vector<GroupRollout> group_rollout();
+  std::vector<NodeRollout> rollout_nodes(uint32_t class_mask);
+  size_t queued_task_reports() const;  // (what the tests look at)
+  std::pair<std::vector<uint64_t>, std::vector<uint8_t>> reported_tasks(const std::vector<uint32_t>& rows);  // the ledger's rows as stored
+  size_t remembered_task_texts() const;
+  static uint64_t reported_task_uid(const std::string& task_id);
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -577,6 +616,16 @@ class GpuMatchPlugin : public SchedulerPlugin {
   void queue_metrics(const Address& address, uint32_t kind, const std::vector<MetricEntry>& entries);
   void flush_metrics_locked();
   std::vector<pm_mx_row> metric_rows_locked(const uint32_t* rows, uint32_t n);
+  // rollout (gpu_match_rollout.cpp): the queue and the texts under rollout_mu_ (LOCK ORDER: nodes, tasks, rollout, the engine)
+  struct RolloutQueue {
+    std::vector<pm_ro_report> reports;
+    std::unordered_map<uint64_t, std::string> texts;  // id -> reported text, of every id the last task report listed or reported since
+  };
+  mutable std::mutex rollout_mu_;
+  RolloutQueue rollout_;
+  void flush_rollout_locked();
+  std::vector<pm_ro_task_row> rollout_task_rows_locked();
+  std::string rollout_text_locked(uint64_t uid, uint32_t task) const;
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

@@ -188,6 +188,22 @@ int32_t pmx_metrics_for_node(pmx_plugin*, const char* address, char* out, size_t
 int32_t pmx_synced_metrics(pmx_plugin*, const char* const* task_ids, const char* const* task_names, uint32_t n_tasks, char* out,
                            size_t cap, size_t* needed);
 
+/* ---- rollout (pm_plugin_rollout_c.cpp): GpuMatchPlugin::enable_rollout / report_task / flush_rollout and the reads.  task_id and
+ * task_state may be NULL (None): update_node_task's match — both present set the report, anything else clears it.  The writes
+ * queue; pmx_flush_rollout and every read send the queue in one ingest.  The texts, numbers in decimal:
+ * pmx_nodes_per_task "<task id>\t<task name or unknown>\t<count>" per reported id; pmx_task_rollout "<task id>\t<task name>\t
+ * <position or ->\t<groups>\t<groups converged>\t<assigned>\t<converged>" and the eight reporter counts; pmx_group_rollout
+ * "<group id>\t<configuration name>\t<task id>\t<size>", the eight same counts, other, silent; pmx_rollout_nodes "<address>\t
+ * <class>\t<state or ->\t<reported task id or ->" ascending by row.  pmx_rollout_summary fills the engine's struct. */
+int32_t pmx_enable_rollout(pmx_plugin*);
+int32_t pmx_report_task(pmx_plugin*, const char* address, const char* task_id /* NULL = None */, const char* task_state /* NULL = None */);
+int32_t pmx_flush_rollout(pmx_plugin*);
+int32_t pmx_nodes_per_task(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_rollout_summary(pmx_plugin*, pm_ro_summary* out);
+int32_t pmx_task_rollout(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_group_rollout(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_rollout_nodes(pmx_plugin*, uint32_t class_mask, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

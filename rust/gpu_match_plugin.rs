@@ -294,6 +294,83 @@ pub const MXB_MERGE: u32 = 1;
 pub const MXB_DELETE: u32 = 2;
 pub const MXF_MAX: u32 = 1;
 
+/// pm_ro_report / pm_ro_summary / pm_ro_task_row / pm_ro_group_row / pm_ro_worker_row (include/pm_engine.h): the rollout ledger's
+/// batch and its reads
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct pm_ro_report {
+    pub worker: u32,
+    pub state: u32,
+    pub uid: u64,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_ro_summary {
+    pub by_class: [u32; 6],
+    pub by_state: [u32; 9],
+    pub groups_with_task: u32,
+    pub groups_converged: u32,
+    pub distinct_uids: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_ro_task_row {
+    pub uid: u64,
+    pub task: u32,
+    pub groups: u32,
+    pub groups_converged: u32,
+    pub assigned: u32,
+    pub converged: u32,
+    pub reporters: [u32; 8],
+    pub _pad: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_ro_group_row {
+    pub group_id: u64,
+    pub slot: u32,
+    pub config: u32,
+    pub task: u32,
+    pub size: u32,
+    pub same: [u32; 8],
+    pub other: u32,
+    pub silent: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_ro_worker_row {
+    pub worker: u32,
+    pub group_slot: u32,
+    pub uid: u64,
+    pub cls: u8,
+    pub state: u8,
+    pub _pad: u16,
+    pub _pad2: u32,
+}
+
+/// PM_TS_* (TaskState, shared/src/models/task.rs:12-22, in its order), PM_TS_NONE, PM_RO_*
+pub const TS_PENDING: u32 = 0;
+pub const TS_PULLING: u32 = 1;
+pub const TS_RUNNING: u32 = 2;
+pub const TS_COMPLETED: u32 = 3;
+pub const TS_FAILED: u32 = 4;
+pub const TS_PAUSED: u32 = 5;
+pub const TS_RESTARTING: u32 = 6;
+pub const TS_UNKNOWN: u32 = 7;
+pub const TS_N: usize = 8;
+pub const TS_NONE: u32 = 255;
+pub const RO_IDLE: u32 = 0;
+pub const RO_STRAY: u32 = 1;
+pub const RO_SILENT: u32 = 2;
+pub const RO_OTHER: u32 = 3;
+pub const RO_BEHIND: u32 = 4;
+pub const RO_CONVERGED: u32 = 5;
+pub const RO_N: u32 = 6;
+
 /// PM_NS_* (NodeStatus, models/node.rs:75-85, in its order), PM_LIVE_TTL_MS, PM_LIVE_GIVE_UP
 pub const NS_DISCOVERED: u8 = 0;
 pub const NS_WAITING: u8 = 1;
@@ -510,6 +587,14 @@ extern "C" {
                          n_series: u32) -> i32;
     fn pm_metrics_totals(e: *mut c_void, sum: *mut f64, count: *mut u32, cap: u32, n_series: *mut u32) -> i32;
     fn pm_metrics_rows(e: *mut c_void, rows: *const u32, n: u32, out: *mut pm_mx_row, cap: u32, n_out: *mut u32) -> i32;
+    fn pm_rollout_enable(e: *mut c_void, on: u32) -> i32;
+    fn pm_rollout_ingest(e: *mut c_void, reports: *const pm_ro_report, n: u32) -> i32;
+    fn pm_rollout_get(e: *mut c_void, idx: *const u32, n: u32, uid: *mut u64, state: *mut u8) -> i32;
+    fn pm_rollout_summary(e: *mut c_void, out: *mut pm_ro_summary) -> i32;
+    fn pm_rollout_tasks(e: *mut c_void, rows: *mut pm_ro_task_row, cap: u32, n: *mut u32) -> i32;
+    fn pm_rollout_groups(e: *mut c_void, rows: *mut pm_ro_group_row, cap: u32, n: *mut u32) -> i32;
+    fn pm_rollout_workers(e: *mut c_void, class_mask: u32, rows: *mut pm_ro_worker_row, cap: u32, n: *mut u32) -> i32;
+    fn pm_host_task_state(s: *const c_char) -> u32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -649,6 +734,44 @@ struct MetricsQueue {
     keys: Vec<(String, String)>,   // series -> (task id or "manual", cleaned label)
 }
 
+/// the task reports queued since the last flush, and the text of every reported id (pruned to what the last task report listed)
+#[derive(Default)]
+struct RolloutQueue {
+    reports: Vec<pm_ro_report>,
+    texts: HashMap<u64, String>,
+}
+
+/// one set_nodes_per_task call of the sync service (metrics/sync_service.rs:258-266)
+#[derive(Default, Debug, Clone, PartialEq)]
+pub struct NodesPerTask {
+    pub task_id: String,
+    pub task_name: String,   // "unknown" where the task list has no such id
+    pub count: u32,
+}
+
+#[derive(Default, Debug, Clone)]
+pub struct TaskRollout {
+    pub task_id: String,
+    pub task_name: String,
+    pub row: pm_ro_task_row,
+}
+
+#[derive(Default, Debug, Clone)]
+pub struct GroupRollout {
+    pub group_id: String,
+    pub configuration_name: String,
+    pub task_id: String,
+    pub row: pm_ro_group_row,
+}
+
+#[derive(Default, Debug, Clone)]
+pub struct NodeRollout {
+    pub address: String,
+    pub cls: u32,
+    pub state: u32,
+    pub task_id: Option<String>,   // the reported id's text (hex where the plugin has none), None: no report
+}
+
 /// one record_compute_task_gauge call of sync_metrics_from_redis (gpu_match_metrics.cpp's SyncedMetric)
 #[derive(Default, Debug, Clone)]
 pub struct SyncedMetric {
@@ -677,6 +800,8 @@ pub struct GpuMatchPlugin {
     tasks: parking_lot::RwLock<Vec<Task>>,   // get_all_tasks order: the engine reports positions in this Vec
     /// the metrics ledger's queue and interner (LOCK ORDER: nodes, metrics, the engine)
     metrics: parking_lot::Mutex<MetricsQueue>,
+    /// the rollout ledger's queue and texts (LOCK ORDER: nodes, tasks, rollout, the engine)
+    rollout: parking_lot::Mutex<RolloutQueue>,
     /// `upload:<node>:<group>:*` key count (scheduler_impl.rs:130-153): stays with the Redis store
     upload_counter: Box<dyn Fn(&Address, &str) -> usize + Send + Sync>,
     /// as in NodeGroupsPlugin (mod.rs:107, 124): the plugins told about every group created / destroyed
@@ -845,7 +970,7 @@ impl GpuMatchPlugin {
                               dist_rank: AtomicU32::new(0),
                               config_names: templates.iter().map(|t| t.name.clone()).collect(),
                               req_models: Vec::new(), nodes: Default::default(), tasks: Default::default(),
-                              metrics: Default::default(),
+                              metrics: Default::default(), rollout: Default::default(),
                               upload_counter, webhook_plugins, republish_on_insert: false,
                               nodes_synced: AtomicBool::new(false), tasks_synced: AtomicBool::new(false),
                               ticked: AtomicBool::new(false), multi_gpu: false };
@@ -2162,6 +2287,175 @@ impl GpuMatchPlugin {
             out.push(m);
         }
         Ok(out)
+    }
+
+    // ---- rollout (INTEGRATION.md "Rollout"): the task fields the heartbeat route stores per node (api/routes/heartbeat.rs:54-73 ->
+    // NodeStore::update_node_task, node_store.rs:339-377) over the engine's rollout ledger, and the reads that join them with the
+    // standing groups.  The writes queue; flush_rollout sends the queue in one pm_rollout_ingest, every read flushes first.
+
+    /// the 64-bit id of a reported task_id text: task_uid of a UUID (hyphenated or the 32 digits alone), else FNV-1a of the bytes.
+    /// A DEVIATION: two texts whose ids collide are one id to the ledger (the reference keys by the text).
+    pub fn reported_task_uid(task_id: &str) -> u64 {
+        if task_id.len() == 32 || task_id.len() == 36 {
+            if let Ok(u) = uuid::Uuid::parse_str(task_id) { return u.as_u64_pair().1; }
+        }
+        task_id.bytes().fold(0xCBF2_9CE4_8422_2325u64, |h, c| (h ^ c as u64).wrapping_mul(0x0000_0100_0000_01B3))
+    }
+
+    /// pm_rollout_enable(on = 1): empty columns; the queue and the texts start over
+    pub fn enable_rollout(&self) -> Result<()> {
+        let _t = self.nodes.read();           // (LOCK ORDER: nodes, tasks, rollout, the engine)
+        let mut q = self.rollout.lock();
+        check(unsafe { pm_rollout_enable(self.engine, 1) })?;
+        *q = RolloutQueue::default();
+        Ok(())
+    }
+
+    /// update_node_task's match (node_store.rs:356-373): both present set the report, anything else clears it
+    pub fn report_task(&self, address: &Address, task_id: Option<&str>, task_state: Option<&str>) {
+        let t = self.nodes.read();
+        let Some(&row) = t.index.get(address) else { return };
+        let mut q = self.rollout.lock();
+        match (task_id, task_state) {
+            (Some(task), Some(state)) => {
+                let uid = Self::reported_task_uid(task);
+                q.texts.entry(uid).or_insert_with(|| task.to_string());   // (the first text of an id stays)
+                let state = CString::new(state).map(|s| unsafe { pm_host_task_state(s.as_ptr()) }).unwrap_or(TS_UNKNOWN);
+                q.reports.push(pm_ro_report { worker: row, state, uid });
+            }
+            _ => q.reports.push(pm_ro_report { worker: row, state: TS_NONE, uid: 0 }),
+        }
+    }
+
+    fn flush_rollout_locked(&self, q: &mut RolloutQueue) -> Result<()> {
+        if q.reports.is_empty() { return Ok(()); }
+        let rc = unsafe { pm_rollout_ingest(self.engine, q.reports.as_ptr(), q.reports.len() as u32) };
+        q.reports.clear();                    // (a refused batch is dropped, not sent again and again)
+        check(rc)
+    }
+
+    pub fn flush_rollout(&self) -> Result<()> {
+        let _t = self.nodes.read();
+        let mut q = self.rollout.lock();
+        self.flush_rollout_locked(&mut q)
+    }
+
+    /// the task report; the texts of ids it no longer lists go (a listed id keeps its text also while the task list carries it: a
+    /// task deleted under its reporters renders with the text they sent)
+    fn rollout_task_rows(&self, tasks: &[Task], q: &mut RolloutQueue) -> Result<Vec<pm_ro_task_row>> {
+        let mut have = 0u32;
+        let rc = unsafe { pm_rollout_tasks(self.engine, std::ptr::null_mut(), 0, &mut have) };
+        if rc != PM_ERANGE { check(rc)?; }
+        let mut out = vec![pm_ro_task_row::default(); have.max(1) as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_rollout_tasks(self.engine, out.as_mut_ptr(), out.len() as u32, &mut got) })?;
+        if got as usize > out.len() { return Err(anyhow!("rollout: the task report grew between two calls")); }
+        out.truncate(got as usize);
+        let mut kept = HashMap::new();
+        for r in &out {
+            if r.task != PM_NONE && r.task as usize >= tasks.len() {
+                return Err(anyhow!("rollout: the engine names a task the plugin has not"));
+            }
+            if let Some(text) = q.texts.remove(&r.uid) { kept.insert(r.uid, text); }
+        }
+        q.texts = kept;
+        Ok(out)
+    }
+
+    fn rollout_text(tasks: &[Task], q: &RolloutQueue, uid: u64, task: u32) -> String {
+        if let Some(t) = tasks.get(task as usize).filter(|_| task != PM_NONE) { return t.id.to_string(); }
+        q.texts.get(&uid).cloned().unwrap_or_else(|| format!("{:x}", uid))
+    }
+
+    pub fn task_rollout(&self) -> Result<Vec<TaskRollout>> {
+        let _t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let mut q = self.rollout.lock();
+        self.flush_rollout_locked(&mut q)?;
+        let rows = self.rollout_task_rows(&tasks, &mut q)?;
+        Ok(rows.into_iter().map(|r| TaskRollout {
+            task_id: Self::rollout_text(&tasks, &q, r.uid, r.task),
+            task_name: if r.task != PM_NONE { tasks[r.task as usize].name.clone() } else { "unknown".to_string() },
+            row: r,
+        }).collect())
+    }
+
+    /// nodes_per_task as the sync service sets it (sync_service.rs:243-267): only tasks with nodes, ascending by the 64-bit id
+    pub fn nodes_per_task(&self) -> Result<Vec<NodesPerTask>> {
+        Ok(self.task_rollout()?.into_iter().filter_map(|t| {
+            let count: u32 = t.row.reporters.iter().sum();
+            (count != 0).then(|| NodesPerTask { task_id: t.task_id, task_name: t.task_name, count })
+        }).collect())
+    }
+
+    pub fn rollout_summary(&self) -> Result<pm_ro_summary> {
+        let _t = self.nodes.read();
+        let mut q = self.rollout.lock();
+        self.flush_rollout_locked(&mut q)?;
+        let mut out = pm_ro_summary::default();
+        check(unsafe { pm_rollout_summary(self.engine, &mut out) })?;
+        Ok(out)
+    }
+
+    pub fn group_rollout(&self) -> Result<Vec<GroupRollout>> {
+        let _t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let mut q = self.rollout.lock();
+        self.flush_rollout_locked(&mut q)?;
+        let mut have = 0u32;
+        let rc = unsafe { pm_rollout_groups(self.engine, std::ptr::null_mut(), 0, &mut have) };
+        if rc != PM_ERANGE { check(rc)?; }
+        let mut rows = vec![pm_ro_group_row::default(); have.max(1) as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_rollout_groups(self.engine, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;
+        if got as usize > rows.len() { return Err(anyhow!("rollout: the group report grew between two calls")); }
+        rows.truncate(got as usize);
+        let mut out = Vec::new();
+        for r in rows {
+            let (Some(cfg), Some(task)) = (self.config_names.get(r.config as usize), tasks.get(r.task as usize)) else {
+                return Err(anyhow!("rollout: the engine names a configuration or a task the plugin has not"));
+            };
+            out.push(GroupRollout { group_id: format!("{:x}", r.group_id), configuration_name: cfg.clone(),
+                                    task_id: task.id.to_string(), row: r });
+        }
+        Ok(out)
+    }
+
+    pub fn rollout_nodes(&self, class_mask: u32) -> Result<Vec<NodeRollout>> {
+        let t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let mut q = self.rollout.lock();
+        self.flush_rollout_locked(&mut q)?;
+        let mut have = 0u32;
+        let rc = unsafe { pm_rollout_workers(self.engine, class_mask, std::ptr::null_mut(), 0, &mut have) };
+        if rc != PM_ERANGE { check(rc)?; }
+        let mut rows = vec![pm_ro_worker_row::default(); have.max(1) as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_rollout_workers(self.engine, class_mask, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;
+        if got as usize > rows.len() { return Err(anyhow!("rollout: the node list grew between two calls")); }
+        rows.truncate(got as usize);
+        // the texts of the reported ids: the task list's where it carries the id (the first row that does), else the remembered one
+        let mut first: HashMap<u64, u32> = HashMap::new();
+        for (k, task) in tasks.iter().enumerate().rev() { first.insert(task_uid(task), k as u32); }
+        let mut out = Vec::new();
+        for r in rows {
+            if r.worker as usize >= t.rows.len() { return Err(anyhow!("rollout: the engine lists a row the plugin does not know")); }
+            let task_id = (r.state as u32 != TS_NONE).then(|| {
+                let task = if r.uid == u64::MAX { PM_NONE } else { first.get(&r.uid).copied().unwrap_or(PM_NONE) };
+                Self::rollout_text(&tasks, &q, r.uid, task)
+            });
+            out.push(NodeRollout { address: t.address_strings[r.worker as usize].clone(), cls: r.cls as u32, state: r.state as u32,
+                                   task_id });
+        }
+        Ok(out)
+    }
+
+    /// the ledger's rows as stored (what the tests look at)
+    pub fn reported_tasks(&self, rows: &[u32]) -> Result<(Vec<u64>, Vec<u8>)> {
+        let mut uid = vec![0u64; rows.len()];
+        let mut state = vec![0u8; rows.len()];
+        check(unsafe { pm_rollout_get(self.engine, rows.as_ptr(), rows.len() as u32, uid.as_mut_ptr(), state.as_mut_ptr()) })?;
+        Ok((uid, state))
     }
 
     /// StatusUpdatePlugin::handle_status_change (status_update_impl.rs:8-39).

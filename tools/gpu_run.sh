@@ -29,6 +29,9 @@
 #   metrics[:<args>]         tools/metrics_probe.py [W] [E] [--bench DIR]: pm_metrics_ingest / _totals / _rows at W rows (100000) x E
 #                            series a row (8), beside each the same call as an unordered_map per node on one host thread
 #                            -> r20_metrics.txt (copy it to profiles/)
+#   rollout[:<args>]         tools/rollout_probe.py [W] [--bench DIR]: pm_rollout_ingest and the four reads at W rows (100000) over the
+#                            groups of a real tick, beside each the same work as a loop on one host thread
+#                            -> r26_rollout.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -153,6 +156,9 @@ PY
     metrics)
       timeout -k 10 300 python tools/metrics_probe.py $arg --out "$out/r20_metrics.txt" > "$out/${n}_metrics.log" 2>&1; echo "metrics rc=$?"
       tail -12 "$out/${n}_metrics.log" ;;
+    rollout)
+      timeout -k 10 300 python tools/rollout_probe.py $arg --out "$out/r26_rollout.txt" > "$out/${n}_rollout.log" 2>&1; echo "rollout rc=$?"
+      tail -12 "$out/${n}_rollout.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
