@@ -921,6 +921,59 @@ int32_t pm_rollout_tasks(pm_engine*, pm_ro_task_row* rows, uint32_t cap, uint32_
 int32_t pm_rollout_groups(pm_engine*, pm_ro_group_row* rows, uint32_t cap, uint32_t* n);
 int32_t pm_rollout_workers(pm_engine*, uint32_t class_mask, pm_ro_worker_row* rows, uint32_t cap, uint32_t* n);
 
+/* ---- node directory (kernels in pm_directory.inc) ---------------------------------------------------------------------------
+ * The store's ORDERED LISTING, paged: NodeStore::get_nodes (store/domains/node_store.rs:163-209) lists every node, stably
+ * sorted Healthy -> Discovered -> everything else -> Dead, and five callers read it: GET /nodes (api/routes/nodes.rs:29-105),
+ * sync_orchestrator_statistics (metrics/sync_service.rs:209-225), sync_chain_with_nodes (status_update/mod.rs:118-142),
+ * process_nodes (:147) and get_uninvited_nodes (node_store.rs:247-282).  With the ledgers on the device a host would otherwise
+ * fetch three whole tables (pm_liveness_get, pm_get_groups, pm_rollout_get), sort and join them; pm_directory makes the list on
+ * the device and hands out ONE WINDOW of it and the counters.  A pure read: there is no enable call, nothing is cached.
+ *
+ * Every worker row in [0, W) is a node (the reference never removes a node from its store).  A row is LISTED if bit `status`
+ * of status_mask is set and its membership matches: PM_DIR_GROUPED = in a live group as pm_get_groups would report at this
+ * moment (a pending tick is taken in first, as pm_rollout_* and pm_metrics_rows do), PM_DIR_UNGROUPED = in none.
+ * ORDER: the listed rows by CLASS, then by base key, then by row index.  The classes are the four levels of the reference's
+ * comparator (node_store.rs:195-206): Healthy, Discovered, {Waiting, Unhealthy, Ejected, Banned, LowBalance} together, Dead.
+ * PM_DIR_BY_ROW: the base key is the row index.  PM_DIR_BY_ADDRESS: the row's addr_rank as the engine holds it (pm_worker_soa,
+ * pm_update_workers, pm_set_addr_ranks); ranks need not be a permutation, every u32 is legal, equal ranks fall back to the
+ * ascending row index.  (DEVIATION: the reference's base order is that of SMEMBERS, which nothing pins; ours is defined.)
+ * OUTPUTS.  *total = listed rows; counts[s] = listed rows of status s, over the whole list, not the window (counts may be
+ * NULL); *n_rows = min(limit, total - offset), 0 when offset >= total (offset + limit is never formed: limit = UINT32_MAX means
+ * "to the end").  The buffer convention is pm_liveness_transitions': *total, counts and *n_rows are always written; cap <
+ * *n_rows, or rows == NULL with *n_rows > 0, is PM_ERANGE with no row copied.  limit = 0 with rows = NULL is the counters-only
+ * query.  Only the window's rows and the counters cross to the host.  A row's group fields are its live group's as
+ * pm_get_groups numbers and reports it; uid / state are the rollout ledger's row, 0 / PM_TS_NONE with the ledger off.
+ * BY_ROW costs a classification pass and one scan (a four-class ordered compaction, no sort); BY_ADDRESS adds a stable radix
+ * sort of the listed rows' 34 key bits.  DETERMINISTIC: integers only, bit-identical from call to call, independent of the
+ * number of workgroups.
+ * ERRORS.  PM_ESTATE: liveness is off (it is the status); a stepwise tick is in progress; dist_world > 1; no workers uploaded.
+ * PM_EINVAL: a null q, total or n_rows; status_mask == 0 or a bit at or above PM_NS_N; an unknown membership or order.
+ * PM_ERANGE: the row buffer too small (above); a table of 2^30 worker rows or more (the four classes' flags are scanned as one
+ * array).  Everything is checked on the host first.  No call consumes anything, compacts groups, clears a cache flag or changes what the
+ * next tick does. */
+enum { PM_DIR_ANY = 0, PM_DIR_GROUPED = 1, PM_DIR_UNGROUPED = 2 };   /* membership */
+enum { PM_DIR_BY_ROW = 0, PM_DIR_BY_ADDRESS = 1 };                   /* order inside a class */
+enum { PM_DC_HEALTHY = 0, PM_DC_DISCOVERED = 1, PM_DC_OTHER = 2, PM_DC_DEAD = 3, PM_DC_N = 4 };
+typedef struct pm_dir_query {
+  uint32_t status_mask;  /* bit s: rows of status PM_NS_s are listed */
+  uint32_t membership;   /* PM_DIR_* : any / in a live group / in none */
+  uint32_t order;        /* PM_DIR_BY_* */
+  uint32_t offset, limit;/* the window [offset, offset + limit) of the ordered list */
+} pm_dir_query;
+typedef struct pm_dir_row {            /* 48 B, padding zero */
+  uint32_t worker;
+  uint8_t status;  /* PM_NS_* */  uint8_t cls; /* PM_DC_* */  uint8_t state; /* PM_TS_* or PM_TS_NONE */  uint8_t _pad;
+  uint32_t counter;                    /* the liveness ledger's unhealthy counter */
+  uint32_t group_slot;                 /* as pm_get_groups numbers them now, or PM_NONE */
+  uint64_t group_id;                   /* PM_NONE (as u64) in no group, as pm_mx_row */
+  uint32_t group_size, config;         /* 0 / 0 in no group */
+  uint32_t task;                       /* the group's claimed task, position in the CURRENT list, or PM_NONE */
+  uint32_t _pad2;
+  uint64_t uid;                        /* the reported task id; 0 with state PM_TS_NONE or rollout off */
+} pm_dir_row;
+int32_t pm_directory(pm_engine*, const pm_dir_query* q, uint32_t* total, uint32_t* counts /* PM_NS_N */,
+                     pm_dir_row* rows, uint32_t cap, uint32_t* n_rows);
+
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).
  * task_of_worker[w] = task index or PM_NONE; applicable_count[w] = number of applicable tasks the

@@ -279,6 +279,34 @@ struct RoPrepArgs {
   uint32_t* val;            // [N] out: the state, or PM_RO_CLAIM | list slot
 };
 
+// node directory (pm_directory.inc): the ordered, paged listing over the liveness ledger, the groups and the rollout ledger
+static constexpr uint32_t PM_DIR_NO_CLASS = 0xFFu;        // DirArgs::cls of a row the query does not list
+struct DirGroup {  // 24 bytes, one per entry of the host's list (tombstones included)
+  uint64_t id;
+  uint32_t cfg, task;  // configuration; the claimed task's position in the current list, PM_NONE: it holds none
+  uint32_t size;
+  uint32_t slot;       // its slot in pm_get_groups order, PM_NONE: dissolved
+};
+struct DirArgs {
+  uint32_t W, G;
+  uint32_t status_mask, membership;  // the query's filter (pm_dir_query)
+  uint32_t offset, n_rows;           // the window [offset, offset + n_rows) of the ordered list
+  const uint8_t* status;     // [W] the liveness ledger
+  const uint32_t* counter;   // [W]
+  const int32_t* group_of;   // [W] host truth, -1 = in no group
+  const DirGroup* g;         // [G]
+  const uint32_t* addr_rank; // [W]
+  const uint64_t* uid;       // [W] the rollout ledger, or nullptr: it is off
+  const uint8_t* state;      // [W]
+  uint8_t* cls;              // [W] out: PM_DC_*, PM_DIR_NO_CLASS: not listed
+  uint32_t* flag;            // [PM_DC_N * W] out, class-major: row w is listed in class c
+  uint32_t* census;          // [PM_NS_N] zeroed; out: listed rows per status
+  const uint32_t* off;       // [PM_DC_N * W + 1] the flags' exclusive scan: a listed row's place in (class, row) order
+  uint32_t* win;             // [n_rows] out (BY_ROW): the window's rows
+  uint64_t* key;             // [total] out (BY_ADDRESS): class << 32 | rank, in (class, row) order
+  uint32_t* val;             // [total] out: the row
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -561,6 +589,12 @@ void launch_ro_group_rows(const RoGroup* g, uint32_t G, const uint32_t* listed, 
                           pm_ro_group_row* rows, hipStream_t s);
 void launch_ro_worker_flags(const uint8_t* cls, uint32_t W, uint32_t class_mask, uint32_t* flag, hipStream_t s);
 void launch_ro_worker_rows(const RoPrepArgs& a, const uint32_t* flag, const uint32_t* off, pm_ro_worker_row* rows, hipStream_t s);
+// node directory (pm_directory.inc)
+void launch_dir_classify(const DirArgs& a, hipStream_t s);
+void launch_dir_window(const DirArgs& a, hipStream_t s);
+void launch_dir_keys(const DirArgs& a, hipStream_t s);
+// rows[k] = the joined record of worker list[k], k < n
+void launch_dir_emit(const DirArgs& a, const uint32_t* list, uint32_t n, pm_dir_row* rows, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -233,6 +233,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_liveness.inc"
 #include "pm_engine_discovery.inc"
 #include "pm_engine_rollout.inc"
+#include "pm_engine_directory.inc"
 
 extern "C" {
 #include "pm_engine_tick.inc"

@@ -1,0 +1,109 @@
+// pm_engine_directory.inc — part of pm_engine.cpp (one translation unit; included in place): the node directory, C ABI:
+// pm_directory (kernels in pm_directory.inc).  Included at file scope.
+//
+// The directory owns no ledger: it joins the liveness ledger (the status), the host's groups and, where it is on, the rollout
+// ledger, per worker row, in the reference's listing order (NodeStore::get_nodes), and hands out one window of the list and
+// the counters.  e->dir is scratch of one call.  Everything is queued on the engine's stream; a call synchronises once for the
+// counters and once more only when it copies rows.  Like the rollout reads it leaves the tick's state alone: no pending delta
+// is consumed, nothing is compacted, no cache flag is cleared.
+extern "C" {
+
+int32_t pm_directory(pm_engine* e, const pm_dir_query* q, uint32_t* total, uint32_t* counts, pm_dir_row* rows, uint32_t cap,
+                     uint32_t* n_rows) {
+  if (!e || !q || !total || !n_rows) return set_error(PM_EINVAL, "null argument");
+  if (!q->status_mask || (q->status_mask >> PM_NS_N)) return set_error(PM_EINVAL, "not a set of node statuses");
+  if (q->membership > PM_DIR_UNGROUPED) return set_error(PM_EINVAL, "not a membership (PM_DIR_ANY / _GROUPED / _UNGROUPED)");
+  if (q->order > PM_DIR_BY_ADDRESS) return set_error(PM_EINVAL, "not an order (PM_DIR_BY_ROW / _BY_ADDRESS)");
+  std::lock_guard<std::mutex> lk(e->mu);
+  int32_t rc = liveness_guard(e);  // (liveness is the status: off, there is nothing to list)
+  if (rc) return rc;
+  if (e->W > 0x3FFFFFFFu) return set_error(PM_ERANGE, "worker table too large for the directory");
+  HIPCHK(hipSetDevice(e->cfg.device));
+  ABSORB_PENDING(e);  // (the groups of a tick that has not been taken in yet: pm_get_groups would report them)
+  if ((rc = liveness_prepare(e))) return rc;
+  if (e->ro.on && (rc = rollout_prepare(e))) return rc;
+  Directory& d = e->dir;
+  const uint32_t W = e->W, G = uint32_t(e->groups.size());
+  HIPCHK(d.h_pin.ensure(1 + PM_NS_N, 1 + PM_NS_N));
+  std::memset(d.h_pin.p, 0, (1 + PM_NS_N) * sizeof(uint32_t));
+  DirArgs a{};
+  if (W) {
+    d.h_g.resize(G);
+    uint32_t live = 0;
+    for (uint32_t k = 0; k < G; ++k) {
+      const Group& gr = e->groups[k];
+      DirGroup& o = d.h_g[k];
+      o.id = gr.id;
+      o.cfg = gr.cfg;
+      o.size = uint32_t(gr.members.size());
+      o.slot = gr.dead ? PM_NONE : live++;  // (tombstones are skipped, as pm_get_groups numbers the list)
+      o.task = gr.dead ? PM_NONE : task_position(e, gr.task);
+    }
+    if ((rc = upload(d.gof, e->h_group_of.data(), size_t(W), e->stream))) return rc;
+    if ((rc = upload(d.g, d.h_g.data(), size_t(G), e->stream))) return rc;
+    const size_t n_flag = size_t(PM_DC_N) * W;
+    HIPCHK(d.cls.ensure(W));
+    HIPCHK(d.flag.ensure(n_flag));
+    HIPCHK(d.off.ensure(n_flag + 1));
+    HIPCHK(d.census.ensure(PM_NS_N));
+    HIPCHK(hipMemsetAsync(d.census.p, 0, PM_NS_N * sizeof(uint32_t), e->stream));
+    a.W = W, a.G = G;
+    a.status_mask = q->status_mask, a.membership = q->membership;
+    a.status = e->live.status.p;
+    a.counter = e->live.counter.p;
+    a.group_of = d.gof.p;
+    a.g = d.g.p;
+    a.addr_rank = e->d_addr_rank.p;
+    a.uid = e->ro.on ? e->ro.uid.p : nullptr;
+    a.state = e->ro.on ? e->ro.state.p : nullptr;
+    a.cls = d.cls.p;
+    a.flag = d.flag.p;
+    a.census = d.census.p;
+    a.off = d.off.p;
+    launch_dir_classify(a, e->stream);
+    launch_mx_scan(d.flag.p, uint32_t(n_flag), d.off.p, d.h_pin.p, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(d.h_pin.p + 1, d.census.p, PM_NS_N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+  }
+  const uint32_t n_listed = d.h_pin.p[0];
+  if (n_listed > W) return set_error(PM_ESTATE, "directory: more listed rows than rows");
+  const uint32_t n = q->offset >= n_listed ? 0u : std::min(q->limit, n_listed - q->offset);
+  *total = n_listed;
+  if (counts) std::copy(d.h_pin.p + 1, d.h_pin.p + 1 + PM_NS_N, counts);
+  *n_rows = n;
+  if (n && (!rows || cap < n)) return set_error(PM_ERANGE, "directory row buffer too small");
+  if (!n) return PM_OK;
+  a.offset = q->offset, a.n_rows = n;
+  const uint32_t* list = nullptr;
+  if (q->order == PM_DIR_BY_ROW) {
+    HIPCHK(d.win.ensure(n));
+    a.win = d.win.p;
+    launch_dir_window(a, e->stream);
+    list = d.win.p;
+  } else {
+    const uint32_t chunks = (n_listed + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
+    for (int b = 0; b < 2; ++b) {
+      HIPCHK(d.key[b].ensure(n_listed));
+      HIPCHK(d.val[b].ensure(n_listed));
+    }
+    HIPCHK(d.hist.ensure(256 * size_t(chunks)));
+    HIPCHK(d.hist_scan.ensure(256 * size_t(chunks) + 1));
+    a.key = d.key[0].p;
+    a.val = d.val[0].p;
+    launch_dir_keys(a, e->stream);
+    uint32_t cur = 0;
+    for (uint32_t p = 0; p < 5u; ++p, cur ^= 1u)  // 32 bits of rank, the class's two in the fifth byte: ends in buffer 1
+      launch_ro_radix_pass(d.key[cur].p, d.val[cur].p, n_listed, 8u * p, d.hist.p, d.hist_scan.p, d.key[cur ^ 1u].p,
+                           d.val[cur ^ 1u].p, e->stream);
+    list = d.val[cur].p + q->offset;
+  }
+  HIPCHK(d.rows.ensure(n));
+  launch_dir_emit(a, list, n, d.rows.p, e->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(rows, d.rows.p, size_t(n) * sizeof(pm_dir_row), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return PM_OK;
+}
+
+}  // extern "C"

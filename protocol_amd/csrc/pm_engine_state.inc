@@ -109,6 +109,22 @@ struct Rollout {
   std::vector<uint8_t> h_state;
 };
 
+// ---- node directory (pm_engine_directory.inc): scratch of one pm_directory call and nothing else — there is no ledger of its
+// own, no enable call and no hook in the upload path; nothing is cached between calls.
+struct Directory {
+  DevBuf<int32_t> gof;        // the join's other side: the host's group_of, its group list
+  DevBuf<DirGroup> g;
+  DevBuf<uint8_t> cls;        // [W]
+  DevBuf<uint32_t> flag, off; // [PM_DC_N * W] (+ 1): the class flags and their scan
+  DevBuf<uint32_t> census;    // [PM_NS_N]
+  DevBuf<uint32_t> win;       // BY_ROW: the window's rows
+  DevBuf<uint64_t> key[2];    // BY_ADDRESS: the sort's keys and rows, ping-pong
+  DevBuf<uint32_t> val[2], hist, hist_scan;
+  DevBuf<pm_dir_row> rows;
+  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_NS_N) the census
+  std::vector<DirGroup> h_g;
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -344,4 +360,5 @@ struct pm_engine {
   Discovery disc;
   Metrics mx;
   Rollout ro;
+  Directory dir;  // (scratch only: never switched)
 };

@@ -97,6 +97,15 @@ ro_worker_row_dt = np.dtype([("worker", "<u4"), ("group_slot", "<u4"), ("uid", "
                              ("_pad", "<u2"), ("_pad2", "<u4")])
 assert (ro_report_dt.itemsize, ro_summary_dt.itemsize, ro_task_row_dt.itemsize, ro_group_row_dt.itemsize,
         ro_worker_row_dt.itemsize) == (16, 72, 64, 64, 24)
+# pm_dir_query, pm_dir_row, PM_DIR_*, PM_DC_* (include/pm_engine.h): node directory
+dir_query_dt = np.dtype([("status_mask", "<u4"), ("membership", "<u4"), ("order", "<u4"), ("offset", "<u4"), ("limit", "<u4")])
+dir_row_dt = np.dtype([("worker", "<u4"), ("status", "u1"), ("cls", "u1"), ("state", "u1"), ("_pad", "u1"), ("counter", "<u4"),
+                       ("group_slot", "<u4"), ("group_id", "<u8"), ("group_size", "<u4"), ("config", "<u4"), ("task", "<u4"),
+                       ("_pad2", "<u4"), ("uid", "<u8")])
+assert dir_query_dt.itemsize == 20 and dir_row_dt.itemsize == 48
+DIR_ANY, DIR_GROUPED, DIR_UNGROUPED = 0, 1, 2
+DIR_BY_ROW, DIR_BY_ADDRESS = 0, 1
+DC_HEALTHY, DC_DISCOVERED, DC_OTHER, DC_DEAD, DC_N = 0, 1, 2, 3, 4
 TS_NAMES = ("PENDING", "PULLING", "RUNNING", "COMPLETED", "FAILED", "PAUSED", "RESTARTING", "UNKNOWN")
 TS_RUNNING, TS_UNKNOWN, TS_N, TS_NONE = 2, 7, 8, 255
 RO_IDLE, RO_STRAY, RO_SILENT, RO_OTHER, RO_BEHIND, RO_CONVERGED, RO_N = 0, 1, 2, 3, 4, 5, 6
@@ -199,6 +208,7 @@ EXPORTS = [
     "pm_metrics_enable", "pm_metrics_ingest", "pm_metrics_totals", "pm_metrics_rows",
     "pm_rollout_enable", "pm_rollout_ingest", "pm_rollout_get", "pm_rollout_summary", "pm_rollout_tasks", "pm_rollout_groups",
     "pm_rollout_workers", "pm_host_task_state",
+    "pm_directory",
 ]
 
 _lib = None
@@ -292,6 +302,7 @@ def lib() -> C.CDLL:
         L.pm_rollout_tasks.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_rollout_groups.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_rollout_workers.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
+        L.pm_directory.argtypes = [vp, vp, C.POINTER(u32), vp, vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -814,6 +825,24 @@ class Engine:
     def rollout_workers(self, class_mask: int = (1 << RO_N) - 1) -> np.ndarray:
         """pm_rollout_workers -> ro_worker_row_dt [n]: the workers whose class bit is in class_mask, ascending"""
         return self._rollout_list(lambda p, cap, n: lib().pm_rollout_workers(self._h, int(class_mask), p, cap, n), ro_worker_row_dt)
+
+    # ---- node directory
+    def directory(self, status_mask: int = (1 << NS_N) - 1, membership: int = DIR_ANY, order: int = DIR_BY_ROW, offset: int = 0,
+                  limit=None):
+        """pm_directory -> (total, counts uint32 [NS_N], rows dir_row_dt [n]): the window [offset, offset + limit) of the listed
+        rows in (class, base key, row) order; limit None = to the end, 0 = the counters alone"""
+        q = np.zeros(1, dtype=dir_query_dt)
+        q[0] = (int(status_mask), int(membership), int(order), int(offset), 0xFFFFFFFF if limit is None else int(limit))
+        total, n, counts = C.c_uint32(0), C.c_uint32(0), np.zeros(NS_N, dtype=np.uint32)
+        rc = lib().pm_directory(self._h, q.ctypes.data, C.byref(total), counts.ctypes.data, None, 0, C.byref(n))
+        if rc != -5:                                           # (PM_ERANGE is the size query's answer)
+            check(rc)
+        if not n.value:
+            return total.value, counts, np.zeros(0, dtype=dir_row_dt)
+        rows = np.zeros(n.value, dtype=dir_row_dt)
+        check(lib().pm_directory(self._h, q.ctypes.data, C.byref(total), counts.ctypes.data, rows.ctypes.data, len(rows),
+                                 C.byref(n)))
+        return total.value, counts, rows[:n.value]
 
     def compat_masks(self) -> np.ndarray:
         out = np.zeros(self.W, dtype=np.uint64)

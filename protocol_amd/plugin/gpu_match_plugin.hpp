@@ -507,6 +507,37 @@ class GpuMatchPlugin : public SchedulerPlugin {
   size_t remembered_task_texts() const;
   static uint64_t reported_task_uid(const std::string& task_id);
 
+  // ---- node directory (INTEGRATION.md "Node directory"; gpu_match_directory.cpp): the store's ordered listing
+  // (NodeStore::get_nodes, store/domains/node_store.rs:163-209: Healthy, Discovered, everything else, Dead) over the engine's
+  // pm_directory, for its callers: GET /nodes (api/routes/nodes.rs:29-105), the sync service's gauge (metrics/sync_service.rs:
+  // 209-225), the inviter (node_store.rs:247-282) and sync_chain_with_nodes (status_update/mod.rs:118-142).  Needs
+  // enable_liveness: the statuses are the ledger's.  Inside a class the order is the row's (PM_DIR_BY_ROW) or the address
+  // text's (PM_DIR_BY_ADDRESS: the rank column sync_nodes keeps) — A DEVIATION: the reference's is SMEMBERS', which nothing
+  // pins.  Only the asked window and the counters leave the device.  LOCK ORDER: nodes, the engine.
+  struct ListedGroup {  // the route's "group" object (nodes.rs:83-88)
+    std::string id;
+    uint32_t size = 0;
+    int64_t created_at = 0;
+    std::string topology_config;  // the configuration's NAME
+  };
+  struct ListedNode {
+    std::string address;
+    NodeStatus status = NodeStatus::Discovered;
+    uint32_t unhealthy_counter = 0;
+    uint32_t task_state = PM_TS_NONE;  // the reported state (PM_TS_*), PM_TS_NONE: no report or rollout off
+    std::optional<ListedGroup> group;
+  };
+  struct NodeListing {
+    uint32_t total = 0;                      // the whole filtered list's length, not the window's
+    std::map<std::string, uint32_t> counts;  // per status name as `{:?}` prints it, over the whole filtered list; present ones only
+    std::vector<ListedNode> nodes;           // the window
+  };
+  NodeListing list_nodes(bool include_dead, uint32_t order = PM_DIR_BY_ROW, uint32_t offset = 0, uint32_t limit = 0xFFFFFFFFu) const;
+  std::map<std::string, uint32_t> status_counts() const;  // every node, lowercase names (sync_service.rs:220), present ones only
+  std::vector<std::string> uninvited_nodes() const;       // the Discovered nodes' addresses, in row order
+  std::vector<std::string> dead_nodes() const;            // the Dead nodes' addresses, in row order (the pool test stays the host's)
+  static const char* status_name(uint32_t status);        // NodeStatus as `{:?}` prints it
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -626,6 +657,9 @@ class GpuMatchPlugin : public SchedulerPlugin {
   void flush_rollout_locked();
   std::vector<pm_ro_task_row> rollout_task_rows_locked();
   std::string rollout_text_locked(uint64_t uid, uint32_t task) const;
+  // node directory (gpu_match_directory.cpp): one window through the size query, checked against the node table
+  std::vector<pm_dir_row> directory_locked(const pm_dir_query& q, uint32_t* total, uint32_t* counts) const;
+  std::vector<std::string> nodes_of_status_locked(uint32_t status) const;
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

@@ -204,6 +204,18 @@ int32_t pmx_task_rollout(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_group_rollout(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_rollout_nodes(pmx_plugin*, uint32_t class_mask, char* out, size_t cap, size_t* needed);
 
+/* ---- node directory (pm_plugin_directory_c.cpp): GpuMatchPlugin::list_nodes / status_counts / uninvited_nodes / dead_nodes
+ * (needs pmx_enable_liveness).  The texts, numbers in decimal: pmx_list_nodes "total\t<total>", then "count\t<status name>\t
+ * <count>" per status that occurs (in name order), then "<address>\t<status name>\t<unhealthy counter>\t<task state or ->\t<group
+ * id or ->\t<group size or ->\t<configuration name or ->" per node of the window, in listing order; pmx_status_counts "<lowercase
+ * status name>\t<count>" per status that occurs; pmx_uninvited_nodes / pmx_dead_nodes one address a line, in row order.
+ * order: 0 = by row, 1 = by address; limit UINT32_MAX = to the end. */
+int32_t pmx_list_nodes(pmx_plugin*, uint32_t include_dead, uint32_t order, uint32_t offset, uint32_t limit, char* out, size_t cap,
+                       size_t* needed);
+int32_t pmx_status_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_uninvited_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_dead_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

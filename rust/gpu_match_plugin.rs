@@ -352,6 +352,47 @@ pub struct pm_ro_worker_row {
     pub _pad2: u32,
 }
 
+/// pm_dir_query / pm_dir_row (include/pm_engine.h): the node directory's query and its joined row
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_dir_query {
+    pub status_mask: u32,
+    pub membership: u32,
+    pub order: u32,
+    pub offset: u32,
+    pub limit: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_dir_row {
+    pub worker: u32,
+    pub status: u8,
+    pub cls: u8,
+    pub state: u8,
+    pub _pad: u8,
+    pub counter: u32,
+    pub group_slot: u32,
+    pub group_id: u64,
+    pub group_size: u32,
+    pub config: u32,
+    pub task: u32,
+    pub _pad2: u32,
+    pub uid: u64,
+}
+
+/// PM_DIR_* (membership, order), PM_DC_* (the listing's four classes)
+pub const DIR_ANY: u32 = 0;
+pub const DIR_GROUPED: u32 = 1;
+pub const DIR_UNGROUPED: u32 = 2;
+pub const DIR_BY_ROW: u32 = 0;
+pub const DIR_BY_ADDRESS: u32 = 1;
+pub const DC_HEALTHY: u32 = 0;
+pub const DC_DISCOVERED: u32 = 1;
+pub const DC_OTHER: u32 = 2;
+pub const DC_DEAD: u32 = 3;
+pub const DC_N: u32 = 4;
+
 /// PM_TS_* (TaskState, shared/src/models/task.rs:12-22, in its order), PM_TS_NONE, PM_RO_*
 pub const TS_PENDING: u32 = 0;
 pub const TS_PULLING: u32 = 1;
@@ -594,6 +635,8 @@ extern "C" {
     fn pm_rollout_tasks(e: *mut c_void, rows: *mut pm_ro_task_row, cap: u32, n: *mut u32) -> i32;
     fn pm_rollout_groups(e: *mut c_void, rows: *mut pm_ro_group_row, cap: u32, n: *mut u32) -> i32;
     fn pm_rollout_workers(e: *mut c_void, class_mask: u32, rows: *mut pm_ro_worker_row, cap: u32, n: *mut u32) -> i32;
+    fn pm_directory(e: *mut c_void, q: *const pm_dir_query, total: *mut u32, counts: *mut u32, rows: *mut pm_dir_row, cap: u32,
+                    n_rows: *mut u32) -> i32;
     fn pm_host_task_state(s: *const c_char) -> u32;
 }
 
@@ -770,6 +813,32 @@ pub struct NodeRollout {
     pub cls: u32,
     pub state: u32,
     pub task_id: Option<String>,   // the reported id's text (hex where the plugin has none), None: no report
+}
+
+/// the "group" object GET /nodes attaches to a node (api/routes/nodes.rs:83-88)
+#[derive(Debug, Clone)]
+pub struct ListedGroup {
+    pub id: String,
+    pub size: u32,
+    pub created_at: chrono::DateTime<chrono::Utc>,
+    pub topology_config: String,   // the configuration's NAME
+}
+
+#[derive(Debug, Clone)]
+pub struct ListedNode {
+    pub address: String,
+    pub status: NodeStatus,
+    pub unhealthy_counter: u32,
+    pub task_state: u32,           // the reported state (TS_*), TS_NONE: no report or rollout off
+    pub group: Option<ListedGroup>,
+}
+
+/// one window of the store's ordered listing (gpu_match_directory.cpp's NodeListing)
+#[derive(Default, Debug, Clone)]
+pub struct NodeListing {
+    pub total: u32,                                  // the whole filtered list's length, not the window's
+    pub counts: std::collections::BTreeMap<String, u32>,   // per status name as `{:?}` prints it; present ones only
+    pub nodes: Vec<ListedNode>,
 }
 
 /// one record_compute_task_gauge call of sync_metrics_from_redis (gpu_match_metrics.cpp's SyncedMetric)
@@ -2449,6 +2518,79 @@ impl GpuMatchPlugin {
         }
         Ok(out)
     }
+
+    // ---- node directory (gpu_match_directory.cpp, statement for statement): NodeStore::get_nodes' ordered listing over
+    // pm_directory, for GET /nodes, the sync service's gauge, the inviter and sync_chain_with_nodes.  LOCK ORDER: nodes, the engine.
+
+    /// one window through the size query, checked against the node table (the node lock is held)
+    fn directory_locked(&self, t: &NodeTable, q: &pm_dir_query, total: &mut u32, counts: Option<&mut [u32; NS_N as usize]>)
+                        -> Result<Vec<pm_dir_row>> {
+        let counts = counts.map_or(std::ptr::null_mut(), |c| c.as_mut_ptr());
+        let mut have = 0u32;
+        let rc = unsafe { pm_directory(self.engine, q, total, counts, std::ptr::null_mut(), 0, &mut have) };
+        if rc != PM_ERANGE { check(rc)?; }      // (PM_ERANGE unless the window is empty)
+        if have == 0 { return Ok(Vec::new()); }
+        let mut rows = vec![pm_dir_row::default(); have as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_directory(self.engine, q, total, counts, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;
+        if got as usize > rows.len() { return Err(anyhow!("directory: the window grew between two calls")); }
+        rows.truncate(got as usize);
+        if rows.iter().any(|r| r.worker as usize >= t.rows.len() || r.status >= NS_N) {
+            return Err(anyhow!("directory: the engine lists a row the plugin does not know"));
+        }
+        Ok(rows)
+    }
+
+    /// GET /nodes (api/routes/nodes.rs:29-105): the window [offset, offset + limit) of the listing, without Dead unless asked
+    pub fn list_nodes(&self, include_dead: bool, order: u32, offset: u32, limit: u32) -> Result<NodeListing> {
+        let t = self.nodes.read();
+        let all = (1u32 << NS_N) - 1;
+        let q = pm_dir_query { status_mask: if include_dead { all } else { all & !(1u32 << NS_DEAD) }, membership: DIR_ANY, order,
+                               offset, limit };
+        let mut counts = [0u32; NS_N as usize];
+        let mut out = NodeListing::default();
+        let rows = self.directory_locked(&t, &q, &mut out.total, Some(&mut counts))?;
+        for (s, &c) in counts.iter().enumerate() {
+            if c != 0 { out.counts.insert(format!("{:?}", node_status_of(s as u8)), c); }   // (the statuses it met: nodes.rs:47-59)
+        }
+        for r in rows {
+            let group = if r.group_slot != PM_NONE {
+                let Some(cfg) = self.config_names.get(r.config as usize) else {
+                    return Err(anyhow!("directory: the engine names a configuration the plugin has not"));
+                };
+                let created_at = self.group_created_at.lock().get(&r.group_id).copied().unwrap_or_else(chrono::Utc::now);
+                Some(ListedGroup { id: format!("{:x}", r.group_id), size: r.group_size, created_at, topology_config: cfg.clone() })
+            } else {
+                None
+            };
+            out.nodes.push(ListedNode { address: t.address_strings[r.worker as usize].clone(), status: node_status_of(r.status),
+                                        unhealthy_counter: r.counter, task_state: r.state as u32, group });
+        }
+        Ok(out)
+    }
+
+    /// the sync service's gauge (metrics/sync_service.rs:209-225): every node, lowercase names, present statuses only
+    pub fn status_counts(&self) -> Result<std::collections::BTreeMap<String, u32>> {
+        let t = self.nodes.read();
+        let q = pm_dir_query { status_mask: (1u32 << NS_N) - 1, membership: DIR_ANY, order: DIR_BY_ROW, offset: 0, limit: 0 };
+        let (mut total, mut counts) = (0u32, [0u32; NS_N as usize]);
+        self.directory_locked(&t, &q, &mut total, Some(&mut counts))?;   // the counters alone
+        Ok(counts.iter().enumerate().filter(|(_, &c)| c != 0)
+               .map(|(s, &c)| (format!("{:?}", node_status_of(s as u8)).to_lowercase(), c)).collect())
+    }
+
+    fn nodes_of_status(&self, status: u8) -> Result<Vec<String>> {
+        let t = self.nodes.read();
+        let q = pm_dir_query { status_mask: 1u32 << status, membership: DIR_ANY, order: DIR_BY_ROW, offset: 0, limit: u32::MAX };
+        let mut total = 0u32;
+        Ok(self.directory_locked(&t, &q, &mut total, None)?.iter().map(|r| t.address_strings[r.worker as usize].clone()).collect())
+    }
+
+    /// get_uninvited_nodes (node_store.rs:247-282): the Discovered nodes, in row order
+    pub fn uninvited_nodes(&self) -> Result<Vec<String>> { self.nodes_of_status(NS_DISCOVERED) }
+
+    /// what sync_chain_with_nodes walks (status_update/mod.rs:118-142): the Dead nodes; the pool test stays the host's
+    pub fn dead_nodes(&self) -> Result<Vec<String>> { self.nodes_of_status(NS_DEAD) }
 
     /// the ledger's rows as stored (what the tests look at)
     pub fn reported_tasks(&self, rows: &[u32]) -> Result<(Vec<u64>, Vec<u8>)> {

@@ -32,6 +32,9 @@
 #   rollout[:<args>]         tools/rollout_probe.py [W] [--bench DIR]: pm_rollout_ingest and the four reads at W rows (100000) over the
 #                            groups of a real tick, beside each the same work as a loop on one host thread
 #                            -> r26_rollout.txt (copy it to profiles/)
+#   directory[:<args>]       tools/directory_probe.py [W ...] [--bench DIR]: pm_directory at 10,000 and 100,000 rows — the counters, a
+#                            first and a middle page by row and by address, the full list — beside each what a host does today
+#                            (three full-table reads, a stable sort, the join) -> r27_directory.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -159,6 +162,9 @@ PY
     rollout)
       timeout -k 10 300 python tools/rollout_probe.py $arg --out "$out/r26_rollout.txt" > "$out/${n}_rollout.log" 2>&1; echo "rollout rc=$?"
       tail -12 "$out/${n}_rollout.log" ;;
+    directory)
+      timeout -k 10 400 python tools/directory_probe.py $arg --out "$out/r27_directory.txt" > "$out/${n}_directory.log" 2>&1; echo "directory rc=$?"
+      tail -20 "$out/${n}_directory.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
