@@ -974,6 +974,92 @@ typedef struct pm_dir_row {            /* 48 B, padding zero */
 int32_t pm_directory(pm_engine*, const pm_dir_query* q, uint32_t* total, uint32_t* counts /* PM_NS_N */,
                      pm_dir_row* rows, uint32_t cap, uint32_t* n_rows);
 
+/* ---- group directory (kernels in pm_groupdir.inc) ---------------------------------------------------------------------------
+ * GET /groups JOINED, FILTERED AND PAGED.  The reference lists its groups in one place, get_all_groups (node_groups/mod.rs:
+ * 1006-1044), sorted by the id's `{:x}` text (:1040), and three callers read it: GET /groups (api/routes/groups.rs:32-66), the
+ * groups_count gauge per configuration name (metrics/sync_service.rs:272-286) and the plugin's own status handlers.  What an
+ * operator asks about a standing group — is every member still Healthy, has every member picked up the group's task — needs
+ * columns that live on the device alone (the liveness and rollout ledgers); a host would fetch pm_get_groups, pm_liveness_get
+ * and pm_rollout_groups whole, join them by worker index and sort id texts.  pm_group_directory makes the joined list on the
+ * device and hands out ONE WINDOW of it and the counters.  A pure read: no enable call, no state of its own, nothing cached.
+ *
+ * LISTED.  A group is listed if it is a live group of the host's list as pm_get_groups would report it at this moment (a
+ * pending tick is taken in first, as in pm_directory; tombstones are skipped and slots are numbered as pm_get_groups numbers
+ * them; nothing is compacted) and passes every filter of the query: bit `config` of config_mask is set (bits at or above the
+ * number of configurations select nothing and are legal: ~0 is "all"); holds = PM_GDIR_ANY / _WITH_TASK / _WITHOUT_TASK by the
+ * claimed task; size_min <= size <= size_max; bit `health` of health_mask; bit `rollout` of rollout_mask.
+ * HEALTH CLASS (the liveness ledger's status of every member), the first match of: PM_GH_LOST some member is Dead, Ejected,
+ * Banned or LowBalance; PM_GH_DEGRADED some member is not Healthy (Discovered, WaitingForHeartbeat, Unhealthy); PM_GH_SOUND
+ * every member is Healthy.  handle_status_change dissolves a group on Dead and LowBalance only (status_update_impl.rs:16-29),
+ * and pm_adopt_groups accepts dead members: LOST and DEGRADED groups stand, and this is the call that lists them.  With liveness
+ * off health_mask must be all classes (7), rows carry PM_GH_NONE and by_status zero, totals.by_health is zero.
+ * ROLLOUT CLASS (the rollout ledger): PM_GR_NO_TASK; PM_GR_CONVERGED the group holds a task and every member is
+ * PM_RO_CONVERGED — pm_rollout_summary.groups_converged's rule, the same comparison (an id of all ones never matches; with
+ * duplicate ids the id names the first live row); PM_GR_ROLLING it holds a task and is not converged.  With rollout off
+ * rollout_mask must be all classes (7), rows carry PM_GR_NONE and zero counters, totals.by_rollout is zero.
+ * ORDER, ties always by ascending slot.  PM_GDIR_BY_SLOT: creation order (one scan, no sort).  PM_GDIR_BY_ID_TEXT: the
+ * reference's: the byte order of format!("{:x}", id) — lowercase, no leading zeros, 0 is "0"; NOT numeric order ("100" < "ff").
+ * PM_GDIR_BY_SIZE_DESC: largest first.
+ * OUTPUTS.  totals: total = listed groups, members_total = their workers, by_health / by_rollout = listed groups per class,
+ * n_cfgs = configurations installed.  by_config[c], c < n_cfgs = listed groups of configuration c (the gauge); by_config may be
+ * NULL, cap_cfgs < n_cfgs with a buffer is PM_ERANGE.  All of these count the whole list, not the window.  rows = the window
+ * [offset, offset + limit) with pm_directory's conventions: *n_rows = min(limit, total - offset), 0 when offset >= total;
+ * offset + limit is never formed, limit = UINT32_MAX is "to the end", limit = 0 is the counters-only query (one
+ * synchronisation).  members = the window's members laid end to end, rows[k].member_begin the first of row k's, each group's in
+ * ascending addr_rank, equal ranks by ascending row (DEFINED, where pm_get_groups sorts unstably); members may be NULL;
+ * *n_members is written either way (it is the window's, so a call that finds its row buffer too small has made the order before
+ * it answers: a caller that wants one sort sizes its buffers from a counters-only query's totals — at most min(limit, total -
+ * offset) rows and members_total members — as both plugin twins do).  A row: task = the claimed task's position in the CURRENT list or PM_NONE; by_status[s] =
+ * members of liveness status s; converged / behind / other / silent = members per rollout relation (PM_RO_CONVERGED / _BEHIND
+ * / _OTHER / _SILENT), summing to size when the group holds a task and rollout is on, all zero otherwise.
+ * The device joins: one thread a worker row adds to its live group's counter words (the lanes of a wave that hit one word
+ * send one atomic), one thread a list entry classifies, filters and counts, the order is a 16-class ordered compaction by
+ * text length and eight stable radix passes (BY_ID_TEXT), four passes (BY_SIZE_DESC) or the scan alone (BY_SLOT).  Only
+ * h_group_of and one record per list entry go up, the counters and the window come down.  The window's MEMBERS are laid out
+ * from the host's own list: they never were on the device's side of the join and do not cross PCIe twice.  The tick's device
+ * mirror of the groups and its delta state are not touched.  DETERMINISTIC: integers only, bit-identical from call to call,
+ * independent of the number of workgroups.
+ * ERRORS, everything checked on the host first.  PM_EINVAL: a null q, totals, n_rows or n_members; config_mask == 0;
+ * health_mask / rollout_mask == 0 or a bit at or above PM_GH_N / PM_GR_N; an unknown holds or order; size_min > size_max.
+ * PM_ESTATE: a stepwise tick is in progress; dist_world > 1 (the multi-GPU engine answers this, like the other ledger reads);
+ * no configurations or workers uploaded; a class mask other than "all" whose ledger is off; rollout on over a task table
+ * uploaded without ids (as pm_rollout_*).  PM_ERANGE: by_config, rows or members too small, or rows == NULL with *n_rows > 0:
+ * totals, by_config (where it fits), *n_rows and *n_members are still written and no row or member is copied; a list of 2^28
+ * entries or more.  No call consumes a pending delta, compacts groups, clears a cache flag or changes what the next tick does. */
+enum { PM_GDIR_ANY = 0, PM_GDIR_WITH_TASK = 1, PM_GDIR_WITHOUT_TASK = 2 };          /* holds */
+enum { PM_GDIR_BY_SLOT = 0, PM_GDIR_BY_ID_TEXT = 1, PM_GDIR_BY_SIZE_DESC = 2 };    /* order */
+enum { PM_GH_LOST = 0, PM_GH_DEGRADED = 1, PM_GH_SOUND = 2, PM_GH_N = 3 };
+#define PM_GH_NONE 255u                                                            /* liveness is off */
+enum { PM_GR_NO_TASK = 0, PM_GR_CONVERGED = 1, PM_GR_ROLLING = 2, PM_GR_N = 3 };
+#define PM_GR_NONE 255u                                                            /* rollout is off */
+typedef struct pm_gdir_query {          /* 40 B */
+  uint64_t config_mask;                 /* bit c: groups of configuration c are listed */
+  uint32_t holds;                       /* PM_GDIR_ANY / _WITH_TASK / _WITHOUT_TASK */
+  uint32_t size_min, size_max;          /* members, inclusive */
+  uint32_t health_mask, rollout_mask;   /* bits over PM_GH_* / PM_GR_* */
+  uint32_t order;                       /* PM_GDIR_BY_* */
+  uint32_t offset, limit;               /* the window [offset, offset + limit) of the ordered list */
+} pm_gdir_query;
+typedef struct pm_gdir_totals {         /* 36 B */
+  uint32_t total, members_total;
+  uint32_t by_health[PM_GH_N], by_rollout[PM_GR_N];
+  uint32_t n_cfgs;
+} pm_gdir_totals;
+typedef struct pm_gdir_row {            /* 80 B, padding zero */
+  uint64_t group_id;
+  uint32_t slot;                        /* as pm_get_groups numbers them now */
+  uint32_t config, size;
+  uint32_t task;                        /* the claimed task, position in the CURRENT list, or PM_NONE */
+  uint32_t member_begin;                /* the group's first entry of `members` */
+  uint8_t health;  /* PM_GH_* or PM_GH_NONE */  uint8_t rollout; /* PM_GR_* or PM_GR_NONE */  uint16_t _pad;
+  uint32_t by_status[PM_NS_N];          /* members per liveness status */
+  uint32_t converged, behind, other, silent;  /* members per rollout relation */
+} pm_gdir_row;
+int32_t pm_group_directory(pm_engine*, const pm_gdir_query* q, pm_gdir_totals* totals,
+                           uint32_t* by_config /* cap_cfgs, may be NULL */, uint32_t cap_cfgs,
+                           pm_gdir_row* rows, uint32_t cap_rows, uint32_t* n_rows,
+                           uint32_t* members /* may be NULL */, uint32_t cap_members, uint32_t* n_members);
+
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).
  * task_of_worker[w] = task index or PM_NONE; applicable_count[w] = number of applicable tasks the

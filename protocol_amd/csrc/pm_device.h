@@ -307,6 +307,34 @@ struct DirArgs {
   uint32_t* val;             // [total] out: the row
 };
 
+// group directory (pm_groupdir.inc): the groups' ordered, filtered, paged listing joined with both ledgers.  A list entry's
+// record is the rollout ledger's RoGroup (the id, the claimed task's id and position, the size, the reported slot).
+static constexpr uint32_t PM_GD_CNT = PM_NS_N + 4;            // a group's counters: by_status[PM_NS_N], converged, behind, other, silent
+static constexpr uint32_t PM_GD_CENSUS = PM_MAX_CONFIGS + PM_GH_N + PM_GR_N + 1;  // by_config, by_health, by_rollout, members_total
+static constexpr uint32_t PM_GD_TEXT_CLASSES = 16;            // BY_ID_TEXT: the hex digits of a u64 id, 1..16
+static constexpr uint32_t PM_GD_NO_CLASS = 0xFFu;             // GdirArgs::cls of an entry the query does not list
+struct GdirArgs {
+  uint32_t W, G;
+  uint64_t config_mask;              // the query's filter (pm_gdir_query)
+  uint32_t holds, size_min, size_max, health_mask, rollout_mask, order;
+  uint32_t n_cls;                    // classes of the ordered compaction: PM_GD_TEXT_CLASSES (BY_ID_TEXT) or 1
+  uint32_t offset, n_rows;           // the window [offset, offset + n_rows) of the ordered list
+  const int32_t* group_of;   // [W] host truth, -1 = in no group
+  const RoGroup* g;          // [G]
+  const uint8_t* status;     // [W] the liveness ledger, or nullptr: it is off
+  const uint64_t* uid;       // [W] the rollout ledger, or nullptr: it is off
+  const uint8_t* state;      // [W]
+  uint32_t* g_cnt;           // [G * PM_GD_CNT] zeroed; out (member pass), in (group pass, emit)
+  uint32_t* census;          // [PM_GD_CENSUS] zeroed; out
+  uint8_t* cls;              // [G] out: the entry's class of the compaction, PM_GD_NO_CLASS: not listed
+  uint8_t* hr;               // [2 G] out: the entry's health and rollout class
+  uint32_t* flag;            // [n_cls * G] out, class-major: entry k is listed in class c
+  const uint32_t* off;       // [n_cls * G + 1] the flags' exclusive scan: a listed entry's place in (class, slot) order
+  uint32_t* win;             // [n_rows] out (BY_SLOT): the window's entries
+  uint64_t* key;             // [total] out (sorted orders): the sort key, in (class, slot) order
+  uint32_t* val;             // [total] out: the entry
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -595,6 +623,13 @@ void launch_dir_window(const DirArgs& a, hipStream_t s);
 void launch_dir_keys(const DirArgs& a, hipStream_t s);
 // rows[k] = the joined record of worker list[k], k < n
 void launch_dir_emit(const DirArgs& a, const uint32_t* list, uint32_t n, pm_dir_row* rows, hipStream_t s);
+// group directory (pm_groupdir.inc)
+void launch_gdir_members(const GdirArgs& a, hipStream_t s);
+void launch_gdir_groups(const GdirArgs& a, hipStream_t s);
+void launch_gdir_window(const GdirArgs& a, hipStream_t s);
+void launch_gdir_keys(const GdirArgs& a, hipStream_t s);
+// rows[k] = the joined record of list entry list[k], k < n (member_begin is the host's: it lays the members out)
+void launch_gdir_emit(const GdirArgs& a, const uint32_t* list, uint32_t n, pm_gdir_row* rows, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

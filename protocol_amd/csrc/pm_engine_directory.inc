@@ -28,17 +28,7 @@ int32_t pm_directory(pm_engine* e, const pm_dir_query* q, uint32_t* total, uint3
   std::memset(d.h_pin.p, 0, (1 + PM_NS_N) * sizeof(uint32_t));
   DirArgs a{};
   if (W) {
-    d.h_g.resize(G);
-    uint32_t live = 0;
-    for (uint32_t k = 0; k < G; ++k) {
-      const Group& gr = e->groups[k];
-      DirGroup& o = d.h_g[k];
-      o.id = gr.id;
-      o.cfg = gr.cfg;
-      o.size = uint32_t(gr.members.size());
-      o.slot = gr.dead ? PM_NONE : live++;  // (tombstones are skipped, as pm_get_groups numbers the list)
-      o.task = gr.dead ? PM_NONE : task_position(e, gr.task);
-    }
+    group_records(e, d.h_g);
     if ((rc = upload(d.gof, e->h_group_of.data(), size_t(W), e->stream))) return rc;
     if ((rc = upload(d.g, d.h_g.data(), size_t(G), e->stream))) return rc;
     const size_t n_flag = size_t(PM_DC_N) * W;

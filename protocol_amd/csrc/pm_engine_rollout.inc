@@ -43,6 +43,33 @@ static int32_t rollout_guard(pm_engine* e) {
   return PM_OK;
 }
 
+// One record per entry of the host's list, tombstones included, for the reads that join the groups on the device (the rollout
+// reads, pm_directory, pm_group_directory): id, configuration, size, the slot pm_get_groups would number it (tombstones are
+// skipped; PM_NONE: dissolved) and the claimed task's position in the current list.  RoGroup also takes the claimed task's id.
+// of_slot (optional): reported slot -> list entry.  Returns the live entries that hold a task.
+static inline void group_record_uid(RoGroup& o, uint64_t uid) { o.uid = uid; }
+static inline void group_record_uid(DirGroup&, uint64_t) {}
+template <class Rec>
+static uint32_t group_records(pm_engine* e, std::vector<Rec>& out, std::vector<uint32_t>* of_slot = nullptr) {
+  const uint32_t G = uint32_t(e->groups.size());
+  out.resize(G);
+  if (of_slot) of_slot->clear();
+  uint32_t live = 0, held = 0;
+  for (uint32_t k = 0; k < G; ++k) {
+    const Group& gr = e->groups[k];
+    Rec& o = out[k];
+    o.id = gr.id;
+    o.cfg = gr.cfg;
+    o.size = uint32_t(gr.members.size());
+    o.slot = gr.dead ? PM_NONE : live++;  // (tombstones are skipped, as pm_get_groups numbers the list)
+    o.task = gr.dead ? PM_NONE : task_position(e, gr.task);
+    group_record_uid(o, o.task == PM_NONE || !e->tasks_have_uid ? 0ull : e->h_tuid[gr.task]);
+    held += o.task != PM_NONE;
+    if (of_slot && !gr.dead) of_slot->push_back(k);
+  }
+  return held;
+}
+
 // What the four reads share: the host's groups go up (the join's other side, as pm_metrics_rows takes it), the workers are
 // classified, the groups' counters and the census are made; with `tasks`, the ids are sorted and ro.task_rows holds the
 // per-task table, *n_tasks its rows.  On return the stream is idle, h_pin[1..] holds the census, `a` names the buffers.
@@ -56,19 +83,7 @@ static int32_t rollout_read(pm_engine* e, bool tasks, RoPrepArgs* a, uint32_t* n
   if ((rc = rollout_prepare(e))) return rc;
   Rollout& ro = e->ro;
   const uint32_t W = e->W, G = uint32_t(e->groups.size());
-  ro.h_g.resize(G);
-  uint32_t live = 0, listed = 0;
-  for (uint32_t k = 0; k < G; ++k) {
-    const Group& gr = e->groups[k];
-    RoGroup& o = ro.h_g[k];
-    o.id = gr.id;
-    o.cfg = gr.cfg;
-    o.size = uint32_t(gr.members.size());
-    o.slot = gr.dead ? PM_NONE : live++;  // (tombstones are skipped, as pm_get_groups numbers the list)
-    o.task = gr.dead ? PM_NONE : task_position(e, gr.task);
-    o.uid = o.task == PM_NONE ? 0ull : e->h_tuid[gr.task];
-    listed += o.task != PM_NONE;
-  }
+  const uint32_t listed = group_records(e, ro.h_g);
   if ((rc = upload(ro.gof, e->h_group_of.data(), size_t(W), e->stream))) return rc;
   if ((rc = upload(ro.g, ro.h_g.data(), size_t(G), e->stream))) return rc;
   const size_t n_cnt = size_t(G) * PM_RO_GCNT + PM_RO_CENSUS, n_flag = size_t(W) + G;

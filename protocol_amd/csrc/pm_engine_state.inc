@@ -125,6 +125,23 @@ struct Directory {
   std::vector<DirGroup> h_g;
 };
 
+// ---- group directory (pm_engine_groupdir.inc): scratch of one pm_group_directory call and nothing else, like Directory
+struct GroupDir {
+  DevBuf<int32_t> gof;        // the join's other side: the host's group_of, its group list
+  DevBuf<RoGroup> g;
+  DevBuf<uint32_t> cnt;       // [G * PM_GD_CNT] the groups' counters, behind them [PM_GD_CENSUS] the census
+  DevBuf<uint8_t> cls, hr;    // [G], [2 G]
+  DevBuf<uint32_t> flag, off; // [n_cls * G] (+ 1): the class flags and their scan
+  DevBuf<uint32_t> win;       // BY_SLOT: the window's entries
+  DevBuf<uint64_t> key[2];    // the sorted orders: keys and entries, ping-pong
+  DevBuf<uint32_t> val[2], hist, hist_scan;
+  DevBuf<pm_gdir_row> rows;
+  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_GD_CENSUS) the census
+  std::vector<RoGroup> h_g;
+  std::vector<uint32_t> h_of_slot;  // reported slot -> list entry
+  std::vector<pm_gdir_row> h_rows;  // the window, before the caller's buffers are known to hold it
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -361,4 +378,5 @@ struct pm_engine {
   Metrics mx;
   Rollout ro;
   Directory dir;  // (scratch only: never switched)
+  GroupDir gdir;  // (the same)
 };

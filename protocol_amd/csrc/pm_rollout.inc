@@ -56,6 +56,28 @@ __global__ __launch_bounds__(256) void ro_get_kernel(const uint32_t* __restrict_
 // a live group that holds a task: what the group list shows and what its members are measured against
 __device__ __forceinline__ bool ro_listed(const RoGroup& gr) { return gr.slot != PM_NONE && gr.task != PM_NONE; }
 
+// THE RULE (stated once; the group directory's member pass asks it too): a member (reported id, state) of a group that holds
+// the task `claimed` is PM_RO_SILENT / _OTHER / _BEHIND / _CONVERGED
+__device__ __forceinline__ uint32_t ro_member_class(uint32_t st, uint64_t id, uint64_t claimed) {
+  const bool reports = st < PM_TS_N;
+  const bool same = reports && id == claimed && id != ~0ull;  // (an id of all ones never matches an assignment)
+  return !reports ? (uint32_t)PM_RO_SILENT : !same ? (uint32_t)PM_RO_OTHER
+       : st == PM_TS_RUNNING ? (uint32_t)PM_RO_CONVERGED : (uint32_t)PM_RO_BEHIND;
+}
+
+// counters by word: the lanes of this wave that add to one word send one atomic (`todo` is wave-uniform); PM_NONE: the lane
+// adds nothing.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_add_words(uint32_t* __restrict__ cnt, uint32_t word, uint32_t lane) {
+  uint64_t todo = __ballot(word != PM_NONE);
+  while (todo) {
+    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+    const uint32_t k = (uint32_t)__shfl((int)word, (int)lead);
+    const uint64_t m = __ballot(word == k);
+    if (lane == lead) atomicAdd(&cnt[k], (uint32_t)__popcll(m));
+    todo &= ~m;
+  }
+}
+
 // threads [0, W): a worker each; threads [W, W + G): whether the list entry is listed
 __global__ __launch_bounds__(256) void ro_classify_kernel(RoPrepArgs a) {
   __shared__ uint32_t s_bin[PM_RO_CENSUS];
@@ -80,9 +102,8 @@ __global__ __launch_bounds__(256) void ro_classify_kernel(RoPrepArgs a) {
     if (!held) {
       cls = reports ? PM_RO_STRAY : PM_RO_IDLE;
     } else {
-      const bool same = reports && id == claimed && id != ~0ull;  // (an id of all ones never matches an assignment)
-      cls = !reports ? PM_RO_SILENT : !same ? PM_RO_OTHER : st == PM_TS_RUNNING ? PM_RO_CONVERGED : PM_RO_BEHIND;
-      word = (uint32_t)g * PM_RO_GCNT + (!reports ? PM_TS_N + 1u : same ? st : (uint32_t)PM_TS_N);
+      cls = ro_member_class(st, id, claimed);
+      word = (uint32_t)g * PM_RO_GCNT + (cls == PM_RO_SILENT ? PM_TS_N + 1u : cls == PM_RO_OTHER ? (uint32_t)PM_TS_N : st);
     }
     a.cls[i] = (uint8_t)cls;
     a.flag[i] = reports ? 1u : 0u;
@@ -98,15 +119,7 @@ __global__ __launch_bounds__(256) void ro_classify_kernel(RoPrepArgs a) {
     const uint64_t m = __ballot(st_bin == s);
     if (lane == 0u && m) atomicAdd(&s_bin[PM_RO_N + s], (uint32_t)__popcll(m));
   }
-  // the groups' counters: the lanes of this wave that add to one word send one atomic (`todo` is wave-uniform)
-  uint64_t todo = __ballot(word != PM_NONE);
-  while (todo) {
-    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-    const uint32_t k = (uint32_t)__shfl((int)word, (int)lead);
-    const uint64_t m = __ballot(word == k);
-    if (lane == lead) atomicAdd(&a.g_cnt[k], (uint32_t)__popcll(m));
-    todo &= ~m;
-  }
+  wave_add_words(a.g_cnt, word, lane);  // the groups' counters
   __syncthreads();
   if (tid < PM_RO_N + PM_TS_N + 1u && s_bin[tid]) atomicAdd(&a.census[tid], s_bin[tid]);
 }

@@ -106,6 +106,19 @@ assert dir_query_dt.itemsize == 20 and dir_row_dt.itemsize == 48
 DIR_ANY, DIR_GROUPED, DIR_UNGROUPED = 0, 1, 2
 DIR_BY_ROW, DIR_BY_ADDRESS = 0, 1
 DC_HEALTHY, DC_DISCOVERED, DC_OTHER, DC_DEAD, DC_N = 0, 1, 2, 3, 4
+# pm_gdir_query, pm_gdir_totals, pm_gdir_row, PM_GDIR_*, PM_GH_*, PM_GR_* (include/pm_engine.h): group directory
+gdir_query_dt = np.dtype([("config_mask", "<u8"), ("holds", "<u4"), ("size_min", "<u4"), ("size_max", "<u4"), ("health_mask", "<u4"),
+                          ("rollout_mask", "<u4"), ("order", "<u4"), ("offset", "<u4"), ("limit", "<u4")])
+gdir_totals_dt = np.dtype([("total", "<u4"), ("members_total", "<u4"), ("by_health", "<u4", (3,)), ("by_rollout", "<u4", (3,)),
+                           ("n_cfgs", "<u4")])
+gdir_row_dt = np.dtype([("group_id", "<u8"), ("slot", "<u4"), ("config", "<u4"), ("size", "<u4"), ("task", "<u4"),
+                        ("member_begin", "<u4"), ("health", "u1"), ("rollout", "u1"), ("_pad", "<u2"), ("by_status", "<u4", (8,)),
+                        ("converged", "<u4"), ("behind", "<u4"), ("other", "<u4"), ("silent", "<u4")])
+assert (gdir_query_dt.itemsize, gdir_totals_dt.itemsize, gdir_row_dt.itemsize) == (40, 36, 80)
+GDIR_ANY, GDIR_WITH_TASK, GDIR_WITHOUT_TASK = 0, 1, 2
+GDIR_BY_SLOT, GDIR_BY_ID_TEXT, GDIR_BY_SIZE_DESC = 0, 1, 2
+GH_LOST, GH_DEGRADED, GH_SOUND, GH_N, GH_NONE = 0, 1, 2, 3, 255
+GR_NO_TASK, GR_CONVERGED, GR_ROLLING, GR_N, GR_NONE = 0, 1, 2, 3, 255
 TS_NAMES = ("PENDING", "PULLING", "RUNNING", "COMPLETED", "FAILED", "PAUSED", "RESTARTING", "UNKNOWN")
 TS_RUNNING, TS_UNKNOWN, TS_N, TS_NONE = 2, 7, 8, 255
 RO_IDLE, RO_STRAY, RO_SILENT, RO_OTHER, RO_BEHIND, RO_CONVERGED, RO_N = 0, 1, 2, 3, 4, 5, 6
@@ -209,6 +222,7 @@ EXPORTS = [
     "pm_rollout_enable", "pm_rollout_ingest", "pm_rollout_get", "pm_rollout_summary", "pm_rollout_tasks", "pm_rollout_groups",
     "pm_rollout_workers", "pm_host_task_state",
     "pm_directory",
+    "pm_group_directory",
 ]
 
 _lib = None
@@ -303,6 +317,7 @@ def lib() -> C.CDLL:
         L.pm_rollout_groups.argtypes = [vp, vp, u32, C.POINTER(u32)]
         L.pm_rollout_workers.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
         L.pm_directory.argtypes = [vp, vp, C.POINTER(u32), vp, vp, u32, C.POINTER(u32)]
+        L.pm_group_directory.argtypes = [vp, vp, vp, vp, u32, vp, u32, C.POINTER(u32), vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -843,6 +858,34 @@ class Engine:
         check(lib().pm_directory(self._h, q.ctypes.data, C.byref(total), counts.ctypes.data, rows.ctypes.data, len(rows),
                                  C.byref(n)))
         return total.value, counts, rows[:n.value]
+
+    def group_directory(self, config_mask: int = 0xFFFFFFFFFFFFFFFF, holds: int = GDIR_ANY, size_min: int = 0,
+                        size_max: int = 0xFFFFFFFF, health_mask: int = (1 << GH_N) - 1, rollout_mask: int = (1 << GR_N) - 1,
+                        order: int = GDIR_BY_SLOT, offset: int = 0, limit=None, want_members: bool = True):
+        """pm_group_directory -> (totals gdir_totals_dt record, by_config uint32 [n_cfgs], rows gdir_row_dt [n], members uint32
+        [n_members] or None): the window [offset, offset + limit) of the listed groups in the chosen order; limit None = to the
+        end, 0 = the counters alone"""
+        q = np.zeros(1, dtype=gdir_query_dt)
+        q[0] = (int(config_mask) & 0xFFFFFFFFFFFFFFFF, int(holds), int(size_min), int(size_max), int(health_mask),
+                int(rollout_mask), int(order), int(offset), 0xFFFFFFFF if limit is None else int(limit))
+        totals = np.zeros(1, dtype=gdir_totals_dt)
+        by_config = np.zeros(PM_MAX_CONFIGS, dtype=np.uint32)
+        n, nm = C.c_uint32(0), C.c_uint32(0)
+        # the counters-only query first (limit 0: no sort, no row): its totals size the buffers for the ONE call that makes the window
+        lim = int(q[0]["limit"])
+        q[0]["limit"] = 0
+        check(lib().pm_group_directory(self._h, q.ctypes.data, totals.ctypes.data, by_config.ctypes.data, len(by_config), None, 0,
+                                       C.byref(n), None, 0, C.byref(nm)))
+        q[0]["limit"] = lim
+        total, off = int(totals[0]["total"]), int(q[0]["offset"])
+        rows = np.zeros(0 if off >= total else min(lim, total - off), dtype=gdir_row_dt)
+        members = np.zeros(int(totals[0]["members_total"]) if len(rows) else 0, dtype=np.uint32) if want_members else None
+        if len(rows):
+            check(lib().pm_group_directory(self._h, q.ctypes.data, totals.ctypes.data, by_config.ctypes.data, len(by_config),
+                                           rows.ctypes.data, len(rows), C.byref(n),
+                                           members.ctypes.data if want_members and len(members) else None,
+                                           len(members) if want_members else 0, C.byref(nm)))
+        return totals[0], by_config[:int(totals[0]["n_cfgs"])].copy(), rows[:n.value], None if members is None else members[:nm.value]
 
     def compat_masks(self) -> np.ndarray:
         out = np.zeros(self.W, dtype=np.uint64)

@@ -538,6 +538,37 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::vector<std::string> dead_nodes() const;            // the Dead nodes' addresses, in row order (the pool test stays the host's)
   static const char* status_name(uint32_t status);        // NodeStatus as `{:?}` prints it
 
+  // ---- group directory (INTEGRATION.md "Group directory"; gpu_match_groupdir.cpp): GET /groups joined, filtered and paged —
+  // the groups as the reference's route lists them (api/routes/groups.rs:32-66, get_all_groups' id-text order), each with the
+  // health class of its members (the liveness ledger), its rollout class (the rollout ledger) and its claimed task; the
+  // groups_count gauge (metrics/sync_service.rs:272-286); the groups that stand on a member that is not Healthy.  Only the
+  // asked window and the counters leave the device.  A class filter other than "all" needs its ledger (enable_liveness /
+  // enable_rollout), else EngineError(PM_ESTATE).  Two deviations: a group's nodes on equal ranks are ordered by row (the
+  // ranks sync_nodes keeps are a permutation, so: none in practice), and created_at is the plugin's clock, as in
+  // get_all_groups.  LOCK ORDER: nodes, tasks, the engine.  get_all_groups stays as it is.
+  struct GroupFilter {
+    uint64_t config_mask = ~0ull;  // bit c: the configuration of constructor index c
+    uint32_t holds = PM_GDIR_ANY;
+    uint32_t size_min = 0, size_max = 0xFFFFFFFFu;
+    uint32_t health_mask = (1u << PM_GH_N) - 1u, rollout_mask = (1u << PM_GR_N) - 1u;
+  };
+  struct ListedNodeGroup {
+    NodeGroup group;                     // id text, node address texts in member order, the plugin's created_at, the configuration name
+    uint32_t health = PM_GH_NONE;        // PM_GH_*, PM_GH_NONE: liveness is off
+    uint32_t rollout = PM_GR_NONE;       // PM_GR_*, PM_GR_NONE: rollout is off
+    std::optional<std::string> task_id;  // the claimed task
+    pm_gdir_row row{};                   // the counters per status and per rollout relation
+  };
+  struct GroupListing {
+    uint32_t total = 0;        // the whole filtered list's length, not the window's
+    pm_gdir_totals totals{};
+    std::vector<ListedNodeGroup> groups;  // the window
+  };
+  GroupListing list_groups(const GroupFilter& filter, uint32_t order = PM_GDIR_BY_ID_TEXT, uint32_t offset = 0,
+                           uint32_t limit = 0xFFFFFFFFu) const;
+  std::map<std::string, uint32_t> group_counts() const;  // configuration name -> groups, present ones only: one counters-only query
+  std::vector<ListedNodeGroup> degraded_groups() const;  // health LOST or DEGRADED, in id-text order
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -660,6 +691,14 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // node directory (gpu_match_directory.cpp): one window through the size query, checked against the node table
   std::vector<pm_dir_row> directory_locked(const pm_dir_query& q, uint32_t* total, uint32_t* counts) const;
   std::vector<std::string> nodes_of_status_locked(uint32_t status) const;
+  // group directory (gpu_match_groupdir.cpp): the counters-only query, then one sized call; checked against the plugin's tables
+  struct GroupWindow {
+    pm_gdir_totals totals{};
+    std::vector<pm_gdir_row> rows;
+    std::vector<uint32_t> members;
+  };
+  GroupWindow group_directory_locked(const pm_gdir_query& q, uint32_t* by_config) const;
+  std::vector<ListedNodeGroup> listed_groups_locked(const GroupWindow& w) const;
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

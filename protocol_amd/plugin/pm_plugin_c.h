@@ -216,6 +216,17 @@ int32_t pmx_status_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_uninvited_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_dead_nodes(pmx_plugin*, char* out, size_t cap, size_t* needed);
 
+/* ---- group directory (pm_plugin_groupdir_c.cpp): GpuMatchPlugin::list_groups / group_counts / degraded_groups.  The texts,
+ * numbers in decimal: pmx_list_groups "total\t<total>\t<members total>", then per group of the window, in listing order,
+ * "<group id>\t<configuration name>\t<size>\t<health: lost, degraded, sound or ->\t<rollout: no_task, converged, rolling or ->\t
+ * <task id or ->\t<created_at>\t<address>,<address>,..." (the nodes in member order); pmx_degraded_groups the same lines without
+ * the first; pmx_group_counts "<configuration name>\t<count>" per configuration that has a group.  order: 0 = by slot, 1 = by
+ * id text, 2 = by size, largest first; limit UINT32_MAX = to the end; a class mask other than 7 needs its ledger. */
+int32_t pmx_list_groups(pmx_plugin*, uint64_t config_mask, uint32_t holds, uint32_t size_min, uint32_t size_max, uint32_t health_mask,
+                        uint32_t rollout_mask, uint32_t order, uint32_t offset, uint32_t limit, char* out, size_t cap, size_t* needed);
+int32_t pmx_group_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_degraded_groups(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

@@ -393,6 +393,68 @@ pub const DC_OTHER: u32 = 2;
 pub const DC_DEAD: u32 = 3;
 pub const DC_N: u32 = 4;
 
+/// pm_gdir_query / pm_gdir_totals / pm_gdir_row (include/pm_engine.h): the group directory's query, counters and joined row
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_gdir_query {
+    pub config_mask: u64,
+    pub holds: u32,
+    pub size_min: u32,
+    pub size_max: u32,
+    pub health_mask: u32,
+    pub rollout_mask: u32,
+    pub order: u32,
+    pub offset: u32,
+    pub limit: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_gdir_totals {
+    pub total: u32,
+    pub members_total: u32,
+    pub by_health: [u32; 3],
+    pub by_rollout: [u32; 3],
+    pub n_cfgs: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_gdir_row {
+    pub group_id: u64,
+    pub slot: u32,
+    pub config: u32,
+    pub size: u32,
+    pub task: u32,
+    pub member_begin: u32,
+    pub health: u8,
+    pub rollout: u8,
+    pub _pad: u16,
+    pub by_status: [u32; 8],
+    pub converged: u32,
+    pub behind: u32,
+    pub other: u32,
+    pub silent: u32,
+}
+
+/// PM_GDIR_* (holds, order), PM_GH_* (health classes), PM_GR_* (rollout classes)
+pub const GDIR_ANY: u32 = 0;
+pub const GDIR_WITH_TASK: u32 = 1;
+pub const GDIR_WITHOUT_TASK: u32 = 2;
+pub const GDIR_BY_SLOT: u32 = 0;
+pub const GDIR_BY_ID_TEXT: u32 = 1;
+pub const GDIR_BY_SIZE_DESC: u32 = 2;
+pub const GH_LOST: u32 = 0;
+pub const GH_DEGRADED: u32 = 1;
+pub const GH_SOUND: u32 = 2;
+pub const GH_N: u32 = 3;
+pub const GH_NONE: u32 = 255;
+pub const GR_NO_TASK: u32 = 0;
+pub const GR_CONVERGED: u32 = 1;
+pub const GR_ROLLING: u32 = 2;
+pub const GR_N: u32 = 3;
+pub const GR_NONE: u32 = 255;
+
 /// PM_TS_* (TaskState, shared/src/models/task.rs:12-22, in its order), PM_TS_NONE, PM_RO_*
 pub const TS_PENDING: u32 = 0;
 pub const TS_PULLING: u32 = 1;
@@ -637,6 +699,9 @@ extern "C" {
     fn pm_rollout_workers(e: *mut c_void, class_mask: u32, rows: *mut pm_ro_worker_row, cap: u32, n: *mut u32) -> i32;
     fn pm_directory(e: *mut c_void, q: *const pm_dir_query, total: *mut u32, counts: *mut u32, rows: *mut pm_dir_row, cap: u32,
                     n_rows: *mut u32) -> i32;
+    fn pm_group_directory(e: *mut c_void, q: *const pm_gdir_query, totals: *mut pm_gdir_totals, by_config: *mut u32, cap_cfgs: u32,
+                          rows: *mut pm_gdir_row, cap_rows: u32, n_rows: *mut u32, members: *mut u32, cap_members: u32,
+                          n_members: *mut u32) -> i32;
     fn pm_host_task_state(s: *const c_char) -> u32;
 }
 
@@ -831,6 +896,42 @@ pub struct ListedNode {
     pub unhealthy_counter: u32,
     pub task_state: u32,           // the reported state (TS_*), TS_NONE: no report or rollout off
     pub group: Option<ListedGroup>,
+}
+
+/// the filter of list_groups (gpu_match_groupdir.cpp's GroupFilter): `GroupFilter::default()` lists every group
+#[derive(Debug, Clone, Copy)]
+pub struct GroupFilter {
+    pub config_mask: u64,          // bit c: the configuration of constructor index c
+    pub holds: u32,
+    pub size_min: u32,
+    pub size_max: u32,
+    pub health_mask: u32,
+    pub rollout_mask: u32,
+}
+
+impl Default for GroupFilter {
+    fn default() -> Self {
+        GroupFilter { config_mask: u64::MAX, holds: GDIR_ANY, size_min: 0, size_max: u32::MAX, health_mask: (1 << GH_N) - 1,
+                      rollout_mask: (1 << GR_N) - 1 }
+    }
+}
+
+/// a group of the group directory: the NodeGroup the route renders, its classes, its claimed task, its counters
+#[derive(Debug, Clone)]
+pub struct ListedNodeGroup {
+    pub group: NodeGroup,
+    pub health: u32,               // GH_*, GH_NONE: liveness is off
+    pub rollout: u32,              // GR_*, GR_NONE: rollout is off
+    pub task_id: Option<String>,   // the claimed task
+    pub row: pm_gdir_row,
+}
+
+/// one window of the group directory (gpu_match_groupdir.cpp's GroupListing)
+#[derive(Default, Debug, Clone)]
+pub struct GroupListing {
+    pub total: u32,                // the whole filtered list's length, not the window's
+    pub totals: pm_gdir_totals,
+    pub groups: Vec<ListedNodeGroup>,
 }
 
 /// one window of the store's ordered listing (gpu_match_directory.cpp's NodeListing)
@@ -2591,6 +2692,109 @@ impl GpuMatchPlugin {
 
     /// what sync_chain_with_nodes walks (status_update/mod.rs:118-142): the Dead nodes; the pool test stays the host's
     pub fn dead_nodes(&self) -> Result<Vec<String>> { self.nodes_of_status(NS_DEAD) }
+
+    // ---- group directory (gpu_match_groupdir.cpp, statement for statement): GET /groups joined, filtered and paged over
+    // pm_group_directory, the groups_count gauge, the groups that stand on a member that is not Healthy.  LOCK ORDER: nodes,
+    // tasks, the engine.  get_all_groups stays as it is.
+
+    /// one window, checked against the plugin's tables (the node and task locks are held).  The COUNTERS-ONLY query first
+    /// (limit 0: one synchronisation, no sort, no row): its totals size the buffers, and ONE call behind it makes the order and
+    /// the window; the engine's own size query (a null row buffer) would make the order twice.
+    fn group_directory_locked(&self, t: &NodeTable, tasks: &[Task], q: &pm_gdir_query, by_config: Option<&mut [u32; 64]>)
+                              -> Result<(pm_gdir_totals, Vec<pm_gdir_row>, Vec<u32>)> {
+        let (by_config, cap_cfgs) = by_config.map_or((std::ptr::null_mut(), 0u32), |c| (c.as_mut_ptr(), 64u32));
+        let mut totals = pm_gdir_totals::default();
+        let counters = pm_gdir_query { limit: 0, ..*q };
+        let (mut have, mut have_members) = (0u32, 0u32);
+        check(unsafe { pm_group_directory(self.engine, &counters, &mut totals, by_config, cap_cfgs, std::ptr::null_mut(), 0, &mut have,
+                                          std::ptr::null_mut(), 0, &mut have_members) })?;
+        have = if q.offset >= totals.total { 0 } else { q.limit.min(totals.total - q.offset) };
+        if have == 0 { return Ok((totals, Vec::new(), Vec::new())); }
+        let mut rows = vec![pm_gdir_row::default(); have as usize];
+        let mut members = vec![0u32; totals.members_total.max(1) as usize];
+        let (mut got, mut got_members) = (0u32, 0u32);
+        check(unsafe { pm_group_directory(self.engine, q, &mut totals, by_config, cap_cfgs, rows.as_mut_ptr(), rows.len() as u32,
+                                          &mut got, members.as_mut_ptr(), members.len() as u32, &mut got_members) })?;
+        if got as usize > rows.len() || got_members as usize > members.len() {
+            return Err(anyhow!("group directory: the window grew between two calls"));
+        }
+        rows.truncate(got as usize);
+        members.truncate(got_members as usize);
+        for r in &rows {
+            if r.config as usize >= self.config_names.len() {
+                return Err(anyhow!("group directory: the engine names a configuration the plugin has not"));
+            }
+            if r.task != PM_NONE && r.task as usize >= tasks.len() {
+                return Err(anyhow!("group directory: the engine names a task the plugin has not"));
+            }
+            if r.member_begin as u64 + r.size as u64 > members.len() as u64 {
+                return Err(anyhow!("group directory: a row's members lie outside the window's"));
+            }
+        }
+        if members.iter().any(|&m| m as usize >= t.address_strings.len()) {
+            return Err(anyhow!("group directory: the engine lists a member the plugin has no address of"));
+        }
+        Ok((totals, rows, members))
+    }
+
+    fn listed_groups_locked(&self, t: &NodeTable, tasks: &[Task], rows: &[pm_gdir_row], members: &[u32]) -> Vec<ListedNodeGroup> {
+        rows.iter().map(|r| {
+            let mem = &members[r.member_begin as usize..(r.member_begin + r.size) as usize];
+            // (formed, creation not reported yet: now, as make_group and list_nodes answer; the C++ twin asks its `clock`, which
+            // is the same clock unless a test has set it)
+            let created_at = self.group_created_at.lock().get(&r.group_id).copied().unwrap_or_else(chrono::Utc::now);
+            let group = NodeGroup {
+                id: format!("{:x}", r.group_id),
+                nodes: mem.iter().map(|&w| t.address_strings[w as usize].clone()).collect::<BTreeSet<String>>(),
+                created_at,
+                configuration_name: self.config_names[r.config as usize].clone(),
+            };
+            let task_id = if r.task != PM_NONE { Some(tasks[r.task as usize].id.to_string()) } else { None };
+            ListedNodeGroup { group, health: r.health as u32, rollout: r.rollout as u32, task_id, row: *r }
+        }).collect()
+    }
+
+    /// GET /groups (api/routes/groups.rs:32-66): the window [offset, offset + limit) of the filtered groups in the chosen order
+    /// (GDIR_BY_ID_TEXT is the reference's, mod.rs:1040)
+    pub fn list_groups(&self, filter: &GroupFilter, order: u32, offset: u32, limit: u32) -> Result<GroupListing> {
+        let t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_gdir_query { config_mask: filter.config_mask, holds: filter.holds, size_min: filter.size_min,
+                                size_max: filter.size_max, health_mask: filter.health_mask, rollout_mask: filter.rollout_mask, order,
+                                offset, limit };
+        let (totals, rows, members) = self.group_directory_locked(&t, &tasks, &q, None)?;
+        Ok(GroupListing { total: totals.total, totals, groups: self.listed_groups_locked(&t, &tasks, &rows, &members) })
+    }
+
+    /// the groups_count gauge (metrics/sync_service.rs:272-286): configuration name -> groups, present ones only; one
+    /// counters-only query
+    pub fn group_counts(&self) -> Result<std::collections::BTreeMap<String, u32>> {
+        let t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_gdir_query { config_mask: u64::MAX, holds: GDIR_ANY, size_min: 0, size_max: u32::MAX, health_mask: (1 << GH_N) - 1,
+                                rollout_mask: (1 << GR_N) - 1, order: GDIR_BY_SLOT, offset: 0, limit: 0 };
+        let mut by_config = [0u32; 64];
+        let (totals, _, _) = self.group_directory_locked(&t, &tasks, &q, Some(&mut by_config))?;
+        if totals.n_cfgs as usize > self.config_names.len() {
+            return Err(anyhow!("group directory: the engine counts a configuration the plugin has not"));
+        }
+        let mut out = std::collections::BTreeMap::new();
+        for c in 0..totals.n_cfgs as usize {
+            if by_config[c] != 0 { *out.entry(self.config_names[c].clone()).or_insert(0) += by_config[c]; }
+        }
+        Ok(out)
+    }
+
+    /// the groups that stand on a member that is not Healthy (health LOST or DEGRADED), in id-text order
+    pub fn degraded_groups(&self) -> Result<Vec<ListedNodeGroup>> {
+        let t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_gdir_query { config_mask: u64::MAX, holds: GDIR_ANY, size_min: 0, size_max: u32::MAX,
+                                health_mask: (1 << GH_LOST) | (1 << GH_DEGRADED), rollout_mask: (1 << GR_N) - 1,
+                                order: GDIR_BY_ID_TEXT, offset: 0, limit: u32::MAX };
+        let (_, rows, members) = self.group_directory_locked(&t, &tasks, &q, None)?;
+        Ok(self.listed_groups_locked(&t, &tasks, &rows, &members))
+    }
 
     /// the ledger's rows as stored (what the tests look at)
     pub fn reported_tasks(&self, rows: &[u32]) -> Result<(Vec<u64>, Vec<u8>)> {

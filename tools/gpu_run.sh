@@ -35,6 +35,10 @@
 #   directory[:<args>]       tools/directory_probe.py [W ...] [--bench DIR]: pm_directory at 10,000 and 100,000 rows — the counters, a
 #                            first and a middle page by row and by address, the full list — beside each what a host does today
 #                            (three full-table reads, a stable sort, the join) -> r27_directory.txt (copy it to profiles/)
+#   groupdir[:<args>]        tools/groupdir_probe.py [W ...] [--bench DIR]: pm_group_directory at 10,000 and 100,000 rows — the counters,
+#                            a first and a middle page in each order, the degraded filter, the full list — beside each what a host
+#                            does today (pm_get_groups + pm_liveness_get + pm_rollout_groups, the join, a sort of id texts)
+#                            -> r28_group_directory.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -165,6 +169,9 @@ PY
     directory)
       timeout -k 10 400 python tools/directory_probe.py $arg --out "$out/r27_directory.txt" > "$out/${n}_directory.log" 2>&1; echo "directory rc=$?"
       tail -20 "$out/${n}_directory.log" ;;
+    groupdir)
+      timeout -k 10 400 python tools/groupdir_probe.py $arg --out "$out/r28_group_directory.txt" > "$out/${n}_groupdir.log" 2>&1; echo "groupdir rc=$?"
+      tail -24 "$out/${n}_groupdir.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
