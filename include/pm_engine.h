@@ -1060,6 +1060,97 @@ int32_t pm_group_directory(pm_engine*, const pm_gdir_query* q, pm_gdir_totals* t
                            pm_gdir_row* rows, uint32_t cap_rows, uint32_t* n_rows,
                            uint32_t* members /* may be NULL */, uint32_t cap_members, uint32_t* n_members);
 
+/* ---- task directory (kernels in pm_taskdir.inc) -----------------------------------------------------------------------------
+ * GET /tasks JOINED, FILTERED AND PAGED.  The reference lists its tasks in one place, TaskStore::get_all_tasks
+ * (store/domains/task_store.rs:57-82, newest first), behind GET /tasks (api/routes/task.rs:20-39); the tasks_count, task_info
+ * and nodes_per_task gauges (metrics/sync_service.rs:228-267) and get_groups_for_task (node_groups/mod.rs:1350-1386) read the
+ * same table.  What an operator asks about a task, can it run on any standing group and has every member of its groups picked
+ * it up, needs columns that live on the device alone: the groups' claims, the live groups per configuration, the rollout
+ * ledger.  A host would fetch pm_task_report's three arrays and pm_rollout_tasks whole, join them on ids, classify, sort and cut
+ * a page; pm_task_directory makes the joined list on the device and hands out ONE WINDOW of it and the counters.  A pure read:
+ * no enable call, no state of its own, nothing cached.
+ *
+ * LISTED.  A task is listed if it is a live row of the caller's CURRENT list (a pending tick is taken in first, as in
+ * pm_directory; deleted rows are skipped, positions are those of the current list) and passes every filter of the query.
+ * config_mask: ~0 is "no configuration filter"; any other value lists a task only if it allows at least one INSTALLED
+ * configuration whose bit is set (bits at or above the number of configurations select nothing and are legal; 0 is PM_EINVAL); a
+ * task whose topo_mask is 0 names only unknown topologies and is listed under ~0 alone.  serve_mask: bits over the SERVING
+ * CLASS, the first match of: PM_TKS_RUNNING some live group holds the task; PM_TKS_WAITING none does and at least one live group
+ * has a configuration the task allows (groups_allowed > 0); PM_TKS_STARVED no such group stands.  rollout_mask: bits over the
+ * ROLLOUT CLASS: PM_TKR_UNHELD no group holds the task; PM_TKR_CONVERGED every group that holds it is converged, by the rule of
+ * pm_rollout_summary.groups_converged, the same comparison; PM_TKR_ROLLING it is held and not every holding group is
+ * converged.  The classes go by the row a group HOLDS (its handle), as the assigned columns do.  With rollout off rollout_mask
+ * must be all classes (7), rows carry PM_TKR_NONE, the reported columns are zero, totals.by_rollout, orphan_uids and
+ * orphan_reporters are zero.  workers_min <= workers_running <= workers_max, inclusive.
+ * ORDER, ties always by ascending list position.  PM_TDIR_BY_LIST: the reference's, newest first (one scan, no sort).
+ * PM_TDIR_BY_OLDEST: the same scan read from its other end.  PM_TDIR_BY_WORKERS_DESC: most assigned workers first.
+ * PM_TDIR_BY_REPORTERS_DESC: the largest sum of reporters[] first; PM_ESTATE with rollout off.
+ * A ROW.  uid (0 where the table was uploaded without ids), created_at, topo_mask as uploaded; task = the position in the
+ * CURRENT list.  ASSIGNED: groups_allowed, groups_running, workers_running are pm_task_report's three columns for that position
+ * at the same moment.  REPORTED: groups_converged, converged and reporters[] are those of the pm_rollout_tasks row whose `task`
+ * is that position (reporters[] sums to the reference's nodes_per_task); zero where no such row exists.  DUPLICATE IDS: an id
+ * names the FIRST live row that carries it, as everywhere in this header: the assigned columns and both classes go by the row a
+ * group holds, the reported columns are credited to that first row, and every other live row with the same id shows zeros
+ * there.  An id of all ones names no task: its reports are orphans.
+ * OUTPUTS.  totals, over the whole list, not the window: tasks = live rows of the list; total = listed; by_serve / by_rollout =
+ * listed tasks per class; unrestricted = listed tasks whose topo_mask is all ones; workers_running / reporters = sums over the
+ * listed tasks; orphan_uids / orphan_reporters = the pm_rollout_tasks rows whose task is PM_NONE (reported ids that name no live
+ * task) and the worker rows that report them, whatever the filters are: the nodes that still report a deleted task; n_cfgs.
+ * by_config[c], c < n_cfgs = listed tasks that allow configuration c (with no filter: pm_config_report's tasks_allowing);
+ * by_config may be NULL, cap_cfgs < n_cfgs with a buffer is PM_ERANGE.  rows = the window [offset, offset + limit) with
+ * pm_directory's conventions: *n_rows = min(limit, total - offset), 0 when offset >= total; offset + limit is never formed,
+ * limit = UINT32_MAX is "to the end", limit = 0 with rows = NULL is the counters-only query.  cap_rows < *n_rows, or rows == NULL
+ * with *n_rows > 0, is PM_ERANGE with totals, by_config (where it fits) and *n_rows written and no row copied.
+ * The device joins: one thread a list entry of the groups adds to the counters of the row it holds and to the live groups of its
+ * configuration; with rollout on the live (id, row) pairs are sorted by eight stable radix passes from ascending row order, so
+ * the first entry of an equal-id run is the first row of the list, pm_rollout_tasks' run reduction is taken over as it is, and
+ * one thread a run finds its row by a lower-bound search or counts an orphan; one thread a slot of the task table classifies,
+ * filters and counts; BY_LIST and BY_OLDEST are one scan of the flags, the two _DESC orders four stable passes over the
+ * complemented key.  One record per group list entry and, with rollout on, the live ids go up; the counters and the window come
+ * down.  With rollout off the counters-only query synchronises once; with it on, the run reduction it takes over sizes its
+ * buffers from two scan totals and synchronises for them.  DETERMINISTIC: integers only, bit-identical from call to call,
+ * independent of the number of workgroups.
+ * ERRORS, everything checked on the host before anything is launched.  PM_EINVAL: a null q, totals or n_rows; config_mask == 0;
+ * serve_mask / rollout_mask == 0 or a bit at or above PM_TKS_N / PM_TKR_N; an unknown order; workers_min > workers_max.
+ * PM_ESTATE: a stepwise tick is in progress; dist_world > 1; no configurations, workers or tasks uploaded; a rollout_mask other
+ * than "all", or BY_REPORTERS_DESC, with the ledger off; rollout on over a task table uploaded without ids.  PM_ERANGE: the
+ * buffers (above); a task index space of 2^28 slots or more.  No call consumes a pending delta, compacts anything, clears a cache
+ * flag or changes what the next tick does. */
+enum { PM_TDIR_BY_LIST = 0, PM_TDIR_BY_OLDEST = 1, PM_TDIR_BY_WORKERS_DESC = 2, PM_TDIR_BY_REPORTERS_DESC = 3 };  /* order */
+enum { PM_TKS_RUNNING = 0, PM_TKS_WAITING = 1, PM_TKS_STARVED = 2, PM_TKS_N = 3 };
+enum { PM_TKR_UNHELD = 0, PM_TKR_CONVERGED = 1, PM_TKR_ROLLING = 2, PM_TKR_N = 3 };
+#define PM_TKR_NONE 255u                                                           /* rollout is off */
+typedef struct pm_tdir_query {          /* 40 B */
+  uint64_t config_mask;                 /* ~0: no filter; else: tasks that allow an installed configuration of the set */
+  uint32_t serve_mask, rollout_mask;    /* bits over PM_TKS_* / PM_TKR_* */
+  uint32_t workers_min, workers_max;    /* workers_running, inclusive */
+  uint32_t order;                       /* PM_TDIR_BY_* */
+  uint32_t offset, limit;               /* the window [offset, offset + limit) of the ordered list */
+  uint32_t _pad;
+} pm_tdir_query;
+typedef struct pm_tdir_totals {         /* 56 B */
+  uint32_t tasks, total;
+  uint32_t by_serve[PM_TKS_N], by_rollout[PM_TKR_N];
+  uint32_t unrestricted;
+  uint32_t workers_running, reporters;
+  uint32_t orphan_uids, orphan_reporters;
+  uint32_t n_cfgs;
+} pm_tdir_totals;
+typedef struct pm_tdir_row {            /* 88 B, padding zero */
+  uint64_t uid;
+  int64_t created_at;
+  uint64_t topo_mask;
+  uint32_t task;                        /* position in the CURRENT list */
+  uint32_t groups_allowed, groups_running, workers_running;   /* pm_task_report's columns */
+  uint32_t groups_converged, converged; /* pm_rollout_tasks' columns */
+  uint32_t reporters[PM_TS_N];
+  uint8_t serve;  /* PM_TKS_* */  uint8_t rollout; /* PM_TKR_* or PM_TKR_NONE */  uint16_t _pad;
+  uint32_t _pad2;
+} pm_tdir_row;
+int32_t pm_task_directory(pm_engine*, const pm_tdir_query* q, pm_tdir_totals* totals,
+                          uint32_t* by_config /* cap_cfgs, may be NULL */, uint32_t cap_cfgs,
+                          pm_tdir_row* rows, uint32_t cap_rows, uint32_t* n_rows);
+
 /* Phase B, reference orientation — NodeGroupsPlugin::filter_tasks (scheduler_impl.rs:11-110) for
  * EVERY worker at once: the T x W topology sweep, the chooser and the per-group claim (SETNX :74).
  * task_of_worker[w] = task index or PM_NONE; applicable_count[w] = number of applicable tasks the

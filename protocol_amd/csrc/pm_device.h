@@ -335,6 +335,55 @@ struct GdirArgs {
   uint32_t* val;             // [total] out: the entry
 };
 
+// task directory (pm_taskdir.inc): the tasks' ordered, filtered, paged listing joined with the groups' claims and the rollout
+// ledger.  A SLOT is a handle of the task index space counted from t_lo: slot r is handle t_lo + r, r < R = t_cap - t_lo.
+enum : uint32_t {  // a slot's counters
+  TD_RUNNING = 0,       // live groups that hold the row
+  TD_WORKERS,           // their members
+  TD_HOLD_CONV,         // those of them that are converged
+  TD_ALLOWED,           // live groups of the configurations its mask allows
+  TD_G_CONV,            // the reported columns, by id: pm_ro_task_row.groups_converged,
+  TD_CONV,              // ... .converged,
+  TD_REP,               // ... .reporters[PM_TS_N]
+  PM_TD_CNT = TD_REP + PM_TS_N
+};
+enum : uint32_t {  // the census, behind the per-configuration counts
+  TD_C_SERVE = PM_MAX_CONFIGS,
+  TD_C_ROLLOUT = TD_C_SERVE + PM_TKS_N,
+  TD_C_UNRESTRICTED = TD_C_ROLLOUT + PM_TKR_N,
+  TD_C_WORKERS,
+  TD_C_REPORTERS,
+  TD_C_ORPHAN_UIDS,
+  TD_C_ORPHAN_REPORTERS,
+  PM_TD_CENSUS
+};
+struct TdirGroup {  // 16 bytes, one per entry of the host's list (tombstones included)
+  uint32_t cfg, size;
+  uint32_t handle;    // the claimed task's handle, PM_NONE: it holds none
+  uint32_t live;      // 0: dissolved
+};
+struct TdirArgs {
+  uint32_t G, n_cfgs, t_lo, t_cap;
+  uint64_t config_mask;              // the query's filter (pm_tdir_query)
+  uint32_t serve_mask, rollout_mask, workers_min, workers_max, order;
+  uint32_t rollout_on;
+  uint32_t offset, n_rows, total;    // the window [offset, offset + n_rows) of the ordered list of `total` entries
+  const TdirGroup* g;        // [G]
+  const uint32_t* ro_gcnt;   // [G * PM_RO_GCNT] the rollout ledger's counters of the groups, or nullptr: it is off
+  const uint64_t *tmask, *tlive;  // the task index space: masks, live bitmap,
+  const uint32_t* tprefix;        // per-word live prefix (positions),
+  const int64_t* created;         // created_at
+  uint32_t* g_per_cfg;       // [PM_MAX_CONFIGS] zeroed; out (group pass): live groups per configuration
+  uint32_t* cnt;             // [R * PM_TD_CNT] zeroed; out (group pass, join, task pass), in (emit)
+  uint32_t* census;          // [PM_TD_CENSUS] zeroed; out
+  uint8_t* cls;              // [2 R] out: the slot's serving and rollout class
+  uint32_t* flag;            // [R] out: the slot is listed
+  const uint32_t* off;       // [R + 1] the flags' exclusive scan: a listed slot's place in list order
+  uint32_t* win;             // [n_rows] out (BY_LIST, BY_OLDEST): the window's slots
+  uint64_t* key;             // [total] out (the _DESC orders): the complemented key, in list order
+  uint32_t* val;             // [total] out: the slot
+};
+
 struct ClaimArgs {
   uint32_t R;            // rows: all workers, or the workers `rows` lists (multi-GPU: the ones this rank owns)
   const uint32_t* rows;  // nullptr = row r is worker r
@@ -630,6 +679,17 @@ void launch_gdir_window(const GdirArgs& a, hipStream_t s);
 void launch_gdir_keys(const GdirArgs& a, hipStream_t s);
 // rows[k] = the joined record of list entry list[k], k < n (member_begin is the host's: it lays the members out)
 void launch_gdir_emit(const GdirArgs& a, const uint32_t* list, uint32_t n, pm_gdir_row* rows, hipStream_t s);
+// task directory (pm_taskdir.inc)
+void launch_tdir_groups(const TdirArgs& a, hipStream_t s);
+// run d of the rollout ledger's per-task table -> the slot of the first live row that carries its id (key / val [n_pairs]: the
+// live (id, slot) pairs sorted by id, ties in slot order), or an orphan
+void launch_tdir_join(const TdirArgs& a, const pm_ro_task_row* runs, uint32_t D, const uint64_t* key, const uint32_t* val,
+                      uint32_t n_pairs, hipStream_t s);
+void launch_tdir_tasks(const TdirArgs& a, hipStream_t s);
+void launch_tdir_window(const TdirArgs& a, hipStream_t s);
+void launch_tdir_keys(const TdirArgs& a, hipStream_t s);
+// rows[k] = the joined record of slot list[k], handles[k] its handle, k < n (uid is the host's: the ids never went up whole)
+void launch_tdir_emit(const TdirArgs& a, const uint32_t* list, uint32_t n, pm_tdir_row* rows, uint32_t* handles, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

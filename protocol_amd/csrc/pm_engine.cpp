@@ -235,6 +235,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_rollout.inc"
 #include "pm_engine_directory.inc"
 #include "pm_engine_groupdir.inc"
+#include "pm_engine_taskdir.inc"
 
 extern "C" {
 #include "pm_engine_tick.inc"

@@ -142,6 +142,25 @@ struct GroupDir {
   std::vector<pm_gdir_row> h_rows;  // the window, before the caller's buffers are known to hold it
 };
 
+// ---- task directory (pm_engine_taskdir.inc): scratch of one pm_task_directory call and nothing else, like Directory
+struct TaskDir {
+  DevBuf<TdirGroup> g;        // the join's other side: the host's group list
+  DevBuf<uint32_t> cnt;       // [R * PM_TD_CNT] the slots' counters, behind them [PM_MAX_CONFIGS] the live groups per configuration, [PM_TD_CENSUS] the census
+  DevBuf<uint8_t> cls;        // [2 R]
+  DevBuf<uint32_t> flag, off; // [R] (+ 1): the listing flags and their scan
+  DevBuf<uint32_t> win;       // BY_LIST, BY_OLDEST: the window's slots
+  DevBuf<uint64_t> key[2];    // the id join's sorted (id, slot) pairs, then the sorted orders' keys and slots, ping-pong
+  DevBuf<uint32_t> val[2], hist, hist_scan;
+  DevBuf<pm_tdir_row> rows;
+  DevBuf<uint32_t> handles;   // the window's handles (the host writes the ids by them)
+  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_TD_CENSUS) the census
+  std::vector<TdirGroup> h_g;
+  std::vector<uint64_t> h_key;      // the live rows' ids, in list order, ...
+  std::vector<uint32_t> h_val;      // ... and their slots
+  std::vector<pm_tdir_row> h_rows;  // the window, before the caller's buffer is known to hold it
+  std::vector<uint32_t> h_handles;
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -379,4 +398,5 @@ struct pm_engine {
   Rollout ro;
   Directory dir;  // (scratch only: never switched)
   GroupDir gdir;  // (the same)
+  TaskDir tdir;   // (the same)
 };

@@ -119,6 +119,19 @@ GDIR_ANY, GDIR_WITH_TASK, GDIR_WITHOUT_TASK = 0, 1, 2
 GDIR_BY_SLOT, GDIR_BY_ID_TEXT, GDIR_BY_SIZE_DESC = 0, 1, 2
 GH_LOST, GH_DEGRADED, GH_SOUND, GH_N, GH_NONE = 0, 1, 2, 3, 255
 GR_NO_TASK, GR_CONVERGED, GR_ROLLING, GR_N, GR_NONE = 0, 1, 2, 3, 255
+# pm_tdir_query, pm_tdir_totals, pm_tdir_row, PM_TDIR_*, PM_TKS_*, PM_TKR_* (include/pm_engine.h): task directory
+tdir_query_dt = np.dtype([("config_mask", "<u8"), ("serve_mask", "<u4"), ("rollout_mask", "<u4"), ("workers_min", "<u4"),
+                          ("workers_max", "<u4"), ("order", "<u4"), ("offset", "<u4"), ("limit", "<u4"), ("_pad", "<u4")])
+tdir_totals_dt = np.dtype([("tasks", "<u4"), ("total", "<u4"), ("by_serve", "<u4", (3,)), ("by_rollout", "<u4", (3,)),
+                           ("unrestricted", "<u4"), ("workers_running", "<u4"), ("reporters", "<u4"), ("orphan_uids", "<u4"),
+                           ("orphan_reporters", "<u4"), ("n_cfgs", "<u4")])
+tdir_row_dt = np.dtype([("uid", "<u8"), ("created_at", "<i8"), ("topo_mask", "<u8"), ("task", "<u4"), ("groups_allowed", "<u4"),
+                        ("groups_running", "<u4"), ("workers_running", "<u4"), ("groups_converged", "<u4"), ("converged", "<u4"),
+                        ("reporters", "<u4", (8,)), ("serve", "u1"), ("rollout", "u1"), ("_pad", "<u2"), ("_pad2", "<u4")])
+assert (tdir_query_dt.itemsize, tdir_totals_dt.itemsize, tdir_row_dt.itemsize) == (40, 56, 88)
+TDIR_BY_LIST, TDIR_BY_OLDEST, TDIR_BY_WORKERS_DESC, TDIR_BY_REPORTERS_DESC = 0, 1, 2, 3
+TKS_RUNNING, TKS_WAITING, TKS_STARVED, TKS_N = 0, 1, 2, 3
+TKR_UNHELD, TKR_CONVERGED, TKR_ROLLING, TKR_N, TKR_NONE = 0, 1, 2, 3, 255
 TS_NAMES = ("PENDING", "PULLING", "RUNNING", "COMPLETED", "FAILED", "PAUSED", "RESTARTING", "UNKNOWN")
 TS_RUNNING, TS_UNKNOWN, TS_N, TS_NONE = 2, 7, 8, 255
 RO_IDLE, RO_STRAY, RO_SILENT, RO_OTHER, RO_BEHIND, RO_CONVERGED, RO_N = 0, 1, 2, 3, 4, 5, 6
@@ -223,6 +236,7 @@ EXPORTS = [
     "pm_rollout_workers", "pm_host_task_state",
     "pm_directory",
     "pm_group_directory",
+    "pm_task_directory",
 ]
 
 _lib = None
@@ -318,6 +332,7 @@ def lib() -> C.CDLL:
         L.pm_rollout_workers.argtypes = [vp, u32, vp, u32, C.POINTER(u32)]
         L.pm_directory.argtypes = [vp, vp, C.POINTER(u32), vp, vp, u32, C.POINTER(u32)]
         L.pm_group_directory.argtypes = [vp, vp, vp, vp, u32, vp, u32, C.POINTER(u32), vp, u32, C.POINTER(u32)]
+        L.pm_task_directory.argtypes = [vp, vp, vp, vp, u32, vp, u32, C.POINTER(u32)]
         L.pm_dist_match_begin.argtypes = [vp, C.POINTER(DistXfer)]
         L.pm_dist_tick_end.argtypes = [vp, C.POINTER(Stats)]
         L.pm_match_per_task_device.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
@@ -886,6 +901,29 @@ class Engine:
                                            members.ctypes.data if want_members and len(members) else None,
                                            len(members) if want_members else 0, C.byref(nm)))
         return totals[0], by_config[:int(totals[0]["n_cfgs"])].copy(), rows[:n.value], None if members is None else members[:nm.value]
+
+    def task_directory(self, config_mask: int = 0xFFFFFFFFFFFFFFFF, serve_mask: int = (1 << TKS_N) - 1,
+                       rollout_mask: int = (1 << TKR_N) - 1, workers_min: int = 0, workers_max: int = 0xFFFFFFFF,
+                       order: int = TDIR_BY_LIST, offset: int = 0, limit=None):
+        """pm_task_directory -> (totals tdir_totals_dt record, by_config uint32 [n_cfgs], rows tdir_row_dt [n]): the window
+        [offset, offset + limit) of the listed tasks in the chosen order; limit None = to the end, 0 = the counters alone"""
+        q = np.zeros(1, dtype=tdir_query_dt)
+        lim = 0xFFFFFFFF if limit is None else int(limit)
+        # the counters-only query first (limit 0: no sort, no row): its total sizes the buffer for the call that makes the window
+        q[0] = (int(config_mask) & 0xFFFFFFFFFFFFFFFF, int(serve_mask), int(rollout_mask), int(workers_min), int(workers_max),
+                int(order), int(offset), 0, 0)
+        totals = np.zeros(1, dtype=tdir_totals_dt)
+        by_config = np.zeros(PM_MAX_CONFIGS, dtype=np.uint32)
+        n = C.c_uint32(0)
+        check(lib().pm_task_directory(self._h, q.ctypes.data, totals.ctypes.data, by_config.ctypes.data, len(by_config), None, 0,
+                                      C.byref(n)))
+        q[0]["limit"] = lim
+        total, off = int(totals[0]["total"]), int(q[0]["offset"])
+        rows = np.zeros(0 if off >= total else min(lim, total - off), dtype=tdir_row_dt)
+        if len(rows):
+            check(lib().pm_task_directory(self._h, q.ctypes.data, totals.ctypes.data, by_config.ctypes.data, len(by_config),
+                                          rows.ctypes.data, len(rows), C.byref(n)))
+        return totals[0], by_config[:int(totals[0]["n_cfgs"])].copy(), rows[:n.value]
 
     def compat_masks(self) -> np.ndarray:
         out = np.zeros(self.W, dtype=np.uint64)

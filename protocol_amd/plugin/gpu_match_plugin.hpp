@@ -569,6 +569,48 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::map<std::string, uint32_t> group_counts() const;  // configuration name -> groups, present ones only: one counters-only query
   std::vector<ListedNodeGroup> degraded_groups() const;  // health LOST or DEGRADED, in id-text order
 
+  // ---- task directory (INTEGRATION.md "Task directory"; gpu_match_taskdir.cpp): GET /tasks joined, filtered and paged — the
+  // tasks as TaskStore::get_all_tasks lists them (store/domains/task_store.rs:57-82, newest first; api/routes/task.rs:20-39), each
+  // with what get_groups_for_task would count (node_groups/mod.rs:1350-1386), what its nodes report and its two classes: can it
+  // run on a standing group, has every member of its groups picked it up.  Ids and names are the plugin's own, by the position
+  // the engine reports.  Only the asked window and the counters leave the device.  A rollout filter other than "all" and the
+  // order by reporters need enable_rollout, else EngineError(PM_ESTATE); queued task reports are not flushed here (flush_rollout,
+  // or any rollout read, does).  LOCK ORDER: nodes, tasks, the engine.
+  struct TaskFilter {
+    uint64_t config_mask = ~0ull;  // ~0: no filter; else bit c: tasks that allow the configuration of constructor index c
+    uint32_t serve_mask = (1u << PM_TKS_N) - 1u, rollout_mask = (1u << PM_TKR_N) - 1u;
+    uint32_t workers_min = 0, workers_max = 0xFFFFFFFFu;
+  };
+  struct ListedTask {
+    std::string id, name;
+    uint32_t serve = PM_TKS_STARVED;   // PM_TKS_*
+    uint32_t rollout = PM_TKR_NONE;    // PM_TKR_*, PM_TKR_NONE: rollout is off
+    pm_tdir_row row{};                 // the assigned and the reported columns
+  };
+  struct TaskListing {
+    uint32_t total = 0;        // the whole filtered list's length, not the window's
+    pm_tdir_totals totals{};
+    std::vector<ListedTask> tasks;  // the window
+  };
+  struct TaskCounts {
+    pm_tdir_totals totals{};
+    std::map<std::string, uint32_t> by_config;  // configuration name -> tasks that allow it, present ones only
+  };
+  // what sync_orchestrator_statistics sets (metrics/sync_service.rs:209-286); the gauges themselves stay the host's
+  struct OrchestratorStatistics {
+    std::map<std::string, uint32_t> nodes_by_status;  // lowercase status name -> nodes, present ones only
+    uint32_t tasks_count = 0;
+    std::vector<NodesPerTask> nodes_per_task;         // (id, name or "unknown", count) of the tasks with reporters
+    std::map<std::string, uint32_t> groups_count;     // configuration name -> groups, present ones only
+  };
+  TaskListing list_tasks(const TaskFilter& filter, uint32_t order = PM_TDIR_BY_LIST, uint32_t offset = 0,
+                         uint32_t limit = 0xFFFFFFFFu) const;
+  TaskCounts task_counts() const;                  // one counters-only query
+  std::vector<ListedTask> starved_tasks() const;   // serving class STARVED, in list order
+  // counters-only queries of the three directories and the rollout task table, one after the other (each under the locks it
+  // needs: not one snapshot); needs enable_liveness and enable_rollout
+  OrchestratorStatistics orchestrator_statistics();
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -699,6 +741,13 @@ class GpuMatchPlugin : public SchedulerPlugin {
   };
   GroupWindow group_directory_locked(const pm_gdir_query& q, uint32_t* by_config) const;
   std::vector<ListedNodeGroup> listed_groups_locked(const GroupWindow& w) const;
+  // task directory (gpu_match_taskdir.cpp): the counters-only query, then one sized call; checked against the plugin's task list
+  struct TaskWindow {
+    pm_tdir_totals totals{};
+    std::vector<pm_tdir_row> rows;
+  };
+  TaskWindow task_directory_locked(const pm_tdir_query& q, uint32_t* by_config) const;
+  std::vector<ListedTask> listed_tasks_locked(const TaskWindow& w) const;
   // tick_dist's (the management loop's thread only): what pm_dist_configure was last told
   std::atomic<uint32_t> dist_rank_{0};   // (read by emit_group_webhooks on any thread)
   uint32_t dist_world_ = 1;

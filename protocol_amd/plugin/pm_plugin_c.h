@@ -227,6 +227,23 @@ int32_t pmx_list_groups(pmx_plugin*, uint64_t config_mask, uint32_t holds, uint3
 int32_t pmx_group_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_degraded_groups(pmx_plugin*, char* out, size_t cap, size_t* needed);
 
+/* ---- task directory (pm_plugin_taskdir_c.cpp): GpuMatchPlugin::list_tasks / task_counts / starved_tasks /
+ * orchestrator_statistics.  The texts, numbers in decimal: pmx_list_tasks "total\t<total>\t<tasks>", then per task of the window, in
+ * listing order, "<task id>\t<name>\t<serve: running, waiting, starved>\t<rollout: unheld, converged, rolling or ->\t<groups
+ * allowed>\t<groups running>\t<workers running>\t<groups converged>\t<converged>\t<reporters>"; pmx_starved_tasks the same lines
+ * without the first; pmx_task_counts "tasks\t<n>", "serve\t<running>\t<waiting>\t<starved>", "rollout\t<unheld>\t<converged>\t
+ * <rolling>", "unrestricted\t<n>", "workers_running\t<n>", "reporters\t<n>", "orphans\t<ids>\t<reporters>", then
+ * "<configuration name>\t<tasks allowing it>" per configuration some task allows; pmx_orchestrator_statistics "nodes\t<status>\t
+ * <count>" per status some node has, "tasks_count\t<n>", "nodes_per_task\t<task id>\t<name or unknown>\t<count>" per task with
+ * reporters, "groups_count\t<configuration name>\t<count>" per configuration that has a group (needs pmx_enable_liveness and
+ * pmx_enable_rollout).  order: 0 = the list's, newest first, 1 = oldest first, 2 = by assigned workers, 3 = by reporters, largest
+ * first; limit UINT32_MAX = to the end; a rollout mask other than 7 and order 3 need the rollout ledger. */
+int32_t pmx_list_tasks(pmx_plugin*, uint64_t config_mask, uint32_t serve_mask, uint32_t rollout_mask, uint32_t workers_min,
+                       uint32_t workers_max, uint32_t order, uint32_t offset, uint32_t limit, char* out, size_t cap, size_t* needed);
+int32_t pmx_task_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_starved_tasks(pmx_plugin*, char* out, size_t cap, size_t* needed);
+int32_t pmx_orchestrator_statistics(pmx_plugin*, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

@@ -455,6 +455,70 @@ pub const GR_ROLLING: u32 = 2;
 pub const GR_N: u32 = 3;
 pub const GR_NONE: u32 = 255;
 
+/// pm_tdir_query / pm_tdir_totals / pm_tdir_row (include/pm_engine.h): the task directory's query, counters and joined row
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_tdir_query {
+    pub config_mask: u64,
+    pub serve_mask: u32,
+    pub rollout_mask: u32,
+    pub workers_min: u32,
+    pub workers_max: u32,
+    pub order: u32,
+    pub offset: u32,
+    pub limit: u32,
+    pub _pad: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_tdir_totals {
+    pub tasks: u32,
+    pub total: u32,
+    pub by_serve: [u32; 3],
+    pub by_rollout: [u32; 3],
+    pub unrestricted: u32,
+    pub workers_running: u32,
+    pub reporters: u32,
+    pub orphan_uids: u32,
+    pub orphan_reporters: u32,
+    pub n_cfgs: u32,
+}
+
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct pm_tdir_row {
+    pub uid: u64,
+    pub created_at: i64,
+    pub topo_mask: u64,
+    pub task: u32,
+    pub groups_allowed: u32,
+    pub groups_running: u32,
+    pub workers_running: u32,
+    pub groups_converged: u32,
+    pub converged: u32,
+    pub reporters: [u32; 8],
+    pub serve: u8,
+    pub rollout: u8,
+    pub _pad: u16,
+    pub _pad2: u32,
+}
+
+/// PM_TDIR_* (order), PM_TKS_* (serving classes), PM_TKR_* (rollout classes)
+pub const TDIR_BY_LIST: u32 = 0;
+pub const TDIR_BY_OLDEST: u32 = 1;
+pub const TDIR_BY_WORKERS_DESC: u32 = 2;
+pub const TDIR_BY_REPORTERS_DESC: u32 = 3;
+pub const TKS_RUNNING: u32 = 0;
+pub const TKS_WAITING: u32 = 1;
+pub const TKS_STARVED: u32 = 2;
+pub const TKS_N: u32 = 3;
+pub const TKR_UNHELD: u32 = 0;
+pub const TKR_CONVERGED: u32 = 1;
+pub const TKR_ROLLING: u32 = 2;
+pub const TKR_N: u32 = 3;
+pub const TKR_NONE: u32 = 255;
+
 /// PM_TS_* (TaskState, shared/src/models/task.rs:12-22, in its order), PM_TS_NONE, PM_RO_*
 pub const TS_PENDING: u32 = 0;
 pub const TS_PULLING: u32 = 1;
@@ -702,6 +766,8 @@ extern "C" {
     fn pm_group_directory(e: *mut c_void, q: *const pm_gdir_query, totals: *mut pm_gdir_totals, by_config: *mut u32, cap_cfgs: u32,
                           rows: *mut pm_gdir_row, cap_rows: u32, n_rows: *mut u32, members: *mut u32, cap_members: u32,
                           n_members: *mut u32) -> i32;
+    fn pm_task_directory(e: *mut c_void, q: *const pm_tdir_query, totals: *mut pm_tdir_totals, by_config: *mut u32, cap_cfgs: u32,
+                         rows: *mut pm_tdir_row, cap_rows: u32, n_rows: *mut u32) -> i32;
     fn pm_host_task_state(s: *const c_char) -> u32;
 }
 
@@ -932,6 +998,56 @@ pub struct GroupListing {
     pub total: u32,                // the whole filtered list's length, not the window's
     pub totals: pm_gdir_totals,
     pub groups: Vec<ListedNodeGroup>,
+}
+
+/// the filter of list_tasks (gpu_match_taskdir.cpp's TaskFilter): `TaskFilter::default()` lists every task
+#[derive(Debug, Clone, Copy)]
+pub struct TaskFilter {
+    pub config_mask: u64,          // u64::MAX: no filter; else bit c: tasks that allow the configuration of constructor index c
+    pub serve_mask: u32,
+    pub rollout_mask: u32,
+    pub workers_min: u32,
+    pub workers_max: u32,
+}
+
+impl Default for TaskFilter {
+    fn default() -> Self {
+        TaskFilter { config_mask: u64::MAX, serve_mask: (1 << TKS_N) - 1, rollout_mask: (1 << TKR_N) - 1, workers_min: 0,
+                     workers_max: u32::MAX }
+    }
+}
+
+/// a task of the task directory: the plugin's id and name, its classes, its assigned and reported columns
+#[derive(Debug, Clone)]
+pub struct ListedTask {
+    pub id: String,
+    pub name: String,
+    pub serve: u32,                // TKS_*
+    pub rollout: u32,              // TKR_*, TKR_NONE: rollout is off
+    pub row: pm_tdir_row,
+}
+
+/// one window of the task directory (gpu_match_taskdir.cpp's TaskListing)
+#[derive(Default, Debug, Clone)]
+pub struct TaskListing {
+    pub total: u32,                // the whole filtered list's length, not the window's
+    pub totals: pm_tdir_totals,
+    pub tasks: Vec<ListedTask>,
+}
+
+#[derive(Default, Debug, Clone)]
+pub struct TaskCounts {
+    pub totals: pm_tdir_totals,
+    pub by_config: std::collections::BTreeMap<String, u32>,   // configuration name -> tasks that allow it, present ones only
+}
+
+/// what sync_orchestrator_statistics sets (metrics/sync_service.rs:209-286); the gauges themselves stay the host's
+#[derive(Default, Debug, Clone)]
+pub struct OrchestratorStatistics {
+    pub nodes_by_status: std::collections::BTreeMap<String, u32>,   // lowercase status name -> nodes, present ones only
+    pub tasks_count: u32,
+    pub nodes_per_task: Vec<NodesPerTask>,                          // the tasks with reporters
+    pub groups_count: std::collections::BTreeMap<String, u32>,      // configuration name -> groups, present ones only
 }
 
 /// one window of the store's ordered listing (gpu_match_directory.cpp's NodeListing)
@@ -2794,6 +2910,89 @@ impl GpuMatchPlugin {
                                 order: GDIR_BY_ID_TEXT, offset: 0, limit: u32::MAX };
         let (_, rows, members) = self.group_directory_locked(&t, &tasks, &q, None)?;
         Ok(self.listed_groups_locked(&t, &tasks, &rows, &members))
+    }
+
+    // ---- task directory (gpu_match_taskdir.cpp, statement for statement): GET /tasks joined, filtered and paged over
+    // pm_task_directory, the counters, the tasks no standing group can run, the sync service's statistics.  LOCK ORDER: nodes,
+    // tasks, the engine.
+
+    /// one window, checked against the plugin's task list (the node and task locks are held).  The COUNTERS-ONLY query first
+    /// (limit 0: no sort, no row): its total sizes the buffer, and ONE call behind it makes the order and the window.
+    fn task_directory_locked(&self, tasks: &[Task], q: &pm_tdir_query, by_config: Option<&mut [u32; 64]>)
+                             -> Result<(pm_tdir_totals, Vec<pm_tdir_row>)> {
+        let (by_config, cap_cfgs) = by_config.map_or((std::ptr::null_mut(), 0u32), |c| (c.as_mut_ptr(), 64u32));
+        let mut totals = pm_tdir_totals::default();
+        let counters = pm_tdir_query { limit: 0, ..*q };
+        let mut have = 0u32;
+        check(unsafe { pm_task_directory(self.engine, &counters, &mut totals, by_config, cap_cfgs, std::ptr::null_mut(), 0, &mut have) })?;
+        have = if q.offset >= totals.total { 0 } else { q.limit.min(totals.total - q.offset) };
+        if have == 0 { return Ok((totals, Vec::new())); }
+        let mut rows = vec![pm_tdir_row::default(); have as usize];
+        let mut got = 0u32;
+        check(unsafe { pm_task_directory(self.engine, q, &mut totals, by_config, cap_cfgs, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;
+        if got as usize > rows.len() { return Err(anyhow!("task directory: the window grew between two calls")); }
+        rows.truncate(got as usize);
+        if rows.iter().any(|r| r.task as usize >= tasks.len()) {
+            return Err(anyhow!("task directory: the engine names a task the plugin has not"));
+        }
+        Ok((totals, rows))
+    }
+
+    fn listed_tasks_locked(&self, tasks: &[Task], rows: &[pm_tdir_row]) -> Vec<ListedTask> {
+        rows.iter().map(|r| {
+            let t = &tasks[r.task as usize];
+            ListedTask { id: t.id.to_string(), name: t.name.clone(), serve: r.serve as u32, rollout: r.rollout as u32, row: *r }
+        }).collect()
+    }
+
+    /// GET /tasks (api/routes/task.rs:20-39): the window [offset, offset + limit) of the filtered tasks in the chosen order
+    /// (TDIR_BY_LIST is the reference's, task_store.rs:57-82)
+    pub fn list_tasks(&self, filter: &TaskFilter, order: u32, offset: u32, limit: u32) -> Result<TaskListing> {
+        let _t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_tdir_query { config_mask: filter.config_mask, serve_mask: filter.serve_mask, rollout_mask: filter.rollout_mask,
+                                workers_min: filter.workers_min, workers_max: filter.workers_max, order, offset, limit, _pad: 0 };
+        let (totals, rows) = self.task_directory_locked(&tasks, &q, None)?;
+        Ok(TaskListing { total: totals.total, totals, tasks: self.listed_tasks_locked(&tasks, &rows) })
+    }
+
+    /// the task table's counters: one counters-only query
+    pub fn task_counts(&self) -> Result<TaskCounts> {
+        let _t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_tdir_query { config_mask: u64::MAX, serve_mask: (1 << TKS_N) - 1, rollout_mask: (1 << TKR_N) - 1, workers_min: 0,
+                                workers_max: u32::MAX, order: TDIR_BY_LIST, offset: 0, limit: 0, _pad: 0 };
+        let mut by_config = [0u32; 64];
+        let (totals, _) = self.task_directory_locked(&tasks, &q, Some(&mut by_config))?;
+        if totals.n_cfgs as usize > self.config_names.len() {
+            return Err(anyhow!("task directory: the engine counts a configuration the plugin has not"));
+        }
+        let mut out = TaskCounts { totals, ..Default::default() };
+        for c in 0..totals.n_cfgs as usize {
+            if by_config[c] != 0 { *out.by_config.entry(self.config_names[c].clone()).or_insert(0) += by_config[c]; }
+        }
+        Ok(out)
+    }
+
+    /// the tasks no standing group can run (serving class STARVED), in list order
+    pub fn starved_tasks(&self) -> Result<Vec<ListedTask>> {
+        let _t = self.nodes.read();
+        let tasks = self.tasks.read();
+        let q = pm_tdir_query { config_mask: u64::MAX, serve_mask: 1 << TKS_STARVED, rollout_mask: (1 << TKR_N) - 1, workers_min: 0,
+                                workers_max: u32::MAX, order: TDIR_BY_LIST, offset: 0, limit: u32::MAX, _pad: 0 };
+        let (_, rows) = self.task_directory_locked(&tasks, &q, None)?;
+        Ok(self.listed_tasks_locked(&tasks, &rows))
+    }
+
+    /// what sync_orchestrator_statistics sets: counters-only queries of the three directories and the rollout task table, one
+    /// after the other (each under the locks it needs: not one snapshot); needs enable_liveness and enable_rollout
+    pub fn orchestrator_statistics(&self) -> Result<OrchestratorStatistics> {
+        Ok(OrchestratorStatistics {
+            nodes_by_status: self.status_counts()?,
+            tasks_count: self.task_counts()?.totals.tasks,
+            nodes_per_task: self.nodes_per_task()?,
+            groups_count: self.group_counts()?,
+        })
     }
 
     /// the ledger's rows as stored (what the tests look at)

@@ -39,6 +39,10 @@
 #                            a first and a middle page in each order, the degraded filter, the full list — beside each what a host
 #                            does today (pm_get_groups + pm_liveness_get + pm_rollout_groups, the join, a sort of id texts)
 #                            -> r28_group_directory.txt (copy it to profiles/)
+#   taskdir[:<args>]         tools/taskdir_probe.py [T:W ...] [--bench DIR]: pm_task_directory at 100,000 tasks over 10,000 workers and
+#                            1,000,000 over 100,000 — the counters, a first and a middle page in each order, the starved filter, the
+#                            full list — beside each what a host does today (pm_task_report + pm_rollout_tasks whole, a hash-map
+#                            join on ids, classification, filter, sort) -> r29_task_directory.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -172,6 +176,9 @@ PY
     groupdir)
       timeout -k 10 400 python tools/groupdir_probe.py $arg --out "$out/r28_group_directory.txt" > "$out/${n}_groupdir.log" 2>&1; echo "groupdir rc=$?"
       tail -24 "$out/${n}_groupdir.log" ;;
+    taskdir)
+      timeout -k 10 500 python tools/taskdir_probe.py $arg --out "$out/r29_task_directory.txt" > "$out/${n}_taskdir.log" 2>&1; echo "taskdir rc=$?"
+      tail -40 "$out/${n}_taskdir.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
