@@ -51,7 +51,9 @@ extern "C" {
                             + pm_discovery_sync (discovery sync),
                             + pm_metrics_enable / _ingest / _totals / _rows (metrics ledger),
                             + pm_rollout_enable / _ingest / _get / _summary / _tasks / _groups / _workers, pm_host_task_state
-                            (rollout ledger): compatible additions, the version stays 3 */
+                            (rollout ledger), + pm_addresses_enable / _set / _rank / _text, pm_keccak256_many,
+                            pm_invite_digests, pm_host_keccak256, pm_host_eip55 (address book): compatible additions, the
+                            version stays 3 */
 
 enum {
   PM_OK = 0,
@@ -1294,6 +1296,41 @@ int32_t pm_dist_tick_end(pm_engine*, pm_stats* stats);
  * device-side fold across ranks; not available with a non-zero price column. */
 int32_t pm_match_per_task_device(pm_engine*, uint64_t* best_ptr, uint64_t* count_ptr, uint32_t* n_tasks);
 
+/* ---- address book (kernels in pm_keccak.inc, pm_addresses.inc) ------------------------------------------------------------
+ * GROUP_INDEX, NEXT_P2P_ADDRESS and a listed group's member order go by a node's place in a BTreeSet<String> of
+ * address.to_string() (node_groups/mod.rs:424-434, scheduler_impl.rs:115-128).  That string is alloy's `Address: Display`:
+ * the EIP-55 mixed-case text, whose case pattern is keccak-256 of the lower-case hex — in byte order '9' < 'B' < 'a', so it
+ * is neither the order of the 20 bytes nor that of the lower-case text.  With the book on the engine holds every row's
+ * 20 bytes, computes the texts and ranks them itself: a host sends the NEW rows' bytes (20 B each) and asks for the rank,
+ * instead of keeping every text sorted and replacing the whole column with pm_set_addr_ranks.  Off by default.
+ *
+ * Every call but pm_addresses_enable and pm_keccak256_many is PM_ESTATE while the book is off or before the workers are
+ * uploaded; every call is PM_ESTATE in the middle of a stepwise tick; a row >= W is PM_ERANGE; n == 0 is a no-op.
+ * pm_upload_workers(keep_groups = 0) forgets every address; keep_groups = 1 and pm_append_workers keep them, the new rows hold
+ * none until pm_addresses_set names them.
+ *
+ * pm_addresses_enable  on: an empty book (again: empties it); off frees it.
+ * pm_addresses_set     rows [first_row, first_row + n) <- addr20[20 n] (`Address` as bytes); a row may be written again.
+ * pm_addresses_rank    PM_ESTATE unless every row of [0, W) holds an address.  Ranks the EIP-55 texts as byte strings, equal
+ *                      texts by ascending row — a permutation of [0, W) — and installs it exactly as pm_set_addr_ranks would
+ *                      (which keeps working: the last writer wins).  rank_out: NULL or [W].
+ * pm_addresses_text    out[43 k ..) = "0x" + the 40 characters of row rows[k] (NULL: row k) + NUL — what
+ *                      address.to_string() prints.  A row without an address is PM_ESTATE.
+ * pm_keccak256_many    keccak-256 (alloy_primitives::keccak256: Keccak padding, not SHA-3's) of n messages packed in `bytes`,
+ *                      message i = [offsets[i], offsets[i + 1]); needs no book.  out[32 i ..) its digest.
+ * pm_invite_digests    NodeInviter::generate_invite (orchestrator/src/node/invite.rs:86-115) up to the signature: for row
+ *                      rows[k], digest = keccak(be32(domain_id) | be32(pool_id) | address | nonce[32 k ..) |
+ *                      be32(expiration_s[k])) with be32 = U256::to_be_bytes, and signing_hash = what sign_message hashes
+ *                      (EIP-191: keccak("\x19Ethereum Signed Message:\n32" | digest)).  Nonces, the clock and the ECDSA step
+ *                      stay with the caller. */
+int32_t pm_addresses_enable(pm_engine*, uint32_t on);
+int32_t pm_addresses_set(pm_engine*, uint32_t first_row, const uint8_t* addr20, uint32_t n);
+int32_t pm_addresses_rank(pm_engine*, uint32_t* rank_out);
+int32_t pm_addresses_text(pm_engine*, const uint32_t* rows, uint32_t n, char* out);
+int32_t pm_keccak256_many(pm_engine*, const uint8_t* bytes, const uint32_t* offsets, uint32_t n, uint8_t* out);
+int32_t pm_invite_digests(pm_engine*, uint32_t domain_id, uint32_t pool_id, const uint32_t* rows, uint32_t n,
+                          const uint8_t* nonce, const uint64_t* expiration_s, uint8_t* digest, uint8_t* signing_hash);
+
 /* ------------------------------------------------------------------ host helpers (no GPU needed)
  * ComputeRequirements::from_str (shared/src/models/node.rs:180-374).  Fills cfg->flags/cpu/ram/
  * storage/alt_count (alt_begin, min/max sizes untouched) and up to alt_cap alternatives; model
@@ -1347,6 +1384,11 @@ uint32_t pm_host_last_file_idx(const char* total_upload_count);
 /* TaskState::from(&str) (shared/src/models/task.rs:24-37): the eight names exactly as written there, anything else (another
  * case, surrounding blanks, NULL) is PM_TS_UNKNOWN. */
 uint32_t pm_host_task_state(const char* s);
+/* alloy_primitives::keccak256 on the host: out32 = keccak-256 (Keccak padding) of bytes[0, len). */
+int32_t pm_host_keccak256(const uint8_t* bytes, size_t len, uint8_t* out32);
+/* `Address: Display` (EIP-55): out43 = "0x", the 40 hex characters — letter i upper-case where nibble i of
+ * keccak-256(the lower-case characters) is >= 8 — and a NUL.  What the address book computes on the device. */
+int32_t pm_host_eip55(const uint8_t* addr20, char* out43);
 
 uint32_t pm_abi_version(void);
 

@@ -23,7 +23,9 @@ extern "C" {
  * tasks), t_dead (tombstones inside the range), regrowths and compactions of the index space since creation, entries
  * of the host group list, its tombstones (dissolved, not yet compacted), retired snapshot buffers.  out[97]: the last
  * carve's again — times the streaming carve dropped a configuration's outstanding tickets and issued them afresh
- * (debug_carve_counters: stream_refreshes).  Copies min(cap, 98) words. */
+ * (debug_carve_counters: stream_refreshes).  out[98], out[99]: the address book's pm_addresses_rank calls that ended on the
+ * one-word sort (no two rows share their first ten characters) and on the all-words sort, since creation (engine.py
+ * debug_address_sorts; off or on again does not reset them).  Copies min(cap, 100) words. */
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap);
 
 /* Timeline of the last streaming carve launch (PM_CARVE_PROF builds; otherwise *n = 0): up to cap events of two words

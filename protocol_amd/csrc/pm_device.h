@@ -254,6 +254,9 @@ struct MxRowsArgs {
 
 // rollout ledger (pm_rollout.inc).  A group slot is an index into the host's list as it stands (tombstones included); what the
 // reads report is RoGroup::slot, the slot pm_get_groups would number it.
+static constexpr uint32_t PM_AB_WORDS = 4;                 // address book: 64-bit words of a row's text key, 10 characters of 5 bits each
+static constexpr uint32_t PM_AB_PASSES = 7;                // ... radix passes of 8 bits over a word's 50
+static constexpr uint32_t PM_AB_TEXT = 43;                 // ... bytes of a rendered text: "0x", 40 characters, NUL
 static constexpr uint32_t PM_RO_CHUNK = 1024;             // keys of one radix chunk: fixed, so the sort does not depend on the grid
 static constexpr uint32_t PM_RO_GCNT = PM_TS_N + 2;       // a group's counters: same[PM_TS_N], other, silent
 static constexpr uint32_t PM_RO_CLAIM = 0x80000000u;      // a sorted key's side word: a group's claim (| list slot), else a reporter's state
@@ -690,6 +693,25 @@ void launch_tdir_window(const TdirArgs& a, hipStream_t s);
 void launch_tdir_keys(const TdirArgs& a, hipStream_t s);
 // rows[k] = the joined record of slot list[k], handles[k] its handle, k < n (uid is the host's: the ids never went up whole)
 void launch_tdir_emit(const TdirArgs& a, const uint32_t* list, uint32_t n, pm_tdir_row* rows, uint32_t* handles, hipStream_t s);
+// keccak-256 (pm_keccak.inc): message i is bytes[off[i], off[i + 1]), its digest the little-endian bytes of out[4 i, 4 i + 4)
+void launch_keccak_many(const uint8_t* bytes, const uint32_t* off, uint32_t n, uint64_t* out, hipStream_t s);
+// address book (pm_addresses.inc).  in: n addresses of five words; the rows first.. take bytes, case mask, text key and flag
+void launch_ab_set(const uint32_t* in, uint32_t first, uint32_t n, uint32_t* bytes, uint64_t* mask, uint64_t* key, uint8_t* set,
+                   hipStream_t s);
+// out[43 k ..) = the EIP-55 text of row rows[k] (null: row k)
+void launch_ab_text(const uint32_t* rows, uint32_t n, const uint32_t* bytes, const uint64_t* mask, uint8_t* out, hipStream_t s);
+void launch_ab_clear(uint8_t* set, uint32_t first, uint32_t end, hipStream_t s);
+// (word 0, row) of every row sorted into key / val [returned buffer]; *ties += neighbours that share word 0
+uint32_t launch_ab_sort_shallow(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
+                                uint32_t* hist_scan, uint32_t* ties, hipStream_t s);
+// the rows sorted by all PM_AB_WORDS words into val [returned buffer]
+uint32_t launch_ab_sort_deep(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
+                             uint32_t* hist_scan, hipStream_t s);
+// rank[val[i]] = i
+void launch_ab_rank(const uint32_t* val, uint32_t W, uint32_t* rank, hipStream_t s);
+// digest / signing [4 k, 4 k + 4): the invite digest of row rows[k] and its EIP-191 signing hash; nonce [4 n], expiration [n]
+void launch_invite_digests(const uint32_t* rows, uint32_t n, const uint32_t* bytes, uint32_t domain_id, uint32_t pool_id,
+                           const uint64_t* nonce, const uint64_t* expiration, uint64_t* digest, uint64_t* signing, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

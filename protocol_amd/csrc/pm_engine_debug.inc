@@ -1,5 +1,5 @@
 // pm_engine_debug.inc — part of pm_engine.cpp (one translation unit; included in place): C ABI: test and measuring hooks of include/pm_engine_debug.h (inside extern "C").
-// debug (include/pm_engine_debug.h): counters of the last carve and of the engine's incremental state; copies min(cap, 98) words
+// debug (include/pm_engine_debug.h): counters of the last carve and of the engine's incremental state; copies min(cap, 100) words
 int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap) {
   if (!e || !out) return set_error(PM_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(e->mu);
@@ -12,6 +12,8 @@ int32_t pm_debug_carve_prof(pm_engine* e, unsigned long long* out, uint32_t cap)
                                      e->groups.size(), e->n_dead_groups, e->pub_retired.size()};
   for (uint32_t k = 88; k < cap && k < 97; ++k) out[k] = inc[k - 88];
   if (cap > 97u) out[97] = e->carve_why[24];  // (the last carve's again: times the streaming carve dropped a configuration's tickets and issued them afresh)
+  if (cap > 98u) out[98] = e->ab.shallow;  // (the address book's ranks by sort path, since creation)
+  if (cap > 99u) out[99] = e->ab.deep;
   return PM_OK;
 }
 

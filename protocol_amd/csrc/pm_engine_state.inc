@@ -161,6 +161,26 @@ struct TaskDir {
   std::vector<uint32_t> h_handles;
 };
 
+// ---- address book (pm_engine_addresses.inc): the 20 bytes, the EIP-55 case mask, the text key and a "set" flag of the workers
+// [0, W); rows behind W hold nothing yet (the next book call clears their flags).  Everything else is scratch of one call.
+struct AddressBook {
+  bool on = false;
+  bool reinit = false;        // an upload dropped the row identities: every flag is cleared by the next book call
+  uint32_t W = 0, n_set = 0;  // rows covered; rows of them that hold an address
+  uint64_t shallow = 0, deep = 0;  // ranks that ended on the one-word / the all-words sort, since creation (pm_debug_carve_prof 98, 99)
+  DevBuf<uint32_t> bytes;     // [5 W]
+  DevBuf<uint64_t> mask;      // [W]
+  DevBuf<uint64_t> keys;      // [PM_AB_WORDS W]
+  DevBuf<uint8_t> set;        // [W]
+  std::vector<uint8_t> h_set; // (the flags' host mirror: what n_set counts)
+  DevBuf<uint32_t> stage;     // a call's inputs: addresses, rows, offsets
+  DevBuf<uint64_t> key[2];    // the sort's keys and rows, ping-pong
+  DevBuf<uint32_t> val[2], hist, hist_scan, ties;
+  DevBuf<uint8_t> text;       // rendered texts; pm_keccak256_many's messages
+  DevBuf<uint64_t> in64, out64;  // nonces and expirations; digests
+  PinBuf<uint32_t> h_pin;     // [0] the ties
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -399,4 +419,5 @@ struct pm_engine {
   Directory dir;  // (scratch only: never switched)
   GroupDir gdir;  // (the same)
   TaskDir tdir;   // (the same)
+  AddressBook ab;
 };

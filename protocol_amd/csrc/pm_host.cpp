@@ -485,6 +485,68 @@ int32_t pm_host_upload_name_vars(const char* in, const char* group_id, uint32_t 
   return give(s, out, cap, needed);
 }
 
+// keccak-256 (rate 136, padding 0x01 ... 0x80) with the state as an array and the steps as loops: written apart from the
+// device's unrolled permutation (pm_keccak.inc) on purpose, so that either checks the other
+static void keccak_f1600_host(uint64_t s[25]) {
+  static const unsigned rot[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};
+  uint64_t lfsr = 1;  // the round constants' bits: x^8 + x^6 + x^5 + x^4 + 1
+  for (int round = 0; round < 24; ++round) {
+    uint64_t c[5], b[25];
+    for (int x = 0; x < 5; ++x) c[x] = s[x] ^ s[x + 5] ^ s[x + 10] ^ s[x + 15] ^ s[x + 20];
+    for (int x = 0; x < 5; ++x) {
+      const uint64_t r = c[(x + 1) % 5], d = c[(x + 4) % 5] ^ ((r << 1) | (r >> 63));
+      for (int y = 0; y < 5; ++y) s[x + 5 * y] ^= d;
+    }
+    for (int x = 0; x < 5; ++x)
+      for (int y = 0; y < 5; ++y) {
+        const uint64_t v = s[x + 5 * y];
+        const unsigned r = rot[x + 5 * y];
+        b[y + 5 * ((2 * x + 3 * y) % 5)] = r ? (v << r) | (v >> (64 - r)) : v;
+      }
+    for (int y = 0; y < 5; ++y)
+      for (int x = 0; x < 5; ++x) s[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
+    for (int j = 0; j < 7; ++j) {
+      if (lfsr & 1) s[0] ^= 1ull << ((1u << j) - 1u);
+      lfsr = (lfsr << 1) ^ ((lfsr >> 7) ? 0x171ull : 0ull);
+    }
+  }
+}
+
+int32_t pm_host_keccak256(const uint8_t* bytes, size_t len, uint8_t* out32) {
+  if ((len && !bytes) || !out32) return pm::set_error(PM_EINVAL, "null argument");
+  uint64_t s[25] = {};
+  const size_t blocks = len / 136 + 1;
+  for (size_t blk = 0; blk < blocks; ++blk) {
+    uint8_t block[136] = {};
+    const size_t at = blk * 136, have = len > at ? std::min<size_t>(len - at, 136) : 0;
+    if (have) std::memcpy(block, bytes + at, have);
+    if (blk + 1 == blocks) block[have] ^= 0x01, block[135] ^= 0x80;
+    for (int i = 0; i < 17; ++i) {
+      uint64_t v = 0;
+      for (int j = 0; j < 8; ++j) v |= uint64_t(block[8 * i + j]) << (8 * j);
+      s[i] ^= v;
+    }
+    keccak_f1600_host(s);
+  }
+  for (int j = 0; j < 32; ++j) out32[j] = uint8_t(s[j / 8] >> (8 * (j % 8)));
+  return PM_OK;
+}
+
+int32_t pm_host_eip55(const uint8_t* addr20, char* out43) {
+  if (!addr20 || !out43) return pm::set_error(PM_EINVAL, "null argument");
+  static const char hex[] = "0123456789abcdef";
+  uint8_t text[40], digest[32];
+  for (int i = 0; i < 20; ++i) text[2 * i] = uint8_t(hex[addr20[i] >> 4]), text[2 * i + 1] = uint8_t(hex[addr20[i] & 15]);
+  pm_host_keccak256(text, 40, digest);
+  out43[0] = '0', out43[1] = 'x';
+  for (int i = 0; i < 40; ++i) {
+    const unsigned nib = (i & 1) ? digest[i / 2] & 15u : digest[i / 2] >> 4;
+    out43[2 + i] = char(text[i] >= 'a' && nib >= 8 ? text[i] - 32 : text[i]);
+  }
+  out43[42] = 0;
+  return PM_OK;
+}
+
 uint32_t pm_abi_version(void) { return PM_ABI_VERSION; }
 
 }  // extern "C"

@@ -237,7 +237,10 @@ EXPORTS = [
     "pm_directory",
     "pm_group_directory",
     "pm_task_directory",
+    "pm_addresses_enable", "pm_addresses_set", "pm_addresses_rank", "pm_addresses_text", "pm_invite_digests",
 ]
+# ... and the declared names that carry a digit, which the header check's name pattern (letters and '_') does not take in
+EXPORTS_NUMBERED = ["pm_keccak256_many", "pm_host_keccak256", "pm_host_eip55"]
 
 _lib = None
 
@@ -349,7 +352,17 @@ def lib() -> C.CDLL:
         L.pm_host_last_file_idx.restype = u32
         L.pm_host_task_state.argtypes = [C.c_char_p]
         L.pm_host_task_state.restype = u32
-        for name in EXPORTS:
+        L.pm_addresses_enable.argtypes = [vp, u32]
+        L.pm_addresses_set.argtypes = [vp, u32, vp, u32]
+        L.pm_addresses_rank.argtypes = [vp, vp]
+        L.pm_addresses_text.argtypes = [vp, vp, u32, vp]
+        L.pm_invite_digests.argtypes = [vp, u32, u32, vp, u32, vp, vp, vp, vp]
+        # (bound where the library has them: a test library that stubs EXPORTS alone lacks them, and a call then fails by name)
+        numbered = {"pm_keccak256_many": [vp, vp, vp, u32, vp], "pm_host_keccak256": [vp, sz, vp], "pm_host_eip55": [vp, vp]}
+        for name in EXPORTS_NUMBERED:
+            if hasattr(L, name):
+                getattr(L, name).argtypes = numbered[name]
+        for name in EXPORTS + [n for n in EXPORTS_NUMBERED if hasattr(L, n)]:
             fn = getattr(L, name)
             if name not in ("pm_last_error", "pm_abi_version", "pm_engine_destroy", "pm_engine_config_default",
                             "pm_host_last_file_idx", "pm_host_task_state"):
@@ -366,6 +379,32 @@ def check(rc: int) -> int:
 
 def _arr(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _addr_bytes(addr20) -> np.ndarray:
+    """addresses as uint8 [n, 20]: an array of that shape, or a sequence of 20-byte strings"""
+    if isinstance(addr20, np.ndarray):
+        a = _arr(addr20, np.uint8)
+    else:
+        a = np.frombuffer(b"".join(bytes(x) for x in addr20), dtype=np.uint8)
+    return a.reshape(-1, 20)
+
+
+def host_keccak256(data: bytes) -> bytes:
+    """pm_host_keccak256"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    out = np.zeros(32, dtype=np.uint8)
+    check(lib().pm_host_keccak256(buf.ctypes.data if len(buf) else None, len(buf), out.ctypes.data))
+    return out.tobytes()
+
+
+def host_eip55(addr20: bytes) -> str:
+    """pm_host_eip55: the EIP-55 text of 20 bytes"""
+    buf = np.frombuffer(bytes(addr20), dtype=np.uint8)
+    assert len(buf) == 20
+    out = np.zeros(43, dtype=np.uint8)
+    check(lib().pm_host_eip55(buf.ctypes.data, out.ctypes.data))
+    return out[:42].tobytes().decode("ascii")
 
 
 TICK_MANY_THREADS = 1
@@ -1080,6 +1119,64 @@ class Engine:
         out = (C.c_uint64 * 3)()
         L.pm_debug_live_allocations(out)
         return tuple(int(v) for v in out)
+
+    # ---- address book (include/pm_engine.h "address book")
+    def enable_addresses(self, on: bool = True):
+        """pm_addresses_enable: on = an empty book over the rows [0, W) (again: empties it); off frees it"""
+        check(lib().pm_addresses_enable(self._h, int(on)))
+
+    def set_addresses(self, first_row: int, addr20):
+        """pm_addresses_set: rows [first_row, first_row + n) <- addr20 (uint8 [n, 20], or n 20-byte strings)"""
+        a = _addr_bytes(addr20)
+        check(lib().pm_addresses_set(self._h, first_row, a.ctypes.data if len(a) else None, len(a)))
+
+    def rank_addresses(self, want: bool = True):
+        """pm_addresses_rank: ranks the EIP-55 texts and installs them as set_addr_ranks would -> the ranks (uint32 [W]) or None"""
+        out = np.zeros(self.W, dtype=np.uint32) if want else None
+        check(lib().pm_addresses_rank(self._h, out.ctypes.data if want and self.W else None))
+        return out
+
+    def address_texts(self, rows=None, n: int | None = None) -> list:
+        """pm_addresses_text -> the EIP-55 texts ("0x" + 40 characters) of the rows (None: the rows [0, n), n None: every row)"""
+        if rows is None:
+            n, ptr = (self.W if n is None else n), None
+        else:
+            rows = _arr(rows, np.uint32)
+            n, ptr = len(rows), (rows.ctypes.data if len(rows) else None)
+        out = np.zeros((max(n, 1), 43), dtype=np.uint8)
+        check(lib().pm_addresses_text(self._h, ptr, n, out.ctypes.data))
+        return [bytes(r[:42]).decode("ascii") for r in out[:n]]
+
+    def keccak256_many(self, messages) -> np.ndarray:
+        """pm_keccak256_many: keccak-256 of every message (bytes-like) -> uint8 [n, 32]"""
+        msgs = [bytes(m) for m in messages]
+        off = np.zeros(len(msgs) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(msgs), dtype=np.uint8)
+        out = np.zeros((max(len(msgs), 1), 32), dtype=np.uint8)
+        check(lib().pm_keccak256_many(self._h, buf.ctypes.data if len(buf) else None, off.ctypes.data, len(msgs), out.ctypes.data))
+        return out[:len(msgs)]
+
+    def invite_digests(self, domain_id: int, pool_id: int, rows, nonces, expirations):
+        """pm_invite_digests: rows [n], nonces uint8 [n, 32], expirations (seconds) [n] -> (digest, signing hash), uint8 [n, 32] each"""
+        rows = _arr(rows, np.uint32)
+        n = len(rows)
+        nonces = _arr(nonces, np.uint8).reshape(n, 32)
+        exp = _arr(expirations, np.uint64)
+        assert len(exp) == n
+        d, s = np.zeros((max(n, 1), 32), dtype=np.uint8), np.zeros((max(n, 1), 32), dtype=np.uint8)
+        check(lib().pm_invite_digests(self._h, domain_id, pool_id, rows.ctypes.data if n else None, n,
+                                      nonces.ctypes.data if n else None, exp.ctypes.data if n else None, d.ctypes.data, s.ctypes.data))
+        return d[:n], s[:n]
+
+    def debug_address_sorts(self) -> dict:
+        """ranks the address book ended on its one-word / all-words sort since creation (pm_debug_carve_prof words 98, 99)"""
+        L = lib()
+        L.pm_debug_carve_prof.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_uint32]
+        L.pm_debug_carve_prof.restype = C.c_int32
+        out = (C.c_ulonglong * 100)()
+        check(L.pm_debug_carve_prof(self._h, out, 100))
+        return {"shallow": int(out[98]), "deep": int(out[99])}
 
     def debug_task_space(self) -> dict:
         """the task index space, the group list and the snapshot buffers (include/pm_engine_debug.h: pm_debug_carve_prof

@@ -294,11 +294,56 @@ std::vector<uint32_t> GpuMatchPlugin::address_ranks(const std::vector<uint32_t>&
   return rank;
 }
 
+// "0x" or nothing, then exactly 40 hex digits of either case (`Address::from_str`; the case is not held to the checksum)
+bool GpuMatchPlugin::parse_address_text(const std::string& text, uint8_t out20[20]) {
+  const size_t at = text.compare(0, 2, "0x") == 0 ? 2 : 0;
+  if (text.size() != at + 40) return false;
+  for (size_t i = 0; i < 40; ++i) {
+    const char c = text[at + i];
+    const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+    if (v < 0) return false;
+    out20[i / 2] = uint8_t((i & 1) ? (out20[i / 2] | v) : (v << 4));
+  }
+  return true;
+}
+
+bool GpuMatchPlugin::address_book_enabled() const {
+  std::shared_lock<std::shared_mutex> lk(nodes_mu_);
+  return book_.on;
+}
+
+std::vector<std::array<uint8_t, 20>> GpuMatchPlugin::book_parse_new_locked(const std::vector<OrchestratorNode>& snapshot) const {
+  std::vector<std::array<uint8_t, 20>> out;
+  std::unordered_map<std::string, const std::string*> fresh;  // bytes -> the text that brought them, of this snapshot's new nodes
+  for (const OrchestratorNode& node : snapshot) {
+    const std::string& text = node.address.to_string();
+    if (nodes_.index.count(node.address)) continue;
+    std::array<uint8_t, 20> b{};
+    if (!parse_address_text(text, b.data())) throw EngineError(PM_EINVAL, "not an address: '" + text + "'");
+    const std::string key(reinterpret_cast<const char*>(b.data()), b.size());
+    const auto it = fresh.find(key);
+    if (it != fresh.end() && *it->second == text) continue;  // (the same text twice in one snapshot: one row)
+    if (it != fresh.end() || book_.by_bytes.count(key))
+      throw EngineError(PM_EINVAL, "an address that has a row under another spelling: '" + text + "'");
+    fresh.emplace(key, &text);
+    out.push_back(b);
+  }
+  return out;
+}
+
+void GpuMatchPlugin::book_admit_locked(uint32_t row, const std::array<uint8_t, 20>& bytes) {
+  book_.bytes.insert(book_.bytes.end(), bytes.begin(), bytes.end());
+  book_.by_bytes.emplace(std::string(reinterpret_cast<const char*>(bytes.data()), bytes.size()), row);
+}
+
 void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
   {
     std::unique_lock<std::shared_mutex> lk(nodes_mu_);
     NodeTable& t = nodes_;
     bool new_model = false;
+    const bool book = book_.on;
+    const std::vector<std::array<uint8_t, 20>> new_bytes = book ? book_parse_new_locked(snapshot) : std::vector<std::array<uint8_t, 20>>();
+    size_t next_new = 0;
     std::vector<bool> seen(t.rows.size(), false);
     RowColumns appended, updated;
     std::vector<uint32_t> upd_idx;
@@ -325,10 +370,14 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
         t.p2p_ids.push_back(node.p2p_id.value_or(std::string()));
         t.rows.push_back(row);
         t.present.push_back(true);
-        const std::string& key = t.address_strings[i];
-        const auto at = std::partition_point(t.by_address.begin(), t.by_address.end(),
-                                             [&](uint32_t j) { return t.address_strings[j] < key; });
-        t.by_address.insert(at, i);
+        if (book) {  // (no sorted list: the engine ranks the texts it computes; book_sync fetches this row's)
+          book_admit_locked(i, new_bytes.at(next_new++));
+        } else {
+          const std::string& key = t.address_strings[i];
+          const auto at = std::partition_point(t.by_address.begin(), t.by_address.end(),
+                                               [&](uint32_t j) { return t.address_strings[j] < key; });
+          t.by_address.insert(at, i);
+        }
         appended.push(row, i);
       }
     }
@@ -343,7 +392,9 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
       // row that is not in the store, as dead — a no-op for a row in no group, the reference's dissolution (and its
       // send_group_destroyed) for the others.
       RowColumns all;
-      const std::vector<uint32_t> ranks = address_ranks(t.by_address, t.rows.size());
+      // (book on: the ranks the engine gave last, a new row's own index behind them — all replaced by book_sync right below)
+      std::vector<uint32_t> ranks = book ? book_.ranks : address_ranks(t.by_address, t.rows.size());
+      for (size_t i = ranks.size(); i < t.rows.size(); ++i) ranks.push_back(uint32_t(i));
       for (size_t i = 0; i < seen.size(); ++i)
         if (!seen[i]) t.present[i] = false;
       std::vector<uint32_t> gone, gone_flags;
@@ -358,6 +409,7 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
       push_model_table(t);
       const pm_worker_soa w = all.soa();
       check(pm_upload_workers(engine_, &w, 1));
+      if (book) book_sync_(*this, 0u, true);  // (every row's bytes again: the engine may have missed any of them)
       if (!gone.empty()) {
         const std::vector<uint32_t> dead(gone.size(), 1u);
         check(pm_on_worker_status_many(engine_, gone.data(), gone_flags.data(), dead.data(), uint32_t(gone.size())));
@@ -386,8 +438,9 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
     if (!upd_idx.empty()) {
       // keep the ranks the engine already has for rewritten rows (ranks among the rows it knows: the new ones of
       // this snapshot are sent behind this call)
-      const std::vector<uint32_t> ranks = address_ranks(t.by_address, seen.size());
-      for (size_t k = 0; k < upd_idx.size(); ++k) updated.addr_rank[k] = ranks[upd_idx[k]];
+      // (book on: the ranks pm_addresses_rank gave last are the ones the engine has)
+      const std::vector<uint32_t> ranks = book ? book_.ranks : address_ranks(t.by_address, seen.size());
+      for (size_t k = 0; k < upd_idx.size(); ++k) updated.addr_rank[k] = upd_idx[k] < ranks.size() ? ranks[upd_idx[k]] : upd_idx[k];
       const pm_worker_soa w = updated.soa();
       check(pm_update_workers(engine_, upd_idx.data(), &w));
     }
@@ -409,9 +462,13 @@ void GpuMatchPlugin::sync_nodes(const std::vector<OrchestratorNode>& snapshot) {
       const pm_worker_soa w = appended.soa();
       check(pm_append_workers(engine_, &w, &first));
       if (first != seen.size()) throw EngineError(PM_ESTATE, "the engine's worker table and the plugin's row map disagree");
-      // a new address shifts the global ranks of the others: GROUP_INDEX only needs the relative order
-      const std::vector<uint32_t> ranks = address_ranks(t.by_address, t.rows.size());
-      check(pm_set_addr_ranks(engine_, ranks.data(), uint32_t(ranks.size())));
+      if (book) {
+        book_sync_(*this, first, false);  // the new rows' bytes, pm_addresses_rank, the new rows' texts
+      } else {
+        // a new address shifts the global ranks of the others: GROUP_INDEX only needs the relative order
+        const std::vector<uint32_t> ranks = address_ranks(t.by_address, t.rows.size());
+        check(pm_set_addr_ranks(engine_, ranks.data(), uint32_t(ranks.size())));
+      }
     }
     engine_rows_stale_ = false;
     nodes_synced_.store(true);
@@ -714,6 +771,12 @@ NodeGroup GpuMatchPlugin::make_group(const NodeTable& t, const pm_group& g, cons
 
 // the reference keys node_to_group by address TEXT: exact string match (binary search in the address-ordered row list)
 std::optional<uint32_t> GpuMatchPlugin::row_of_address_text(const NodeTable& t, const std::string& text) const {
+  if (book_.on) {  // by the bytes: any spelling of the address finds the row
+    uint8_t b[20];
+    if (!parse_address_text(text, b)) return std::nullopt;
+    const auto it = book_.by_bytes.find(std::string(reinterpret_cast<const char*>(b), sizeof(b)));
+    return it == book_.by_bytes.end() ? std::nullopt : std::optional<uint32_t>(it->second);
+  }
   const auto at = std::partition_point(t.by_address.begin(), t.by_address.end(), [&](uint32_t j) { return t.address_strings[j] < text; });
   if (at == t.by_address.end() || t.address_strings[*at] != text) return std::nullopt;
   return *at;
@@ -797,7 +860,12 @@ std::unordered_map<std::string, std::optional<NodeGroup>> GpuMatchPlugin::get_no
 }
 
 size_t GpuMatchPlugin::get_idx_in_group(const NodeGroup& node_group, const std::string& node_addr) const {
-  const auto it = std::find(node_group.nodes.begin(), node_group.nodes.end(), node_addr);
+  auto it = std::find(node_group.nodes.begin(), node_group.nodes.end(), node_addr);
+  if (it == node_group.nodes.end()) {  // (book on: the group lists the device's texts; another spelling of a member's address is that member)
+    std::shared_lock<std::shared_mutex> lk(nodes_mu_);
+    const std::optional<uint32_t> row = book_.on ? row_of_address_text(nodes_, node_addr) : std::nullopt;
+    if (row) it = std::find(node_group.nodes.begin(), node_group.nodes.end(), nodes_.address_strings[*row]);
+  }
   if (it == node_group.nodes.end()) throw std::out_of_range("Node " + node_addr + " not found in group");
   return size_t(it - node_group.nodes.begin());
 }

@@ -611,6 +611,25 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // needs: not one snapshot); needs enable_liveness and enable_rollout
   OrchestratorStatistics orchestrator_statistics();
 
+  // ---- address book (INTEGRATION.md "Address book"; gpu_match_addresses.cpp): pm_addresses_* / pm_invite_digests.  Off by
+  // default: the texts the callers passed are ranked on the host and rendered as they came.  With the book on, sync_nodes
+  // parses each NEW node's address text to its 20 bytes (an optional "0x", 40 hex digits of either case; anything else, or a
+  // second spelling of an address that has a row, is EngineError(PM_EINVAL) naming the text, before anything changed), sends
+  // only the new rows' bytes and calls pm_addresses_rank where it kept `by_address` sorted and replaced the whole rank column;
+  // every address text the read surface renders is the device's EIP-55 text (`Address: Display`), fetched once per new row.
+  // Texts passed IN are looked up by their bytes, so any spelling finds the node.
+  void enable_address_book();  // with rows already known: parses and sends them all, ranks, fetches their texts
+  bool address_book_enabled() const;
+  static bool parse_address_text(const std::string& text, uint8_t out20[20]);
+  // NodeInviter::generate_invite up to the signature (node/invite.rs:86-115), for the nodes uninvited_nodes() lists, in its order:
+  // `nonce` is asked once per node (rand::random there), expiration_s is the caller's clock; the ECDSA step stays with the wallet
+  struct InviteDigest {
+    std::string address;
+    std::array<uint8_t, 32> nonce{}, digest{}, signing_hash{};
+  };
+  std::vector<InviteDigest> invite_digests(uint32_t domain_id, uint32_t pool_id, const std::function<std::array<uint8_t, 32>()>& nonce,
+                                           uint64_t expiration_s) const;
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -693,6 +712,22 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // against an engine without the liveness exports): handle_status_change's write to the ledger
   void (*liveness_note_)(const GpuMatchPlugin&, uint32_t row, NodeStatus status) = nullptr;
   static void liveness_note(const GpuMatchPlugin& self, uint32_t row, NodeStatus status);
+  // address book (gpu_match_addresses.cpp; under the node lock): the rows' 20 bytes, bytes -> row, and how many rows render the
+  // device's text.  book_sync_ is set by enable_address_book to book_sync (a pointer, as liveness_note_ is): sync_nodes' engine
+  // calls — the bytes of the rows [first, end) or of every row, the rank, the texts of the rows that have none yet
+  struct AddressBookState {
+    bool on = false;
+    std::vector<uint8_t> bytes;                         // 20 a row
+    std::unordered_map<std::string, uint32_t> by_bytes; // (the 20 bytes as a string)
+    size_t texts = 0;                                   // address_strings[0, texts) are the device's
+    std::vector<uint32_t> ranks;                        // what pm_addresses_rank gave last
+  };
+  AddressBookState book_;
+  void (*book_sync_)(GpuMatchPlugin&, uint32_t first, bool all) = nullptr;
+  static void book_sync(GpuMatchPlugin& self, uint32_t first, bool all);
+  // the new addresses of a snapshot, parsed (EngineError(PM_EINVAL) before anything changed); in the snapshot's order
+  std::vector<std::array<uint8_t, 20>> book_parse_new_locked(const std::vector<OrchestratorNode>& snapshot) const;
+  void book_admit_locked(uint32_t row, const std::array<uint8_t, 20>& bytes);
   // discovery sync (exclusive node lock): the endpoint column by row (ip empty = unknown: PM_EP_NONE), the interning map, the
   // endpoints of addresses without a row yet; last_status_change per row in ms, 0 = None.  Both grow lazily to the rows.
   struct EndpointColumn {

@@ -244,6 +244,15 @@ int32_t pmx_task_counts(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_starved_tasks(pmx_plugin*, char* out, size_t cap, size_t* needed);
 int32_t pmx_orchestrator_statistics(pmx_plugin*, char* out, size_t cap, size_t* needed);
 
+/* ---- address book (pm_plugin_addresses_c.cpp): GpuMatchPlugin::enable_address_book / invite_digests.  With the book on every
+ * address text of this face is the EIP-55 text the device computed, and an address passed in is found under any spelling.  The
+ * text of pmx_invite_digests (needs pmx_enable_liveness: the nodes are pmx_uninvited_nodes', in its order): "<address>\t<nonce>\t
+ * <digest>\t<signing hash>" per node, 64 lower-case hex digits each; this face draws the nonces itself — a test driver's
+ * plumbing: splitmix64 from nonce_seed, four little-endian words a nonce — where the C++ method takes the caller's source. */
+int32_t pmx_enable_address_book(pmx_plugin*);
+int32_t pmx_invite_digests(pmx_plugin*, uint32_t domain_id, uint32_t pool_id, uint64_t nonce_seed, uint64_t expiration_s, char* out,
+                           size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

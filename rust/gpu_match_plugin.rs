@@ -769,6 +769,16 @@ extern "C" {
     fn pm_task_directory(e: *mut c_void, q: *const pm_tdir_query, totals: *mut pm_tdir_totals, by_config: *mut u32, cap_cfgs: u32,
                          rows: *mut pm_tdir_row, cap_rows: u32, n_rows: *mut u32) -> i32;
     fn pm_host_task_state(s: *const c_char) -> u32;
+    // address book (include/pm_engine.h "address book")
+    fn pm_addresses_enable(e: *mut c_void, on: u32) -> i32;
+    fn pm_addresses_set(e: *mut c_void, first_row: u32, addr20: *const u8, n: u32) -> i32;
+    fn pm_addresses_rank(e: *mut c_void, rank_out: *mut u32) -> i32;
+    fn pm_addresses_text(e: *mut c_void, rows: *const u32, n: u32, out: *mut c_char) -> i32;
+    fn pm_keccak256_many(e: *mut c_void, bytes: *const u8, offsets: *const u32, n: u32, out: *mut u8) -> i32;
+    fn pm_invite_digests(e: *mut c_void, domain_id: u32, pool_id: u32, rows: *const u32, n: u32, nonce: *const u8,
+                         expiration_s: *const u64, digest: *mut u8, signing_hash: *mut u8) -> i32;
+    fn pm_host_keccak256(bytes: *const u8, len: usize, out32: *mut u8) -> i32;
+    fn pm_host_eip55(addr20: *const u8, out43: *mut c_char) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -881,6 +891,13 @@ struct NodeTable {
     by_address: Vec<u32>,           // rows in address-string order (kept sorted: a new node is one binary search)
     spec_models: Vec<String>,       // interned gpu.model strings; the index is gpu_model_class
     spec_model_index: HashMap<String, u32>,
+    /// address book (enable_address_book): the rows' 20 bytes, bytes -> row, how many rows render the device's text, and the
+    /// ranks pm_addresses_rank gave last (a rewritten row is sent with the rank it has).  by_address is not kept then.
+    book_on: bool,
+    book_bytes: Vec<u8>,
+    book_by_bytes: HashMap<[u8; 20], u32>,
+    book_texts: usize,
+    book_ranks: Vec<u32>,
     /// an engine call of sync_nodes failed half-way: the row map above is ahead of the engine's worker table (tombstones
     /// recorded here and never sent, rows appended here the engine does not have) — the next interval re-sends every row
     engine_rows_stale: bool,
@@ -1399,9 +1416,15 @@ impl GpuMatchPlugin {
                     t.p2p_ids.push(node.p2p_id.clone().unwrap_or_default());
                     t.rows.push(row.clone());
                     t.present.push(true);
-                    let key = &t.address_strings[i as usize];
-                    let at = t.by_address.partition_point(|&j| t.address_strings[j as usize] < *key);
-                    t.by_address.insert(at, i);
+                    if t.book_on {  // (no sorted list: the engine ranks the texts it computes; book_sync fetches this row's)
+                        let bytes: [u8; 20] = node.address.into_array();  // (an Address IS its bytes: nothing to parse on this side)
+                        t.book_bytes.extend_from_slice(&bytes);
+                        t.book_by_bytes.insert(bytes, i);
+                    } else {
+                        let key = &t.address_strings[i as usize];
+                        let at = t.by_address.partition_point(|&j| t.address_strings[j as usize] < *key);
+                        t.by_address.insert(at, i);
+                    }
                     appended.push(&row, i);
                 }
             }
@@ -1416,7 +1439,9 @@ impl GpuMatchPlugin {
             // (rows never move, so a group's row indices are as valid as before).  Then the deaths the engine may have
             // missed: every row that is not in the store, as dead — a no-op for a row in no group, the reference's
             // dissolution (and its send_group_destroyed) for the others.
-            let ranks = Self::address_ranks(&t.by_address, t.rows.len());
+            // (book on: the ranks the engine gave last, a new row's own index behind them — all replaced by book_sync right below)
+            let mut ranks = if t.book_on { t.book_ranks.clone() } else { Self::address_ranks(&t.by_address, t.rows.len()) };
+            for i in ranks.len()..t.rows.len() { ranks.push(i as u32); }
             for i in 0..seen.len() { if !seen[i] { t.present[i] = false; } }
             let mut all = RowColumns::default();
             let (mut gone, mut gone_flags) = (Vec::<u32>::new(), Vec::<u32>::new());
@@ -1431,6 +1456,7 @@ impl GpuMatchPlugin {
             }
             self.push_model_table(&t);
             check(unsafe { pm_upload_workers(self.engine, &all.soa(), 1) })?;
+            if t.book_on { self.book_sync(&mut t, 0, true)?; }  // (every row's bytes again: the engine may have missed any of them)
             if !gone.is_empty() {
                 let dead = vec![1u32; gone.len()];
                 check(unsafe { pm_on_worker_status_many(self.engine, gone.as_ptr(), gone_flags.as_ptr(), dead.as_ptr(), gone.len() as u32) })?;
@@ -1459,8 +1485,9 @@ impl GpuMatchPlugin {
         if !upd_idx.is_empty() {
             // keep the ranks the engine already has for rewritten rows (ranks among the rows it knows: the new
             // ones of this snapshot are sent behind this call)
-            let ranks = Self::address_ranks(&t.by_address, seen.len());
-            for (k, &i) in upd_idx.iter().enumerate() { updated.addr_rank[k] = ranks[i as usize]; }
+            // (book on: the ranks pm_addresses_rank gave last are the ones the engine has)
+            let ranks = if t.book_on { t.book_ranks.clone() } else { Self::address_ranks(&t.by_address, seen.len()) };
+            for (k, &i) in upd_idx.iter().enumerate() { updated.addr_rank[k] = ranks.get(i as usize).copied().unwrap_or(i); }
             check(unsafe { pm_update_workers(self.engine, upd_idx.as_ptr(), &updated.soa()) })?;
         }
         if !appended.flags.is_empty() {
@@ -1476,14 +1503,99 @@ impl GpuMatchPlugin {
             if first as usize != seen.len() {
                 return Err(anyhow!("pm_engine error {PM_ESTATE}: the engine's worker table and the plugin's row map disagree"));
             }
-            // a new address shifts the global ranks of the others: GROUP_INDEX only needs the relative order
-            let ranks = Self::address_ranks(&t.by_address, t.rows.len());
-            check(unsafe { pm_set_addr_ranks(self.engine, ranks.as_ptr(), ranks.len() as u32) })?;
+            if t.book_on {
+                self.book_sync(&mut t, first, false)?;  // the new rows' bytes, pm_addresses_rank, the new rows' texts
+            } else {
+                // a new address shifts the global ranks of the others: GROUP_INDEX only needs the relative order
+                let ranks = Self::address_ranks(&t.by_address, t.rows.len());
+                check(unsafe { pm_set_addr_ranks(self.engine, ranks.as_ptr(), ranks.len() as u32) })?;
+            }
         }
         t.engine_rows_stale = false;
         self.nodes_synced.store(true, Ordering::Release);
         drop(t);
         self.emit_group_webhooks()      // tombstoned nodes dissolved their groups
+    }
+
+    // ---- address book (gpu_match_addresses.cpp, statement for statement; INTEGRATION.md "Address book")
+
+    /// (the node write lock is held.)  The bytes of the rows [first, end) — or of every row — go up, the engine ranks its texts,
+    /// and the rows that render no device text yet get theirs: 43 bytes a new row come back, once.  (alloy's Display gives the
+    /// same text; taking the device's keeps one source for what is ranked and what is shown, as the C++ twin must.)
+    fn book_sync(&self, t: &mut NodeTable, first: u32, all: bool) -> Result<()> {
+        let w = t.rows.len() as u32;
+        if t.book_bytes.len() != 20 * w as usize {
+            return Err(anyhow!("pm_engine error {PM_ESTATE}: the address book and the plugin's row map disagree"));
+        }
+        let from = if all { 0 } else { first };
+        if from < w {
+            check(unsafe { pm_addresses_set(self.engine, from, t.book_bytes.as_ptr().add(20 * from as usize), w - from) })?;
+        }
+        if w == 0 { return Ok(()); }
+        t.book_ranks.resize(w as usize, 0);
+        check(unsafe { pm_addresses_rank(self.engine, t.book_ranks.as_mut_ptr()) })?;  // (kept: a rewritten row is sent with the rank it has)
+        if t.book_texts < w as usize {
+            let rows: Vec<u32> = (t.book_texts as u32..w).collect();
+            let mut text = vec![0 as c_char; 43 * rows.len()];
+            check(unsafe { pm_addresses_text(self.engine, rows.as_ptr(), rows.len() as u32, text.as_mut_ptr()) })?;
+            for (k, &row) in rows.iter().enumerate() {
+                let bytes: Vec<u8> = text[43 * k..43 * k + 42].iter().map(|&c| c as u8).collect();
+                t.address_strings[row as usize] = String::from_utf8_lossy(&bytes).into_owned();
+            }
+            t.book_texts = w as usize;
+        }
+        Ok(())
+    }
+
+    /// Off by default.  With the book on sync_nodes sends only the new rows' bytes and calls pm_addresses_rank where it kept
+    /// `by_address` sorted and replaced the whole rank column; with rows already known: sends them all, ranks, fetches their texts.
+    pub fn enable_address_book(&self) -> Result<()> {
+        let mut t = self.nodes.write();
+        if t.book_on { return Ok(()); }
+        let (mut bytes, mut by_bytes) = (Vec::<u8>::new(), HashMap::<[u8; 20], u32>::new());
+        for (i, a) in t.addresses.iter().enumerate() {
+            let b: [u8; 20] = a.into_array();
+            bytes.extend_from_slice(&b);
+            by_bytes.insert(b, i as u32);
+        }
+        check(unsafe { pm_addresses_enable(self.engine, 1) })?;
+        t.book_on = true;
+        t.book_bytes = bytes;
+        t.book_by_bytes = by_bytes;
+        t.book_texts = 0;
+        t.book_ranks.clear();
+        t.by_address.clear();  // (not kept any more: row_of_address_text goes by the bytes)
+        if !t.rows.is_empty() && self.nodes_synced.load(Ordering::Acquire) && !t.engine_rows_stale { self.book_sync(&mut t, 0, true)?; }
+        Ok(())
+    }
+
+    pub fn address_book_enabled(&self) -> bool { self.nodes.read().book_on }
+
+    /// NodeInviter::generate_invite up to the signature (node/invite.rs:86-115), for the nodes uninvited_nodes() lists, in its
+    /// order: (address text, nonce, digest, signing hash).  `nonce` is asked once per node (rand::random there), expiration_s
+    /// is the caller's clock; wallet.signer.sign_hash(signing hash) is the step that stays with the wallet.
+    pub fn invite_digests(&self, domain_id: u32, pool_id: u32, mut nonce: impl FnMut() -> [u8; 32], expiration_s: u64)
+                          -> Result<Vec<(String, [u8; 32], [u8; 32], [u8; 32])>> {
+        let t = self.nodes.read();
+        if !t.book_on { return Err(anyhow!("pm_engine error {PM_ESTATE}: the address book is off (enable_address_book)")); }
+        let q = pm_dir_query { status_mask: 1u32 << NS_DISCOVERED, membership: DIR_ANY, order: DIR_BY_ROW, offset: 0, limit: u32::MAX };
+        let mut total = 0u32;
+        let listed = self.directory_locked(&t, &q, &mut total, None)?;
+        let n = listed.len();
+        if n == 0 { return Ok(Vec::new()); }
+        let rows: Vec<u32> = listed.iter().map(|r| r.worker).collect();
+        let nonces: Vec<[u8; 32]> = (0..n).map(|_| nonce()).collect();
+        let flat: Vec<u8> = nonces.iter().flatten().copied().collect();
+        let expiration = vec![expiration_s; n];
+        let (mut digest, mut signing) = (vec![0u8; 32 * n], vec![0u8; 32 * n]);
+        check(unsafe { pm_invite_digests(self.engine, domain_id, pool_id, rows.as_ptr(), n as u32, flat.as_ptr(), expiration.as_ptr(),
+                                         digest.as_mut_ptr(), signing.as_mut_ptr()) })?;
+        Ok((0..n).map(|k| {
+            let (mut d, mut s) = ([0u8; 32], [0u8; 32]);
+            d.copy_from_slice(&digest[32 * k..32 * k + 32]);
+            s.copy_from_slice(&signing[32 * k..32 * k + 32]);
+            (t.address_strings[rows[k] as usize].clone(), nonces[k], d, s)
+        }).collect())
     }
 
     /// rank of address.to_string() in byte order (BTreeSet<String>, mod.rs:424-434) among the first `known` rows:
@@ -1757,6 +1869,10 @@ impl GpuMatchPlugin {
 
     /// the reference keys node_to_group by address TEXT: exact string match (binary search in the address-ordered rows)
     fn row_of_address_text(t: &NodeTable, text: &str) -> Option<u32> {
+        if t.book_on {  // by the bytes: any spelling of the address finds the row
+            let a: Address = text.parse().ok()?;
+            return t.book_by_bytes.get(&a.into_array()).copied();
+        }
         let at = t.by_address.partition_point(|&j| t.address_strings[j as usize].as_str() < text);
         t.by_address.get(at).copied().filter(|&j| t.address_strings[j as usize] == text)
     }
@@ -1833,7 +1949,11 @@ impl GpuMatchPlugin {
 
     /// get_idx_in_group (mod.rs:424-434)
     pub fn get_idx_in_group(&self, node_group: &NodeGroup, node_addr: &str) -> Result<usize, Error> {
-        node_group.nodes.iter().position(|n| n == node_addr).ok_or_else(|| anyhow!("Node {} not found in group", node_addr))
+        if let Some(at) = node_group.nodes.iter().position(|n| n == node_addr) { return Ok(at); }
+        // (book on: the group lists the device's texts; another spelling of a member's address is that member)
+        let t = self.nodes.read();
+        let shown = if t.book_on { Self::row_of_address_text(&t, node_addr).map(|row| t.address_strings[row as usize].clone()) } else { None };
+        shown.and_then(|text| node_group.nodes.iter().position(|n| *n == text)).ok_or_else(|| anyhow!("Node {} not found in group", node_addr))
     }
 
     fn ordered_templates(&self, enabled: u64) -> Vec<NodeGroupConfiguration> {

@@ -43,6 +43,10 @@
 #                            1,000,000 over 100,000 — the counters, a first and a middle page in each order, the starved filter, the
 #                            full list — beside each what a host does today (pm_task_report + pm_rollout_tasks whole, a hash-map
 #                            join on ids, classification, filter, sort) -> r29_task_directory.txt (copy it to profiles/)
+#   addresses[:<args>]       tools/address_probe.py [W ...] [--bench DIR]: the address book at 10,000, 100,000 and 1,000,000 rows with
+#                            1 % appended a step — pm_addresses_set, pm_addresses_rank on both sort paths, a page of texts, the invite
+#                            digests — beside the set + rank pair what the plugin does today (an EIP-55 text per new address, the
+#                            sorted insert, the re-rank, pm_set_addr_ranks) -> r30_address_book.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -179,6 +183,9 @@ PY
     taskdir)
       timeout -k 10 500 python tools/taskdir_probe.py $arg --out "$out/r29_task_directory.txt" > "$out/${n}_taskdir.log" 2>&1; echo "taskdir rc=$?"
       tail -40 "$out/${n}_taskdir.log" ;;
+    addresses)
+      timeout -k 10 600 python tools/address_probe.py $arg --out "$out/r30_address_book.txt" > "$out/${n}_addresses.log" 2>&1; echo "addresses rc=$?"
+      tail -40 "$out/${n}_addresses.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
