@@ -207,35 +207,25 @@ void launch_ab_clear(uint8_t* set, uint32_t first, uint32_t end, hipStream_t s) 
   hipLaunchKernelGGL(ab_clear_kernel, dim3((end - first + 255u) / 256u), dim3(256), 0, s, set, first, end);
 }
 
-// `passes` stable passes over the low bits of key[cur] / val[cur]; returns the buffer that holds the result
-static uint32_t ab_sort_word(uint64_t* const key[2], uint32_t* const val[2], uint32_t cur, uint32_t W, uint32_t* hist, uint32_t* hist_scan,
-                             hipStream_t s) {
-  for (uint32_t p = 0; p < PM_AB_PASSES; ++p, cur ^= 1u)
-    launch_ro_radix_pass(key[cur], val[cur], W, 8u * p, hist, hist_scan, key[cur ^ 1u], val[cur ^ 1u], s);
-  return cur;
-}
-
-uint32_t launch_ab_sort_shallow(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
-                                uint32_t* hist_scan, uint32_t* ties, hipStream_t s) {
+uint32_t launch_ab_sort_shallow(const uint64_t* keys, uint32_t W, const RoSortBufs& b, uint32_t* ties, hipStream_t s) {
   if (!W) return 0u;
   const dim3 grid((W + 255u) / 256u);
-  hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)nullptr, W, 0u, key[0], val[0]);
-  const uint32_t cur = ab_sort_word(key, val, 0u, W, hist, hist_scan, s);
-  hipLaunchKernelGGL(ab_ties_kernel, grid, dim3(256), 0, s, key[cur], W, ties);
+  hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)nullptr, W, 0u, b.key[0], b.val[0]);
+  const uint32_t cur = launch_ro_radix_sort(b, W, PM_AB_PASSES, 0u, s);
+  hipLaunchKernelGGL(ab_ties_kernel, grid, dim3(256), 0, s, b.key[cur], W, ties);
   return cur;
 }
 
-uint32_t launch_ab_sort_deep(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
-                             uint32_t* hist_scan, hipStream_t s) {
+uint32_t launch_ab_sort_deep(const uint64_t* keys, uint32_t W, const RoSortBufs& b, hipStream_t s) {
   if (!W) return 0u;
   const dim3 grid((W + 255u) / 256u);
   uint32_t cur = 0u;
   for (uint32_t w = PM_AB_WORDS; w-- > 0u;) {
     if (w + 1u == PM_AB_WORDS)
-      hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)nullptr, W, w, key[cur], val[cur]);
+      hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)nullptr, W, w, b.key[cur], b.val[cur]);
     else
-      hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)val[cur], W, w, key[cur], (uint32_t*)nullptr);
-    cur = ab_sort_word(key, val, cur, W, hist, hist_scan, s);
+      hipLaunchKernelGGL(ab_gather_kernel, grid, dim3(256), 0, s, keys, (const uint32_t*)b.val[cur], W, w, b.key[cur], (uint32_t*)nullptr);
+    cur = launch_ro_radix_sort(b, W, PM_AB_PASSES, cur, s);
   }
   return cur;
 }

@@ -660,6 +660,15 @@ void launch_ro_emit(const RoPrepArgs& a, hipStream_t s);
 // one radix pass over digit (key >> shift) & 255: hist [256][chunks] (digit-major), scanned into `hist_scan`
 void launch_ro_radix_pass(const uint64_t* key_in, const uint32_t* val_in, uint32_t N, uint32_t shift, uint32_t* hist,
                           uint32_t* hist_scan, uint64_t* key_out, uint32_t* val_out, hipStream_t s);
+// what a key sort works in: keys and side words, ping-pong, and a pass's histogram and its scan (KeySort of
+// pm_engine_types.inc owns and sizes them)
+struct RoSortBufs {
+  uint64_t* key[2];
+  uint32_t* val[2];
+  uint32_t *hist, *hist_scan;
+};
+// `passes` stable passes from the low byte over the N keys of buffer `cur`; returns the buffer that holds the result
+uint32_t launch_ro_radix_sort(const RoSortBufs& b, uint32_t N, uint32_t passes, uint32_t cur, hipStream_t s);
 void launch_ro_heads(const uint64_t* key, uint32_t N, uint32_t* head, hipStream_t s);
 void launch_ro_starts(const uint32_t* head, const uint32_t* head_off, uint32_t N, uint32_t* start, hipStream_t s);
 // one row per run of equal keys: start [D] the runs' first entries
@@ -671,14 +680,16 @@ void launch_ro_worker_flags(const uint8_t* cls, uint32_t W, uint32_t class_mask,
 void launch_ro_worker_rows(const RoPrepArgs& a, const uint32_t* flag, const uint32_t* off, pm_ro_worker_row* rows, hipStream_t s);
 // node directory (pm_directory.inc)
 void launch_dir_classify(const DirArgs& a, hipStream_t s);
-void launch_dir_window(const DirArgs& a, hipStream_t s);
+// the three directories' window (Args: DirArgs, GdirArgs, TdirArgs): of the n_index entries of the index space, those whose
+// place falls in [a.offset, a.offset + a.n_rows) write themselves to a.win[place - a.offset]
+template <class Args>
+void launch_list_window(const Args& a, uint32_t n_index, hipStream_t s);
 void launch_dir_keys(const DirArgs& a, hipStream_t s);
 // rows[k] = the joined record of worker list[k], k < n
 void launch_dir_emit(const DirArgs& a, const uint32_t* list, uint32_t n, pm_dir_row* rows, hipStream_t s);
 // group directory (pm_groupdir.inc)
 void launch_gdir_members(const GdirArgs& a, hipStream_t s);
 void launch_gdir_groups(const GdirArgs& a, hipStream_t s);
-void launch_gdir_window(const GdirArgs& a, hipStream_t s);
 void launch_gdir_keys(const GdirArgs& a, hipStream_t s);
 // rows[k] = the joined record of list entry list[k], k < n (member_begin is the host's: it lays the members out)
 void launch_gdir_emit(const GdirArgs& a, const uint32_t* list, uint32_t n, pm_gdir_row* rows, hipStream_t s);
@@ -689,7 +700,6 @@ void launch_tdir_groups(const TdirArgs& a, hipStream_t s);
 void launch_tdir_join(const TdirArgs& a, const pm_ro_task_row* runs, uint32_t D, const uint64_t* key, const uint32_t* val,
                       uint32_t n_pairs, hipStream_t s);
 void launch_tdir_tasks(const TdirArgs& a, hipStream_t s);
-void launch_tdir_window(const TdirArgs& a, hipStream_t s);
 void launch_tdir_keys(const TdirArgs& a, hipStream_t s);
 // rows[k] = the joined record of slot list[k], handles[k] its handle, k < n (uid is the host's: the ids never went up whole)
 void launch_tdir_emit(const TdirArgs& a, const uint32_t* list, uint32_t n, pm_tdir_row* rows, uint32_t* handles, hipStream_t s);
@@ -702,11 +712,9 @@ void launch_ab_set(const uint32_t* in, uint32_t first, uint32_t n, uint32_t* byt
 void launch_ab_text(const uint32_t* rows, uint32_t n, const uint32_t* bytes, const uint64_t* mask, uint8_t* out, hipStream_t s);
 void launch_ab_clear(uint8_t* set, uint32_t first, uint32_t end, hipStream_t s);
 // (word 0, row) of every row sorted into key / val [returned buffer]; *ties += neighbours that share word 0
-uint32_t launch_ab_sort_shallow(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
-                                uint32_t* hist_scan, uint32_t* ties, hipStream_t s);
+uint32_t launch_ab_sort_shallow(const uint64_t* keys, uint32_t W, const RoSortBufs& b, uint32_t* ties, hipStream_t s);
 // the rows sorted by all PM_AB_WORDS words into val [returned buffer]
-uint32_t launch_ab_sort_deep(const uint64_t* keys, uint32_t W, uint64_t* const key[2], uint32_t* const val[2], uint32_t* hist,
-                             uint32_t* hist_scan, hipStream_t s);
+uint32_t launch_ab_sort_deep(const uint64_t* keys, uint32_t W, const RoSortBufs& b, hipStream_t s);
 // rank[val[i]] = i
 void launch_ab_rank(const uint32_t* val, uint32_t W, uint32_t* rank, hipStream_t s);
 // digest / signing [4 k, 4 k + 4): the invite digest of row rows[k] and its EIP-191 signing hash; nonce [4 n], expiration [n]

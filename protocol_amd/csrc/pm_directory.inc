@@ -10,7 +10,11 @@
 // (class, row) order at off[cls * W + w]: the class's base and the row's rank inside the class in one word, and the total behind
 // the last flag.  That is the whole of BY_ROW's order: a four-class ordered compaction, no sort.
 //
-// WINDOW (BY_ROW).  Only the rows whose place falls in [offset, offset + n_rows) write, their index into win[place - offset].
+// PLACE.  list_place(a, i): entry i's place in scan order, or PM_NONE where it is not listed (or no entry).  Every directory
+// states its own once, and both its window and its keys kernel ask it.
+//
+// WINDOW (BY_ROW).  Only the rows whose place falls in [offset, offset + n_rows) write, their index into win[place - offset]:
+// list_window_kernel, the one window kernel of the three directories, over the directory's argument block.
 //
 // KEYS (BY_ADDRESS).  Every listed row writes (class << 32 | rank, row) at its place; launch_ro_radix_pass then sorts the 34
 // significant bits in five passes (stable, fixed chunks: ties keep (class, row) order, and the class is in the key, so ties
@@ -54,22 +58,25 @@ __global__ __launch_bounds__(256) void dir_classify_kernel(DirArgs a) {
   if (tid < PM_NS_N && s_bin[tid]) atomicAdd(&a.census[tid], s_bin[tid]);
 }
 
-__global__ __launch_bounds__(256) void dir_window_kernel(DirArgs a) {
-  const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-  if (w >= a.W) return;
+__device__ __forceinline__ uint32_t list_place(const DirArgs& a, uint32_t w) {
+  if (w >= a.W) return PM_NONE;
   const uint32_t cls = a.cls[w];
-  if (cls >= PM_DC_N) return;
-  const uint32_t at = a.off[(size_t)cls * a.W + w];
-  if (at >= a.offset && at - a.offset < a.n_rows) a.win[at - a.offset] = w;
+  return cls < PM_DC_N ? a.off[(size_t)cls * a.W + w] : PM_NONE;
+}
+
+// Args: a directory's argument block — list_place(a, i), and offset, n_rows, win
+template <class Args>
+__global__ __launch_bounds__(256) void list_window_kernel(Args a) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t at = list_place(a, i);
+  if (at != PM_NONE && at >= a.offset && at - a.offset < a.n_rows) a.win[at - a.offset] = i;
 }
 
 __global__ __launch_bounds__(256) void dir_keys_kernel(DirArgs a) {
   const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-  if (w >= a.W) return;
-  const uint32_t cls = a.cls[w];
-  if (cls >= PM_DC_N) return;
-  const uint32_t at = a.off[(size_t)cls * a.W + w];
-  a.key[at] = ((uint64_t)cls << 32) | a.addr_rank[w];
+  const uint32_t at = list_place(a, w);
+  if (at == PM_NONE) return;
+  a.key[at] = ((uint64_t)a.cls[w] << 32) | a.addr_rank[w];
   a.val[at] = w;
 }
 
@@ -109,10 +116,14 @@ void launch_dir_classify(const DirArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(dir_classify_kernel, dim3((a.W + 255u) / 256u), dim3(256), 0, s, a);
 }
 
-void launch_dir_window(const DirArgs& a, hipStream_t s) {
-  if (!a.W || !a.n_rows) return;
-  hipLaunchKernelGGL(dir_window_kernel, dim3((a.W + 255u) / 256u), dim3(256), 0, s, a);
+template <class Args>
+void launch_list_window(const Args& a, uint32_t n_index, hipStream_t s) {
+  if (!n_index || !a.n_rows) return;
+  hipLaunchKernelGGL(list_window_kernel<Args>, dim3((n_index + 255u) / 256u), dim3(256), 0, s, a);
 }
+// one instantiation a directory, behind its list_place: here, in pm_groupdir.inc and in pm_taskdir.inc (a new directory: its
+// kernel file behind this one, a list_place overload for its Args, one such line)
+template void launch_list_window<DirArgs>(const DirArgs&, uint32_t, hipStream_t);
 
 void launch_dir_keys(const DirArgs& a, hipStream_t s) {
   if (!a.W) return;

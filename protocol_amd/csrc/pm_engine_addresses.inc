@@ -110,29 +110,22 @@ int32_t pm_addresses_rank(pm_engine* e, uint32_t* rank_out) {
   const uint32_t W = e->W;
   if (ab.n_set != W) return set_error(PM_ESTATE, "rows without an address (pm_addresses_set)");
   if (!W) return PM_OK;
-  const uint32_t chunks = (W + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-  for (int b = 0; b < 2; ++b) {
-    HIPCHK(ab.key[b].ensure(W));
-    HIPCHK(ab.val[b].ensure(W));
-  }
-  HIPCHK(ab.hist.ensure(256 * size_t(chunks)));
-  HIPCHK(ab.hist_scan.ensure(256 * size_t(chunks) + 1));
+  HIPCHK(ab.sort.ensure(W));
   HIPCHK(ab.ties.ensure(1));
   HIPCHK(e->d_addr_rank.ensure(W));  // (the worker upload sized it)
-  uint64_t* const key[2] = {ab.key[0].p, ab.key[1].p};
-  uint32_t* const val[2] = {ab.val[0].p, ab.val[1].p};
+  const RoSortBufs bufs = ab.sort.bufs();
   HIPCHK(hipMemsetAsync(ab.ties.p, 0, sizeof(uint32_t), e->stream));
-  uint32_t cur = launch_ab_sort_shallow(ab.keys.p, W, key, val, ab.hist.p, ab.hist_scan.p, ab.ties.p, e->stream);
+  uint32_t cur = launch_ab_sort_shallow(ab.keys.p, W, bufs, ab.ties.p, e->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(ab.h_pin.p, ab.ties.p, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   if (ab.h_pin.p[0]) {  // two rows share their first ten characters: every word decides
-    cur = launch_ab_sort_deep(ab.keys.p, W, key, val, ab.hist.p, ab.hist_scan.p, e->stream);
+    cur = launch_ab_sort_deep(ab.keys.p, W, bufs, e->stream);
     ab.deep++;
   } else {
     ab.shallow++;
   }
-  launch_ab_rank(val[cur], W, e->d_addr_rank.p, e->stream);
+  launch_ab_rank(bufs.val[cur], W, e->d_addr_rank.p, e->stream);
   HIPCHK(hipGetLastError());
   e->h_addr_rank.resize(W);
   HIPCHK(hipMemcpyAsync(e->h_addr_rank.data(), e->d_addr_rank.p, size_t(W) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));

@@ -24,17 +24,17 @@ int32_t pm_directory(pm_engine* e, const pm_dir_query* q, uint32_t* total, uint3
   if (e->ro.on && (rc = rollout_prepare(e))) return rc;
   Directory& d = e->dir;
   const uint32_t W = e->W, G = uint32_t(e->groups.size());
-  HIPCHK(d.h_pin.ensure(1 + PM_NS_N, 1 + PM_NS_N));
-  std::memset(d.h_pin.p, 0, (1 + PM_NS_N) * sizeof(uint32_t));
+  HIPCHK(d.pg.pin(PM_NS_N));
   DirArgs a{};
+  uint32_t n_listed = 0;
   if (W) {
     group_records(e, d.h_g);
     if ((rc = upload(d.gof, e->h_group_of.data(), size_t(W), e->stream))) return rc;
     if ((rc = upload(d.g, d.h_g.data(), size_t(G), e->stream))) return rc;
     const size_t n_flag = size_t(PM_DC_N) * W;
     HIPCHK(d.cls.ensure(W));
-    HIPCHK(d.flag.ensure(n_flag));
-    HIPCHK(d.off.ensure(n_flag + 1));
+    HIPCHK(d.pg.flag.ensure(n_flag));
+    HIPCHK(d.pg.off.ensure(n_flag + 1));
     HIPCHK(d.census.ensure(PM_NS_N));
     HIPCHK(hipMemsetAsync(d.census.p, 0, PM_NS_N * sizeof(uint32_t), e->stream));
     a.W = W, a.G = G;
@@ -47,47 +47,27 @@ int32_t pm_directory(pm_engine* e, const pm_dir_query* q, uint32_t* total, uint3
     a.uid = e->ro.on ? e->ro.uid.p : nullptr;
     a.state = e->ro.on ? e->ro.state.p : nullptr;
     a.cls = d.cls.p;
-    a.flag = d.flag.p;
+    a.flag = d.pg.flag.p;
     a.census = d.census.p;
-    a.off = d.off.p;
+    a.off = d.pg.off.p;
     launch_dir_classify(a, e->stream);
-    launch_mx_scan(d.flag.p, uint32_t(n_flag), d.off.p, d.h_pin.p, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(d.h_pin.p + 1, d.census.p, PM_NS_N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    if ((rc = page_counters(d.pg, uint32_t(n_flag), d.census.p, PM_NS_N, e->stream, &n_listed))) return rc;
   }
-  const uint32_t n_listed = d.h_pin.p[0];
   if (n_listed > W) return set_error(PM_ESTATE, "directory: more listed rows than rows");
   const uint32_t n = q->offset >= n_listed ? 0u : std::min(q->limit, n_listed - q->offset);
   *total = n_listed;
-  if (counts) std::copy(d.h_pin.p + 1, d.h_pin.p + 1 + PM_NS_N, counts);
+  if (counts) std::copy(d.pg.h_pin.p + 1, d.pg.h_pin.p + 1 + PM_NS_N, counts);
   *n_rows = n;
   if (n && (!rows || cap < n)) return set_error(PM_ERANGE, "directory row buffer too small");
   if (!n) return PM_OK;
   a.offset = q->offset, a.n_rows = n;
   const uint32_t* list = nullptr;
-  if (q->order == PM_DIR_BY_ROW) {
-    HIPCHK(d.win.ensure(n));
-    a.win = d.win.p;
-    launch_dir_window(a, e->stream);
-    list = d.win.p;
-  } else {
-    const uint32_t chunks = (n_listed + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-    for (int b = 0; b < 2; ++b) {
-      HIPCHK(d.key[b].ensure(n_listed));
-      HIPCHK(d.val[b].ensure(n_listed));
-    }
-    HIPCHK(d.hist.ensure(256 * size_t(chunks)));
-    HIPCHK(d.hist_scan.ensure(256 * size_t(chunks) + 1));
-    a.key = d.key[0].p;
-    a.val = d.val[0].p;
-    launch_dir_keys(a, e->stream);
-    uint32_t cur = 0;
-    for (uint32_t p = 0; p < 5u; ++p, cur ^= 1u)  // 32 bits of rank, the class's two in the fifth byte: ends in buffer 1
-      launch_ro_radix_pass(d.key[cur].p, d.val[cur].p, n_listed, 8u * p, d.hist.p, d.hist_scan.p, d.key[cur ^ 1u].p,
-                           d.val[cur ^ 1u].p, e->stream);
-    list = d.val[cur].p + q->offset;
-  }
+  const uint32_t passes = q->order == PM_DIR_BY_ROW ? 0u : 5u;  // BY_ADDRESS: 32 bits of rank, the class's two in the fifth byte
+  const hipStream_t s = e->stream;  // (the callables capture the arguments, the stream and the index space, by value but for a)
+  rc = page_list(
+      d.pg, n_listed, q->offset, n, passes, s, [&a, s, W](uint32_t* win) { a.win = win, launch_list_window(a, W, s); },
+      [&a, s](uint64_t* key, uint32_t* val) { a.key = key, a.val = val, launch_dir_keys(a, s); }, &list);
+  if (rc) return rc;
   HIPCHK(d.rows.ensure(n));
   launch_dir_emit(a, list, n, d.rows.p, e->stream);
   HIPCHK(hipGetLastError());

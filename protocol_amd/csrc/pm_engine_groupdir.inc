@@ -40,9 +40,9 @@ int32_t pm_group_directory(pm_engine* e, const pm_gdir_query* q, pm_gdir_totals*
   if (e->ro.on && (rc = rollout_prepare(e))) return rc;
   GroupDir& d = e->gdir;
   const uint32_t W = e->W, G = uint32_t(e->groups.size()), n_cfgs = uint32_t(e->cfgs.size());
-  HIPCHK(d.h_pin.ensure(1 + PM_GD_CENSUS, 1 + PM_GD_CENSUS));
-  std::memset(d.h_pin.p, 0, (1 + PM_GD_CENSUS) * sizeof(uint32_t));
+  HIPCHK(d.pg.pin(PM_GD_CENSUS));
   GdirArgs a{};
+  uint32_t n_listed = 0;
   if (G) {
     group_records(e, d.h_g, &d.h_of_slot);
     a.n_cls = q->order == PM_GDIR_BY_ID_TEXT ? PM_GD_TEXT_CLASSES : 1u;
@@ -52,8 +52,8 @@ int32_t pm_group_directory(pm_engine* e, const pm_gdir_query* q, pm_gdir_totals*
     HIPCHK(d.cnt.ensure(n_cnt));
     HIPCHK(d.cls.ensure(G));
     HIPCHK(d.hr.ensure(2 * size_t(G)));
-    HIPCHK(d.flag.ensure(n_flag));
-    HIPCHK(d.off.ensure(n_flag + 1));
+    HIPCHK(d.pg.flag.ensure(n_flag));
+    HIPCHK(d.pg.off.ensure(n_flag + 1));
     HIPCHK(hipMemsetAsync(d.cnt.p, 0, n_cnt * sizeof(uint32_t), e->stream));
     a.W = W, a.G = G;
     a.config_mask = q->config_mask;
@@ -68,18 +68,14 @@ int32_t pm_group_directory(pm_engine* e, const pm_gdir_query* q, pm_gdir_totals*
     a.census = d.cnt.p + size_t(G) * PM_GD_CNT;
     a.cls = d.cls.p;
     a.hr = d.hr.p;
-    a.flag = d.flag.p;
-    a.off = d.off.p;
+    a.flag = d.pg.flag.p;
+    a.off = d.pg.off.p;
     launch_gdir_members(a, e->stream);
     launch_gdir_groups(a, e->stream);
-    launch_mx_scan(d.flag.p, uint32_t(n_flag), d.off.p, d.h_pin.p, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(d.h_pin.p + 1, a.census, PM_GD_CENSUS * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    if ((rc = page_counters(d.pg, uint32_t(n_flag), a.census, PM_GD_CENSUS, e->stream, &n_listed))) return rc;
   }
-  const uint32_t n_listed = d.h_pin.p[0];
   if (n_listed > G) return set_error(PM_ESTATE, "group directory: more listed groups than groups");
-  const uint32_t* c = d.h_pin.p + 1;
+  const uint32_t* c = d.pg.h_pin.p + 1;
   totals->total = n_listed;
   totals->members_total = c[PM_GD_CENSUS - 1];
   std::copy(c + PM_MAX_CONFIGS, c + PM_MAX_CONFIGS + PM_GH_N, totals->by_health);
@@ -93,30 +89,13 @@ int32_t pm_group_directory(pm_engine* e, const pm_gdir_query* q, pm_gdir_totals*
   if (n) {
     a.offset = q->offset, a.n_rows = n;
     const uint32_t* list = nullptr;
-    if (q->order == PM_GDIR_BY_SLOT) {
-      HIPCHK(d.win.ensure(n));
-      a.win = d.win.p;
-      launch_gdir_window(a, e->stream);
-      list = d.win.p;
-    } else {
-      const uint32_t chunks = (n_listed + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-      for (int b = 0; b < 2; ++b) {
-        HIPCHK(d.key[b].ensure(n_listed));
-        HIPCHK(d.val[b].ensure(n_listed));
-      }
-      HIPCHK(d.hist.ensure(256 * size_t(chunks)));
-      HIPCHK(d.hist_scan.ensure(256 * size_t(chunks) + 1));
-      a.key = d.key[0].p;
-      a.val = d.val[0].p;
-      launch_gdir_keys(a, e->stream);
-      // BY_ID_TEXT: every byte of A, eight passes; BY_SIZE_DESC: the four bytes of UINT32_MAX - size.  Both end in buffer 0.
-      const uint32_t passes = q->order == PM_GDIR_BY_ID_TEXT ? 8u : 4u;
-      uint32_t cur = 0;
-      for (uint32_t p = 0; p < passes; ++p, cur ^= 1u)
-        launch_ro_radix_pass(d.key[cur].p, d.val[cur].p, n_listed, 8u * p, d.hist.p, d.hist_scan.p, d.key[cur ^ 1u].p,
-                             d.val[cur ^ 1u].p, e->stream);
-      list = d.val[cur].p + q->offset;
-    }
+    // BY_ID_TEXT: every byte of A, eight passes; BY_SIZE_DESC: the four bytes of UINT32_MAX - size
+    const uint32_t passes = q->order == PM_GDIR_BY_SLOT ? 0u : q->order == PM_GDIR_BY_ID_TEXT ? 8u : 4u;
+    const hipStream_t s = e->stream;  // (the callables capture the arguments, the stream and the index space, by value but for a)
+    rc = page_list(
+        d.pg, n_listed, q->offset, n, passes, s, [&a, s, G](uint32_t* win) { a.win = win, launch_list_window(a, G, s); },
+        [&a, s](uint64_t* key, uint32_t* val) { a.key = key, a.val = val, launch_gdir_keys(a, s); }, &list);
+    if (rc) return rc;
     HIPCHK(d.rows.ensure(n));
     d.h_rows.resize(n);
     launch_gdir_emit(a, list, n, d.rows.p, e->stream);

@@ -108,26 +108,18 @@ static int32_t rollout_read(pm_engine* e, bool tasks, RoPrepArgs* a, uint32_t* n
   HIPCHK(hipStreamSynchronize(e->stream));
   const uint32_t N = ro.h_pin.p[0];  // reporting rows + listed groups
   if (N > n_flag) return set_error(PM_ESTATE, "rollout: more keys than rows and groups");
-  HIPCHK(ro.key[0].ensure(N ? N : 1));
-  HIPCHK(ro.val[0].ensure(N ? N : 1));
+  HIPCHK(ro.sort.ensure_first(N));
   a->off = ro.off.p;
-  a->key = ro.key[0].p;
-  a->val = ro.val[0].p;
+  a->key = ro.sort.key[0].p;
+  a->val = ro.sort.val[0].p;
   launch_ro_emit(*a, e->stream);  // (also without `tasks`: it counts the converged groups)
   uint32_t D = 0;
   if (tasks && N) {
-    const uint32_t chunks = (N + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-    HIPCHK(ro.key[1].ensure(N));
-    HIPCHK(ro.val[1].ensure(N));
-    HIPCHK(ro.hist.ensure(256 * size_t(chunks)));
-    HIPCHK(ro.hist_scan.ensure(256 * size_t(chunks) + 1));
+    HIPCHK(ro.sort.ensure(N));
     HIPCHK(ro.head.ensure(N));
     HIPCHK(ro.head_off.ensure(size_t(N) + 1));
-    uint32_t cur = 0;
-    for (uint32_t p = 0; p < 8u; ++p, cur ^= 1u)  // every byte of the id: eight passes, ending in buffer 0
-      launch_ro_radix_pass(ro.key[cur].p, ro.val[cur].p, N, 8u * p, ro.hist.p, ro.hist_scan.p, ro.key[cur ^ 1u].p,
-                           ro.val[cur ^ 1u].p, e->stream);
-    launch_ro_heads(ro.key[0].p, N, ro.head.p, e->stream);
+    const uint32_t cur = ro.sort.sort(N, 8u, 0u, e->stream);  // every byte of the id
+    launch_ro_heads(ro.sort.key[cur].p, N, ro.head.p, e->stream);
     launch_mx_scan(ro.head.p, N, ro.head_off.p, ro.h_pin.p, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -136,7 +128,7 @@ static int32_t rollout_read(pm_engine* e, bool tasks, RoPrepArgs* a, uint32_t* n
     HIPCHK(ro.start.ensure(D ? D : 1));
     HIPCHK(ro.task_rows.ensure(D ? D : 1));
     launch_ro_starts(ro.head.p, ro.head_off.p, N, ro.start.p, e->stream);
-    launch_ro_reduce(ro.key[0].p, ro.val[0].p, N, ro.start.p, D, ro.g.p, ro.cnt.p, ro.task_rows.p, e->stream);
+    launch_ro_reduce(ro.sort.key[cur].p, ro.sort.val[cur].p, N, ro.start.p, D, ro.g.p, ro.cnt.p, ro.task_rows.p, e->stream);
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(ro.h_pin.p + 1, a->census, PM_RO_CENSUS * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));

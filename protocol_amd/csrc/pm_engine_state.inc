@@ -99,8 +99,8 @@ struct Rollout {
   DevBuf<uint8_t> cls;        // [W]
   DevBuf<uint32_t> cnt;       // [G * PM_RO_GCNT] the groups' counters, behind them [PM_RO_CENSUS] the census
   DevBuf<uint32_t> flag, off;  // [W + G] (+ 1): reports / is listed, and the scan; the lists' flags and offsets
-  DevBuf<uint64_t> key[2];    // the sort's keys and side words, ping-pong
-  DevBuf<uint32_t> val[2], hist, hist_scan, head, head_off, start;
+  KeySort sort;               // the id sort: the keys (buffer 0 is made by every read) and their side words
+  DevBuf<uint32_t> head, head_off, start;
   DevBuf<pm_ro_task_row> task_rows;
   DevBuf<pm_ro_group_row> group_rows;
   DevBuf<pm_ro_worker_row> worker_rows;
@@ -115,13 +115,9 @@ struct Directory {
   DevBuf<int32_t> gof;        // the join's other side: the host's group_of, its group list
   DevBuf<DirGroup> g;
   DevBuf<uint8_t> cls;        // [W]
-  DevBuf<uint32_t> flag, off; // [PM_DC_N * W] (+ 1): the class flags and their scan
+  ListPage pg;                // [PM_DC_N * W] class flags; BY_ROW is scan order, BY_ADDRESS sorted; PM_NS_N census words
   DevBuf<uint32_t> census;    // [PM_NS_N]
-  DevBuf<uint32_t> win;       // BY_ROW: the window's rows
-  DevBuf<uint64_t> key[2];    // BY_ADDRESS: the sort's keys and rows, ping-pong
-  DevBuf<uint32_t> val[2], hist, hist_scan;
   DevBuf<pm_dir_row> rows;
-  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_NS_N) the census
   std::vector<DirGroup> h_g;
 };
 
@@ -131,12 +127,8 @@ struct GroupDir {
   DevBuf<RoGroup> g;
   DevBuf<uint32_t> cnt;       // [G * PM_GD_CNT] the groups' counters, behind them [PM_GD_CENSUS] the census
   DevBuf<uint8_t> cls, hr;    // [G], [2 G]
-  DevBuf<uint32_t> flag, off; // [n_cls * G] (+ 1): the class flags and their scan
-  DevBuf<uint32_t> win;       // BY_SLOT: the window's entries
-  DevBuf<uint64_t> key[2];    // the sorted orders: keys and entries, ping-pong
-  DevBuf<uint32_t> val[2], hist, hist_scan;
+  ListPage pg;                // [n_cls * G] class flags; BY_SLOT is scan order, the others sorted; PM_GD_CENSUS census words
   DevBuf<pm_gdir_row> rows;
-  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_GD_CENSUS) the census
   std::vector<RoGroup> h_g;
   std::vector<uint32_t> h_of_slot;  // reported slot -> list entry
   std::vector<pm_gdir_row> h_rows;  // the window, before the caller's buffers are known to hold it
@@ -147,13 +139,10 @@ struct TaskDir {
   DevBuf<TdirGroup> g;        // the join's other side: the host's group list
   DevBuf<uint32_t> cnt;       // [R * PM_TD_CNT] the slots' counters, behind them [PM_MAX_CONFIGS] the live groups per configuration, [PM_TD_CENSUS] the census
   DevBuf<uint8_t> cls;        // [2 R]
-  DevBuf<uint32_t> flag, off; // [R] (+ 1): the listing flags and their scan
-  DevBuf<uint32_t> win;       // BY_LIST, BY_OLDEST: the window's slots
-  DevBuf<uint64_t> key[2];    // the id join's sorted (id, slot) pairs, then the sorted orders' keys and slots, ping-pong
-  DevBuf<uint32_t> val[2], hist, hist_scan;
+  ListPage pg;                // [R] listing flags; BY_LIST and BY_OLDEST are scan order, the _DESC orders sorted; PM_TD_CENSUS
+                              // census words.  pg.sort holds the id join's sorted (id, slot) pairs first
   DevBuf<pm_tdir_row> rows;
   DevBuf<uint32_t> handles;   // the window's handles (the host writes the ids by them)
-  PinBuf<uint32_t> h_pin;     // [0] the scan's total, [1, 1 + PM_TD_CENSUS) the census
   std::vector<TdirGroup> h_g;
   std::vector<uint64_t> h_key;      // the live rows' ids, in list order, ...
   std::vector<uint32_t> h_val;      // ... and their slots
@@ -174,8 +163,8 @@ struct AddressBook {
   DevBuf<uint8_t> set;        // [W]
   std::vector<uint8_t> h_set; // (the flags' host mirror: what n_set counts)
   DevBuf<uint32_t> stage;     // a call's inputs: addresses, rows, offsets
-  DevBuf<uint64_t> key[2];    // the sort's keys and rows, ping-pong
-  DevBuf<uint32_t> val[2], hist, hist_scan, ties;
+  KeySort sort;               // the rank's sort: keys and rows
+  DevBuf<uint32_t> ties;
   DevBuf<uint8_t> text;       // rendered texts; pm_keccak256_many's messages
   DevBuf<uint64_t> in64, out64;  // nonces and expirations; digests
   PinBuf<uint32_t> h_pin;     // [0] the ties

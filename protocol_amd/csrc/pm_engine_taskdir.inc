@@ -46,9 +46,9 @@ int32_t pm_task_directory(pm_engine* e, const pm_tdir_query* q, pm_tdir_totals* 
   TaskDir& d = e->tdir;
   const uint32_t G = uint32_t(e->groups.size()), n_cfgs = uint32_t(e->cfgs.size());
   const uint32_t R = e->t_cap - e->t_lo;  // slots: the used part of the index space, tombstones included
-  HIPCHK(d.h_pin.ensure(1 + PM_TD_CENSUS, 1 + PM_TD_CENSUS));
-  std::memset(d.h_pin.p, 0, (1 + PM_TD_CENSUS) * sizeof(uint32_t));
+  HIPCHK(d.pg.pin(PM_TD_CENSUS));
   TdirArgs a{};
+  uint32_t n_listed = 0;
   if (R) {
     d.h_g.resize(G);
     for (uint32_t k = 0; k < G; ++k) {
@@ -61,8 +61,8 @@ int32_t pm_task_directory(pm_engine* e, const pm_tdir_query* q, pm_tdir_totals* 
     const size_t n_cnt = size_t(R) * PM_TD_CNT + PM_MAX_CONFIGS + PM_TD_CENSUS;
     HIPCHK(d.cnt.ensure(n_cnt));
     HIPCHK(d.cls.ensure(2 * size_t(R)));
-    HIPCHK(d.flag.ensure(R));
-    HIPCHK(d.off.ensure(size_t(R) + 1));
+    HIPCHK(d.pg.flag.ensure(R));
+    HIPCHK(d.pg.off.ensure(size_t(R) + 1));
     HIPCHK(hipMemsetAsync(d.cnt.p, 0, n_cnt * sizeof(uint32_t), e->stream));
     a.G = G, a.n_cfgs = n_cfgs, a.t_lo = e->t_lo, a.t_cap = e->t_cap;
     a.config_mask = q->config_mask;
@@ -77,8 +77,8 @@ int32_t pm_task_directory(pm_engine* e, const pm_tdir_query* q, pm_tdir_totals* 
     a.g_per_cfg = d.cnt.p + size_t(R) * PM_TD_CNT;
     a.census = a.g_per_cfg + PM_MAX_CONFIGS;
     a.cls = d.cls.p;
-    a.flag = d.flag.p;
-    a.off = d.off.p;
+    a.flag = d.pg.flag.p;
+    a.off = d.pg.off.p;
     launch_tdir_groups(a, e->stream);
     if (D) {
       // the live rows' (id, slot) pairs in list order; sorted by id they keep that order inside a run of equal ids
@@ -90,39 +90,30 @@ int32_t pm_task_directory(pm_engine* e, const pm_tdir_query* q, pm_tdir_totals* 
           d.h_val.push_back(u - e->t_lo);
         }
       const uint32_t n_pairs = uint32_t(d.h_key.size());
-      if ((rc = upload(d.key[0], d.h_key.data(), size_t(n_pairs), e->stream))) return rc;
-      if ((rc = upload(d.val[0], d.h_val.data(), size_t(n_pairs), e->stream))) return rc;
+      KeySort& ks = d.pg.sort;
+      if ((rc = upload(ks.key[0], d.h_key.data(), size_t(n_pairs), e->stream))) return rc;
+      if ((rc = upload(ks.val[0], d.h_val.data(), size_t(n_pairs), e->stream))) return rc;
+      uint32_t cur = 0;
       if (n_pairs) {
-        const uint32_t chunks = (n_pairs + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-        HIPCHK(d.key[1].ensure(n_pairs));
-        HIPCHK(d.val[1].ensure(n_pairs));
-        HIPCHK(d.hist.ensure(256 * size_t(chunks)));
-        HIPCHK(d.hist_scan.ensure(256 * size_t(chunks) + 1));
-        uint32_t cur = 0;
-        for (uint32_t p = 0; p < 8u; ++p, cur ^= 1u)  // every byte of the id: eight passes, ending in buffer 0
-          launch_ro_radix_pass(d.key[cur].p, d.val[cur].p, n_pairs, 8u * p, d.hist.p, d.hist_scan.p, d.key[cur ^ 1u].p,
-                               d.val[cur ^ 1u].p, e->stream);
+        HIPCHK(ks.ensure(n_pairs));
+        cur = ks.sort(n_pairs, 8u, 0u, e->stream);  // every byte of the id
       }
-      launch_tdir_join(a, e->ro.task_rows.p, D, d.key[0].p, d.val[0].p, n_pairs, e->stream);
+      launch_tdir_join(a, e->ro.task_rows.p, D, ks.key[cur].p, ks.val[cur].p, n_pairs, e->stream);
     }
     launch_tdir_tasks(a, e->stream);
-    launch_mx_scan(d.flag.p, R, d.off.p, d.h_pin.p, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(d.h_pin.p + 1, a.census, PM_TD_CENSUS * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    if ((rc = page_counters(d.pg, R, a.census, PM_TD_CENSUS, e->stream, &n_listed))) return rc;
   } else if (D) {
     // no slot at all: every reported id is an orphan
     d.h_rows.clear();
     std::vector<pm_ro_task_row> runs(D);
     HIPCHK(hipMemcpyAsync(runs.data(), e->ro.task_rows.p, size_t(D) * sizeof(pm_ro_task_row), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    d.h_pin.p[1 + TD_C_ORPHAN_UIDS] = D;
+    d.pg.h_pin.p[1 + TD_C_ORPHAN_UIDS] = D;
     for (const pm_ro_task_row& r : runs)
-      for (uint32_t s = 0; s < PM_TS_N; ++s) d.h_pin.p[1 + TD_C_ORPHAN_REPORTERS] += r.reporters[s];
+      for (uint32_t s = 0; s < PM_TS_N; ++s) d.pg.h_pin.p[1 + TD_C_ORPHAN_REPORTERS] += r.reporters[s];
   }
-  const uint32_t n_listed = d.h_pin.p[0];
   if (n_listed > e->T) return set_error(PM_ESTATE, "task directory: more listed tasks than tasks");
-  const uint32_t* c = d.h_pin.p + 1;
+  const uint32_t* c = d.pg.h_pin.p + 1;
   totals->tasks = e->T;
   totals->total = n_listed;
   std::copy(c + TD_C_SERVE, c + TD_C_SERVE + PM_TKS_N, totals->by_serve);
@@ -142,28 +133,13 @@ int32_t pm_task_directory(pm_engine* e, const pm_tdir_query* q, pm_tdir_totals* 
   if (!n) return PM_OK;
   a.offset = q->offset, a.n_rows = n, a.total = n_listed;
   const uint32_t* list = nullptr;
-  if (q->order == PM_TDIR_BY_LIST || q->order == PM_TDIR_BY_OLDEST) {
-    HIPCHK(d.win.ensure(n));
-    a.win = d.win.p;
-    launch_tdir_window(a, e->stream);
-    list = d.win.p;
-  } else {
-    const uint32_t chunks = (n_listed + PM_RO_CHUNK - 1u) / PM_RO_CHUNK;
-    for (int b = 0; b < 2; ++b) {
-      HIPCHK(d.key[b].ensure(n_listed));
-      HIPCHK(d.val[b].ensure(n_listed));
-    }
-    HIPCHK(d.hist.ensure(256 * size_t(chunks)));
-    HIPCHK(d.hist_scan.ensure(256 * size_t(chunks) + 1));
-    a.key = d.key[0].p;
-    a.val = d.val[0].p;
-    launch_tdir_keys(a, e->stream);
-    uint32_t cur = 0;
-    for (uint32_t p = 0; p < 4u; ++p, cur ^= 1u)  // the four bytes of UINT32_MAX - value: ending in buffer 0
-      launch_ro_radix_pass(d.key[cur].p, d.val[cur].p, n_listed, 8u * p, d.hist.p, d.hist_scan.p, d.key[cur ^ 1u].p,
-                           d.val[cur ^ 1u].p, e->stream);
-    list = d.val[cur].p + q->offset;
-  }
+  // BY_LIST and BY_OLDEST are scan order; the _DESC orders: the four bytes of UINT32_MAX - value
+  const uint32_t passes = q->order == PM_TDIR_BY_LIST || q->order == PM_TDIR_BY_OLDEST ? 0u : 4u;
+  const hipStream_t s = e->stream;  // (the callables capture the arguments, the stream and the index space, by value but for a)
+  rc = page_list(
+      d.pg, n_listed, q->offset, n, passes, s, [&a, s, R](uint32_t* win) { a.win = win, launch_list_window(a, R, s); },
+      [&a, s](uint64_t* key, uint32_t* val) { a.key = key, a.val = val, launch_tdir_keys(a, s); }, &list);
+  if (rc) return rc;
   HIPCHK(d.rows.ensure(n));
   HIPCHK(d.handles.ensure(n));
   d.h_rows.resize(n);

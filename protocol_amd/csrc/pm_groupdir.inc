@@ -14,7 +14,8 @@
 // class-major: flag[c * G + k].  BY_SLOT and BY_SIZE_DESC have one class; BY_ID_TEXT has sixteen, the id's hex digits L.  ONE
 // exclusive scan over the flags gives every listed entry its place in (class, slot) order and the total behind the last flag.
 //
-// ORDER.  BY_SLOT: the scan is the order; the entries whose place falls in the window write their index.  BY_ID_TEXT: the text
+// ORDER.  BY_SLOT: the scan is the order; the entries whose place falls in the window write their index (list_window_kernel of
+// pm_directory.inc over list_place below).  BY_ID_TEXT: the text
 // order of format!("{:x}", id) is (A, L) ascending, A = id << 4 (16 - L) (DESIGN 4.x has the proof).  The entries stand in
 // (L, slot) order behind the compaction; eight stable radix passes over A (launch_ro_radix_pass: fixed chunks, ties keep
 // entry order) leave them in (A, L, slot) order.  A and L together are 68 bits; L never enters the key.  BY_SIZE_DESC: four
@@ -103,21 +104,17 @@ __global__ __launch_bounds__(256) void gdir_group_kernel(GdirArgs a) {
   if (tid < PM_GD_CENSUS && s_bin[tid]) atomicAdd(&a.census[tid], s_bin[tid]);
 }
 
-__global__ __launch_bounds__(256) void gdir_window_kernel(GdirArgs a) {
-  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-  if (k >= a.G) return;
+__device__ __forceinline__ uint32_t list_place(const GdirArgs& a, uint32_t k) {
+  if (k >= a.G) return PM_NONE;
   const uint32_t cls = a.cls[k];
-  if (cls >= a.n_cls) return;
-  const uint32_t at = a.off[(size_t)cls * a.G + k];
-  if (at >= a.offset && at - a.offset < a.n_rows) a.win[at - a.offset] = k;
+  return cls < a.n_cls ? a.off[(size_t)cls * a.G + k] : PM_NONE;
 }
 
 __global__ __launch_bounds__(256) void gdir_keys_kernel(GdirArgs a) {
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-  if (k >= a.G) return;
+  const uint32_t at = list_place(a, k);
+  if (at == PM_NONE) return;
   const uint32_t cls = a.cls[k];
-  if (cls >= a.n_cls) return;
-  const uint32_t at = a.off[(size_t)cls * a.G + k];
   const RoGroup gr = a.g[k];
   // BY_ID_TEXT: the id's digits pushed to the top (L = cls + 1 of them; 0 stays 0).  BY_SIZE_DESC: largest first.
   a.key[at] = a.order == PM_GDIR_BY_ID_TEXT ? gr.id << (4u * (PM_GD_TEXT_CLASSES - 1u - cls)) : (uint64_t)(0xFFFFFFFFu - gr.size);
@@ -160,10 +157,8 @@ void launch_gdir_groups(const GdirArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(gdir_group_kernel, dim3((a.G + 255u) / 256u), dim3(256), 0, s, a);
 }
 
-void launch_gdir_window(const GdirArgs& a, hipStream_t s) {
-  if (!a.G || !a.n_rows) return;
-  hipLaunchKernelGGL(gdir_window_kernel, dim3((a.G + 255u) / 256u), dim3(256), 0, s, a);
-}
+// (the template stands in pm_directory.inc, included in front of this file; it finds list_place above by its argument's type)
+template void launch_list_window<GdirArgs>(const GdirArgs&, uint32_t, hipStream_t);
 
 void launch_gdir_keys(const GdirArgs& a, hipStream_t s) {
   if (!a.G) return;

@@ -324,6 +324,12 @@ void launch_ro_radix_pass(const uint64_t* key_in, const uint32_t* val_in, uint32
                      val_out);
 }
 
+uint32_t launch_ro_radix_sort(const RoSortBufs& b, uint32_t N, uint32_t passes, uint32_t cur, hipStream_t s) {
+  for (uint32_t p = 0; p < passes; ++p, cur ^= 1u)
+    launch_ro_radix_pass(b.key[cur], b.val[cur], N, 8u * p, b.hist, b.hist_scan, b.key[cur ^ 1u], b.val[cur ^ 1u], s);
+  return cur;
+}
+
 void launch_ro_heads(const uint64_t* key, uint32_t N, uint32_t* head, hipStream_t s) {
   if (!N) return;
   hipLaunchKernelGGL(ro_heads_kernel, dim3((N + 255u) / 256u), dim3(256), 0, s, key, N, head);

@@ -19,7 +19,7 @@
 // global atomic a non-zero bin and workgroup — and the listing flag.  ONE exclusive scan over the flags gives every listed slot
 // its place in list order.
 //
-// ORDER.  BY_LIST: the scan is the order.  BY_OLDEST: place total - 1 - scan.  The _DESC orders: the listed slots compacted in
+// ORDER.  BY_LIST: the scan is the order.  BY_OLDEST: place total - 1 - scan (list_place; list_window_kernel of pm_directory.inc).  The _DESC orders: the listed slots compacted in
 // list order, four stable radix passes over UINT32_MAX - value (launch_ro_radix_pass: ties keep list order).
 //
 // EMIT.  One thread per window slot: the position from the live prefix, the columns, the classes, one 88-byte row written whole.
@@ -173,18 +173,15 @@ __global__ __launch_bounds__(256) void tdir_task_kernel(TdirArgs a) {
   if (tid < TD_C_ORPHAN_UIDS && s_bin[tid]) atomicAdd(&a.census[tid], s_bin[tid]);  // (the orphans are the join's)
 }
 
-__global__ __launch_bounds__(256) void tdir_window_kernel(TdirArgs a) {
-  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= a.t_cap - a.t_lo || !a.flag[r]) return;
-  const uint32_t at = a.order == PM_TDIR_BY_OLDEST ? a.total - 1u - a.off[r] : a.off[r];
-  if (at >= a.offset && at - a.offset < a.n_rows) a.win[at - a.offset] = r;
+__device__ __forceinline__ uint32_t list_place(const TdirArgs& a, uint32_t r) {
+  if (r >= a.t_cap - a.t_lo || !a.flag[r]) return PM_NONE;
+  return a.order == PM_TDIR_BY_OLDEST ? a.total - 1u - a.off[r] : a.off[r];
 }
 
 __global__ __launch_bounds__(256) void tdir_keys_kernel(TdirArgs a) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-  if (r >= a.t_cap - a.t_lo || !a.flag[r]) return;
-  const uint32_t at = a.off[r];
-  if (at >= a.total) return;
+  const uint32_t at = list_place(a, r);
+  if (at >= a.total) return;  // (PM_NONE too)
   const uint32_t* c = a.cnt + (size_t)r * PM_TD_CNT;
   uint32_t v = c[TD_WORKERS];
   if (a.order == PM_TDIR_BY_REPORTERS_DESC) {
@@ -241,10 +238,8 @@ void launch_tdir_tasks(const TdirArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(tdir_task_kernel, dim3((a.t_cap - a.t_lo + 255u) / 256u), dim3(256), 0, s, a);
 }
 
-void launch_tdir_window(const TdirArgs& a, hipStream_t s) {
-  if (a.t_cap <= a.t_lo || !a.n_rows) return;
-  hipLaunchKernelGGL(tdir_window_kernel, dim3((a.t_cap - a.t_lo + 255u) / 256u), dim3(256), 0, s, a);
-}
+// (the template stands in pm_directory.inc, included in front of this file; it finds list_place above by its argument's type)
+template void launch_list_window<TdirArgs>(const TdirArgs&, uint32_t, hipStream_t);
 
 void launch_tdir_keys(const TdirArgs& a, hipStream_t s) {
   if (a.t_cap <= a.t_lo || !a.total) return;

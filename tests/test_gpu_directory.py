@@ -239,6 +239,11 @@ def _plain(W, ranks=None, statuses=None, group_size=0):
     eng = E.Engine(group_id_seed=3)
     cfg_rows, alt_rows, _ = host.pack_configs([("any", 1, 8, None)])
     eng.set_configs(cfg_rows, alt_rows)
+    return _fill(eng, W, ranks, statuses, group_size)
+
+
+def _fill(eng, W, ranks=None, statuses=None, group_size=0):
+    """a table of W rows (the upload drops what the engine held), three tasks, groups over the first half, the statuses"""
     eng.upload_workers(_cols(W, ranks=ranks))
     eng.upload_tasks(np.full(3, 1, dtype=np.uint64), np.array([3, 2, 1], dtype=np.int64), np.array([11, 12, 13], dtype=np.uint64))
     if group_size:
@@ -281,6 +286,28 @@ def test_by_address_rank_edges(name):
     total, _, rows = _read(eng, M.query(order=M.BY_ADDRESS))
     keys = [(r[2], int(ranks[r[0]]), r[0]) for r in rows]
     assert total == W_SORT and keys == sorted(keys)
+    eng.close()
+
+
+def test_one_engine_across_index_space_sizes():
+    """One engine; the table 65 rows, then the smallest whose sort histogram takes two tiles of the scan, then 65 again, then the
+    smallest with two chunks (the sizes as tests/test_gpu_addresses.py takes them from the source).  At each size the sorted order,
+    whole and a window, and a page in scan order between them and the next size's.  The scratch keeps what the largest size
+    made it: a buffer sized for an earlier n, or the wrong result buffer behind the sort's five passes, is a list that is not
+    the model's."""
+    two_chunks, two_tiles = RO_CHUNK + 1, (SCAN_TILE // 256) * RO_CHUNK + 1
+    assert SCAN_TILE % 256 == 0 and 256 * -(-two_tiles // RO_CHUNK) > SCAN_TILE >= 256 * -(-(two_tiles - 1) // RO_CHUNK)
+    eng = E.Engine(group_id_seed=3)
+    cfg_rows, alt_rows, _ = host.pack_configs([("any", 1, 8, None)])
+    eng.set_configs(cfg_rows, alt_rows)
+    for step, W in enumerate((65, two_tiles, 65, two_chunks)):
+        rng = np.random.default_rng(40 + step)
+        ranks = rng.integers(0, 1 << 32, W, dtype=np.uint64).astype(np.uint32)
+        _fill(eng, W, ranks, rng.integers(0, M.NS_N, W), group_size=3)
+        qs = [M.query(order=M.BY_ADDRESS), M.query(order=M.BY_ROW, offset=W // 2, limit=40),
+              M.query(order=M.BY_ADDRESS, status_mask=M.NOT_DEAD, offset=W // 3, limit=40), M.query(order=M.BY_ROW)]
+        state = _check(eng, ranks.tolist(), [11, 12, 13], qs, (step, W))
+        assert len(state[0]) == W and len(set(state[0])) == M.NS_N
     eng.close()
 
 

@@ -122,6 +122,11 @@ def _engine(W, groups, n_cfgs=1, ranks=None, statuses=None, reports=None, live=T
     eng = E.Engine(group_id_seed=seed)
     cfg_rows, alt_rows, _ = host.pack_configs([(f"c{k}", 1, 4096, None) for k in range(n_cfgs)])
     eng.set_configs(cfg_rows, alt_rows)
+    return _fill(eng, W, groups, ranks, statuses, reports, live, ro, tasks)
+
+
+def _fill(eng, W, groups, ranks=None, statuses=None, reports=None, live=True, ro=True, tasks=TASKS):
+    """a table of W rows (the upload drops what the engine held), the tasks, exactly `groups`, fresh ledgers"""
     eng.upload_workers(_cols(W, ranks=ranks))
     T = len(tasks)
     eng.upload_tasks(np.full(T, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64), np.arange(T, 0, -1).astype(np.int64), np.array(tasks, dtype=np.uint64))
@@ -280,6 +285,28 @@ def test_sorted_orders_at_the_chunk_edges(G):
     texts = [format(r[0], "x") for r in got[0][2]]
     assert len(texts) == G and texts == sorted(texts)
     assert [(-r[3], r[1]) for r in got[1][2]] == sorted((-r[3], r[1]) for r in got[1][2])
+    eng.close()
+
+
+def test_one_engine_across_index_space_sizes():
+    """One engine; the list 65 groups, then the smallest whose sort histogram takes two tiles of the scan, then 65 again, then
+    the smallest with two chunks (the sizes as tests/test_gpu_addresses.py takes them from the source).  At each size both sorted
+    orders and a page in scan order between them and the next size's.  The scratch keeps what the largest size made it: a buffer
+    sized for an earlier n, or the wrong result buffer behind the passes, is a list that is not the model's."""
+    two_chunks, two_tiles = RO_CHUNK + 1, (SCAN_TILE // 256) * RO_CHUNK + 1
+    assert SCAN_TILE % 256 == 0 and 256 * -(-two_tiles // RO_CHUNK) > SCAN_TILE >= 256 * -(-(two_tiles - 1) // RO_CHUNK)
+    eng = E.Engine(group_id_seed=3)
+    cfg_rows, alt_rows, _ = host.pack_configs([(f"c{k}", 1, 4096, None) for k in range(2)])
+    eng.set_configs(cfg_rows, alt_rows)
+    for step, G in enumerate((65, two_tiles, 65, two_chunks)):
+        rng = np.random.default_rng(40 + step)
+        groups, W = _even_groups(G, rng, 2, sizes=(1, 2, 1, 3))
+        _fill(eng, W, groups, None, *_random_ledgers(W, rng))
+        qs = [M.query(order=M.BY_ID_TEXT), M.query(order=M.BY_SLOT, offset=G // 2, limit=40),
+              M.query(order=M.BY_SIZE_DESC, offset=G // 3, limit=40), M.query(order=M.BY_SLOT, health_mask=LOST_OR_DEGRADED)]
+        _, got = _check(eng, range(W), TASKS, qs, (step, G))
+        texts = [format(r[0], "x") for r in got[0][2]]
+        assert len(texts) == G and texts == sorted(texts)
     eng.close()
 
 

@@ -142,6 +142,11 @@ def _engine(W, tasks, groups, n_cfgs=1, reports=None, ro=True, seed=3):
     eng = E.Engine(group_id_seed=seed)
     cfg_rows, alt_rows, _ = host.pack_configs([(f"c{k}", 1, 4096, None) for k in range(n_cfgs)])
     eng.set_configs(cfg_rows, alt_rows)
+    return _fill(eng, W, tasks, groups, reports, ro)
+
+
+def _fill(eng, W, tasks, groups, reports=None, ro=True):
+    """a table of W rows (the upload drops what the engine held), exactly `tasks` and `groups`, a fresh ledger"""
     eng.upload_workers(_cols(W))
     eng.upload_tasks(*_soa(tasks))
     g = np.zeros(len(groups), dtype=E.group_dt)
@@ -280,6 +285,28 @@ def test_tombstones_in_the_window():
     eng.rollout_ingest(_reports([(w, M.TS_RUNNING, 900_003) for w in range(590, 600)]))
     _, got = _check(eng, tasks, qs, "reports for a new task")
     assert got[0][2][3][9][M.TS_RUNNING] == 10
+    eng.close()
+
+
+def test_one_engine_across_index_space_sizes():
+    """One engine; the table 65 tasks, then the smallest whose sort histogram takes two tiles of the scan, then 65 again, then
+    the smallest with two chunks (the sizes as tests/test_gpu_addresses.py takes them from the source).  At each size both sorted
+    orders — behind the id join's own sort of the live rows — and a page in scan order between them and the next size's.  The
+    scratch keeps what the largest size made it: a buffer sized for an earlier n, or the wrong result buffer behind the passes,
+    is a list that is not the model's."""
+    two_chunks, two_tiles = RO_CHUNK + 1, (SCAN_TILE // 256) * RO_CHUNK + 1
+    assert SCAN_TILE % 256 == 0 and 256 * -(-two_tiles // RO_CHUNK) > SCAN_TILE >= 256 * -(-(two_tiles - 1) // RO_CHUNK)
+    eng = E.Engine(group_id_seed=3)
+    cfg_rows, alt_rows, _ = host.pack_configs([(f"c{k}", 1, 4096, None) for k in range(3)])
+    eng.set_configs(cfg_rows, alt_rows)
+    for step, T in enumerate((65, two_tiles, 65, two_chunks)):
+        rng = np.random.default_rng(40 + step)
+        tasks, groups, reports = _table(T, rng)
+        _fill(eng, 600, tasks, groups, reports)
+        qs = [M.query(order=M.BY_WORKERS_DESC), M.query(order=M.BY_LIST, offset=T // 2, limit=40),
+              M.query(order=M.BY_REPORTERS_DESC, offset=T // 3, limit=40), M.query(order=M.BY_OLDEST, offset=T // 2, limit=40)]
+        _, got = _check(eng, tasks, qs, (step, T))
+        assert got[0][0][1] == T and len(got[0][2]) == T
     eng.close()
 
 
