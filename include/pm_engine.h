@@ -1331,6 +1331,61 @@ int32_t pm_keccak256_many(pm_engine*, const uint8_t* bytes, const uint32_t* offs
 int32_t pm_invite_digests(pm_engine*, uint32_t domain_id, uint32_t pool_id, const uint32_t* rows, uint32_t n,
                           const uint8_t* nonce, const uint64_t* expiration_s, uint8_t* digest, uint8_t* signing_hash);
 
+/* ---- request gate (kernels in pm_secp256k1.inc) -----------------------------------------------------------------------------
+ * ValidateSignature (shared/src/security/auth_signature_middleware.rs:374-422) in front of /heartbeat and /storage, and the
+ * heartbeat handler's ban check (orchestrator/src/api/routes/heartbeat.rs:38-52), for a batch of requests: the EIP-191 hash of
+ * path + canonical JSON, the signer's address recovered from the 65-byte signature, the comparison with x-address, and the
+ * node's row and liveness status from the address book.  The verdict carries the row, so the beats can be folded into the
+ * liveness, metrics and rollout ledgers by row without a host-side address map.  Signing stays with the host: no private key
+ * reaches the device.  What follows in the middleware (:424-483: the rate limit, the request's age, the nonce) needs the clock
+ * and Redis and stays with the host, as does serialising the JSON.
+ *
+ * Recovery, by alloy's rules through k256 as INTEGRATION.md "Request gate" records them: sig65 = r | s | v with r and s
+ * big-endian; v 0 or 27 = R's y is even, 1 or 28 = odd, any other byte is no signature; 1 <= r < n and 1 <= s < n, else no
+ * key; R's x is r itself, never r + n; a high s is taken as it stands, which recovers the key of (r, n - s, the other parity);
+ * z = the 32-byte hash mod n; Q = r^-1 (s R - z G), and Q = infinity is no key; the address is the last 20 bytes of
+ * keccak-256(Qx | Qy), 64 big-endian bytes.
+ *
+ * pm_ecrecover_many    needs no book: entry i = hash32[32 i ..), sig65[65 i ..) -> ok_out[i] = 1 and addr20_out[20 i ..),
+ *                      pub64_out[64 i ..) (NULL: not wanted), or ok_out[i] = 0 and zeros.  PM_ESTATE only in the middle of a
+ *                      stepwise tick.
+ * pm_verify_requests   message i = bytes[offsets[i], offsets[i + 1]): path + payload string exactly as the middleware formats
+ *                      it; sig65 and claimed20 (x-address as bytes) per request; flags[i] & PM_RQ_FLAG_BAD_ADDRESS = the
+ *                      x-address text did not parse (flags NULL: none did not).  out[i].code is the FIRST of these that
+ *                      applies, in the middleware's order:
+ *                        PM_RQ_BAD_SIGNATURE  v is no recovery id                     (INVALID_SIGNATURE_FORMAT)
+ *                        PM_RQ_NO_KEY         nothing is recovered                    (ADDRESS_RECOVERY_FAILED)
+ *                        PM_RQ_BAD_ADDRESS    the flag — behind a failed recovery    (INVALID_ADDRESS_FORMAT)
+ *                        PM_RQ_MISMATCH       the recovered address is not claimed20
+ *                        PM_RQ_UNKNOWN        no row holds the address                (ADDRESS_NOT_AUTHORIZED)
+ *                        PM_RQ_EJECTED        the row is Ejected                      (ADDRESS_NOT_AUTHORIZED)
+ *                        PM_RQ_BANNED         passes the middleware; the handler's "Node is banned"
+ *                        PM_RQ_OK
+ *                      With liveness off EJECTED and BANNED are never given and status is 0xFF.  row: the LOWEST row that
+ *                      holds the recovered address (rows without an address hold none), from MISMATCH on when there is one,
+ *                      else 0xFFFFFFFF; address: the recovered one, zeros up to NO_KEY.  counts[c] = requests with code c,
+ *                      counted on the device.  The join is an index of the book's rows sorted by their 20 bytes, built by
+ *                      the first call that needs it and dropped by pm_addresses_set, pm_addresses_enable,
+ *                      pm_upload_workers with keep_groups = 0 and pm_append_workers.  PM_ESTATE: the book is off, no workers,
+ *                      or a stepwise tick is in progress.
+ * Both: PM_EINVAL for a NULL pointer with n > 0 or offsets that descend; n == 0 is a no-op; pure reads of the engine's tables
+ * (the cached index apart): no path of the tick changes. */
+enum { PM_RQ_BAD_SIGNATURE = 0, PM_RQ_NO_KEY = 1, PM_RQ_BAD_ADDRESS = 2, PM_RQ_MISMATCH = 3, PM_RQ_UNKNOWN = 4,
+       PM_RQ_EJECTED = 5, PM_RQ_BANNED = 6, PM_RQ_OK = 7, PM_RQ_N_CODES = 8 };
+#define PM_RQ_FLAG_BAD_ADDRESS 1u
+typedef struct pm_rq_verdict {
+  uint32_t code;        /* PM_RQ_* */
+  uint32_t row;         /* the node's row, or 0xFFFFFFFF */
+  uint8_t status;       /* the row's PM_NS_* status, or 0xFF: no row, or liveness is off */
+  uint8_t _pad[3];
+  uint8_t address[20];  /* the recovered address */
+} pm_rq_verdict;
+int32_t pm_ecrecover_many(pm_engine*, const uint8_t* hash32, const uint8_t* sig65, uint32_t n, uint8_t* addr20_out,
+                          uint8_t* pub64_out /* NULL ok */, uint8_t* ok_out);
+int32_t pm_verify_requests(pm_engine*, const uint8_t* bytes, const uint32_t* offsets, const uint8_t* sig65,
+                           const uint8_t* claimed20, const uint8_t* flags /* NULL = 0 */, uint32_t n, pm_rq_verdict* out,
+                           uint32_t* counts /* PM_RQ_N_CODES */);
+
 /* ------------------------------------------------------------------ host helpers (no GPU needed)
  * ComputeRequirements::from_str (shared/src/models/node.rs:180-374).  Fills cfg->flags/cpu/ram/
  * storage/alt_count (alt_begin, min/max sizes untouched) and up to alt_cap alternatives; model
@@ -1389,6 +1444,10 @@ int32_t pm_host_keccak256(const uint8_t* bytes, size_t len, uint8_t* out32);
 /* `Address: Display` (EIP-55): out43 = "0x", the 40 hex characters — letter i upper-case where nibble i of
  * keccak-256(the lower-case characters) is >= 8 — and a NUL.  What the address book computes on the device. */
 int32_t pm_host_eip55(const uint8_t* addr20, char* out43);
+/* One recovery on the host, by the rules of "request gate" above: hash32 [32], sig65 [65] -> addr20 [20].  PM_OK, or
+ * PM_EPARSE with addr20 zeroed where pm_ecrecover_many says ok = 0.  This project's plain C++, not k256: the mock engine's
+ * recovery, the tests' second opinion and the probe's CPU figure. */
+int32_t pm_host_ecrecover(const uint8_t* hash32, const uint8_t* sig65, uint8_t* addr20);
 
 uint32_t pm_abi_version(void);
 

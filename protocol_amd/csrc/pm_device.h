@@ -720,6 +720,17 @@ void launch_ab_rank(const uint32_t* val, uint32_t W, uint32_t* rank, hipStream_t
 // digest / signing [4 k, 4 k + 4): the invite digest of row rows[k] and its EIP-191 signing hash; nonce [4 n], expiration [n]
 void launch_invite_digests(const uint32_t* rows, uint32_t n, const uint32_t* bytes, uint32_t domain_id, uint32_t pool_id,
                            const uint64_t* nonce, const uint64_t* expiration, uint64_t* digest, uint64_t* signing, hipStream_t s);
+// request gate (pm_secp256k1.inc).  hash: 32 big-endian bytes an entry (aligned words), sig: 65 bytes an entry -> ok [n], addr
+// [5 n] the address's bytes as words, pub [8 n] (null: not wanted) Qx | Qy as the words that hold their big-endian bytes
+void launch_ecrecover(const uint64_t* hash, const uint8_t* sig, uint32_t n, uint32_t* addr, uint64_t* pub, uint8_t* ok, hipStream_t s);
+// out[4 i, 4 i + 4) = the EIP-191 hash of message bytes[off[i], off[i + 1]), as launch_keccak_many lays a digest out
+void launch_eip191_many(const uint8_t* bytes, const uint32_t* off, uint32_t n, uint64_t* out, hipStream_t s);
+// the book's rows sorted by their 20 bytes, equal ones by row, rows without an address last, into val [returned buffer]
+uint32_t launch_gate_index(const uint32_t* bytes, const uint8_t* set, uint32_t W, const RoSortBufs& b, hipStream_t s);
+// out [8 n]: pm_rq_verdict as words; counts [PM_RQ_N_CODES] += the census; status null: liveness is off
+void launch_gate_verdict(const uint32_t* addr, const uint8_t* ok, const uint8_t* sig, const uint32_t* claimed, const uint8_t* flags,
+                         uint32_t n, const uint32_t* idx, uint32_t n_idx, const uint32_t* book, const uint8_t* status, uint32_t* out,
+                         uint32_t* counts, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

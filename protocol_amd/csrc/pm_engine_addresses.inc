@@ -13,6 +13,7 @@ static void addresses_release(pm_engine* e) {
   AddressBook fresh;
   fresh.on = e->ab.on;
   fresh.shallow = e->ab.shallow, fresh.deep = e->ab.deep;
+  fresh.epoch = e->ab.epoch + 1;
   e->ab = std::move(fresh);
 }
 
@@ -33,6 +34,7 @@ static int32_t addresses_prepare(pm_engine* e) {
     HIPCHK(hipGetLastError());
     if (!keep) ab.h_set.clear(), ab.n_set = 0;
     ab.h_set.resize(W, 0);
+    ab.epoch++;
   }
   ab.W = W;
   ab.reinit = false;
@@ -91,6 +93,7 @@ int32_t pm_addresses_set(pm_engine* e, uint32_t first_row, const uint8_t* addr20
   HIPCHK(hipMemcpyAsync(ab.stage.p, addr20, 20 * size_t(n), hipMemcpyHostToDevice, e->stream));
   launch_ab_set(ab.stage.p, first_row, n, ab.bytes.p, ab.mask.p, ab.keys.p, ab.set.p, e->stream);
   HIPCHK(hipGetLastError());
+  ab.epoch++;
   for (uint32_t k = 0; k < n; ++k) {
     ab.n_set += ab.h_set[first_row + k] ? 0u : 1u;
     ab.h_set[first_row + k] = 1;

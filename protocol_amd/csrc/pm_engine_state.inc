@@ -156,6 +156,7 @@ struct AddressBook {
   bool on = false;
   bool reinit = false;        // an upload dropped the row identities: every flag is cleared by the next book call
   uint32_t W = 0, n_set = 0;  // rows covered; rows of them that hold an address
+  uint64_t epoch = 0;         // grows whenever a row's address, or the rows themselves, may have changed: what the request gate's index is built against
   uint64_t shallow = 0, deep = 0;  // ranks that ended on the one-word / the all-words sort, since creation (pm_debug_carve_prof 98, 99)
   DevBuf<uint32_t> bytes;     // [5 W]
   DevBuf<uint64_t> mask;      // [W]
@@ -168,6 +169,25 @@ struct AddressBook {
   DevBuf<uint8_t> text;       // rendered texts; pm_keccak256_many's messages
   DevBuf<uint64_t> in64, out64;  // nonces and expirations; digests
   PinBuf<uint32_t> h_pin;     // [0] the ties
+};
+
+// ---- request gate (pm_engine_gate.inc): the index of the address book's rows by their 20 bytes — built by the first
+// pm_verify_requests that needs it and again whenever the book's epoch has moved — and the scratch of one call
+struct Gate {
+  bool valid = false;         // sort.val[cur][0, n_idx) is the index of the book at `epoch` with W rows
+  uint32_t cur = 0, n_idx = 0, W = 0;
+  uint64_t epoch = 0;
+  uint64_t builds = 0;        // indexes built since creation
+  KeySort sort;               // the index: three-word keys, rows
+  DevBuf<uint8_t> text;       // the requests' messages
+  DevBuf<uint32_t> off;       // their offsets
+  DevBuf<uint64_t> hash;      // [4 n] the hashes: pm_ecrecover_many's input, the EIP-191 kernel's output
+  DevBuf<uint8_t> sig;        // [65 n]
+  DevBuf<uint32_t> addr;      // [5 n] recovered
+  DevBuf<uint64_t> pub;       // [8 n]
+  DevBuf<uint8_t> ok, flags;  // [n]
+  DevBuf<uint32_t> claimed;   // [5 n]
+  DevBuf<uint32_t> out;       // [8 n] the verdicts, behind them [PM_RQ_N_CODES] the census
 };
 
 struct pm_engine {
@@ -409,4 +429,5 @@ struct pm_engine {
   GroupDir gdir;  // (the same)
   TaskDir tdir;   // (the same)
   AddressBook ab;
+  Gate gate;      // (the book's index and scratch: never switched)
 };

@@ -547,6 +547,194 @@ int32_t pm_host_eip55(const uint8_t* addr20, char* out43) {
   return PM_OK;
 }
 
+}  // extern "C"
+
+// secp256k1 public-key recovery on the host, with the numbers as arrays of four 64-bit limbs (least significant first), the
+// steps as loops over them and one reduction for both moduli: written apart from the device's named-limb arithmetic
+// (pm_secp256k1.inc) on purpose, so that either checks the other.  Public data: nothing here is constant time.
+namespace {
+
+typedef unsigned __int128 u128;
+struct U256 {
+  uint64_t w[4];
+};
+// a modulus m > 2^255 as its limbs and c = 2^256 - m (three limbs at the most)
+struct Modulus {
+  U256 m;
+  uint64_t c[3];
+};
+const Modulus FP = {{{0xFFFFFFFEFFFFFC2Full, 0xFFFFFFFFFFFFFFFFull, 0xFFFFFFFFFFFFFFFFull, 0xFFFFFFFFFFFFFFFFull}}, {0x1000003D1ull, 0, 0}};
+const Modulus FN = {{{0xBFD25E8CD0364141ull, 0xBAAEDCE6AF48A03Bull, 0xFFFFFFFFFFFFFFFEull, 0xFFFFFFFFFFFFFFFFull}},
+                    {0x402DA1732FC9BEBFull, 0x4551231950B75FC4ull, 1}};
+const U256 SECP_GX = {{0x59F2815B16F81798ull, 0x029BFCDB2DCE28D9ull, 0x55A06295CE870B07ull, 0x79BE667EF9DCBBACull}};
+const U256 SECP_GY = {{0x9C47D08FFB10D4B8ull, 0xFD17B448A6855419ull, 0x5DA4FBFC0E1108A8ull, 0x483ADA7726A3C465ull}};
+
+bool u_is_zero(const U256& a) { return !(a.w[0] | a.w[1] | a.w[2] | a.w[3]); }
+bool u_eq(const U256& a, const U256& b) { return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && a.w[3] == b.w[3]; }
+bool u_less(const U256& a, const U256& b) {
+  for (int i = 3; i >= 0; --i)
+    if (a.w[i] != b.w[i]) return a.w[i] < b.w[i];
+  return false;
+}
+uint64_t u_add(U256& r, const U256& a, const U256& b) {
+  u128 t = 0;
+  for (int i = 0; i < 4; ++i) t += u128(a.w[i]) + b.w[i], r.w[i] = uint64_t(t), t >>= 64;
+  return uint64_t(t);
+}
+uint64_t u_sub(U256& r, const U256& a, const U256& b) {
+  uint64_t borrow = 0;
+  for (int i = 0; i < 4; ++i) {
+    const u128 t = u128(a.w[i]) - b.w[i] - borrow;
+    r.w[i] = uint64_t(t), borrow = uint64_t(t >> 64) & 1u;
+  }
+  return borrow;
+}
+U256 m_add(const U256& a, const U256& b, const Modulus& M) {
+  U256 r, t;
+  const uint64_t carry = u_add(r, a, b);
+  if (carry || !u_less(r, M.m)) u_sub(t, r, M.m), r = t;
+  return r;
+}
+U256 m_sub(const U256& a, const U256& b, const Modulus& M) {
+  U256 r, t;
+  if (u_sub(r, a, b)) u_add(t, r, M.m), r = t;
+  return r;
+}
+// a b mod m: the 512-bit product, then high half times c folded into the low half until nothing is left above 2^256
+U256 m_mul(const U256& a, const U256& b, const Modulus& M) {
+  uint64_t t[8] = {};
+  for (int i = 0; i < 4; ++i) {
+    u128 carry = 0;
+    for (int j = 0; j < 4; ++j) carry += u128(a.w[i]) * b.w[j] + t[i + j], t[i + j] = uint64_t(carry), carry >>= 64;
+    t[i + 4] = uint64_t(carry);
+  }
+  while (t[4] | t[5] | t[6] | t[7]) {
+    uint64_t f[8] = {t[0], t[1], t[2], t[3], 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) {
+      u128 carry = 0;
+      for (int j = 0; j < 3; ++j) carry += u128(t[4 + i]) * M.c[j] + f[i + j], f[i + j] = uint64_t(carry), carry >>= 64;
+      for (int k = i + 3; carry && k < 8; ++k) carry += f[k], f[k] = uint64_t(carry), carry >>= 64;
+    }
+    std::memcpy(t, f, sizeof t);
+  }
+  U256 r = {{t[0], t[1], t[2], t[3]}}, d;
+  while (!u_less(r, M.m)) u_sub(d, r, M.m), r = d;
+  return r;
+}
+// a^e mod m, the exponent's bits from the top
+U256 m_pow(const U256& a, const U256& e, const Modulus& M) {
+  U256 r = {{1, 0, 0, 0}};
+  for (int i = 255; i >= 0; --i) {
+    r = m_mul(r, r, M);
+    if ((e.w[i >> 6] >> (i & 63)) & 1u) r = m_mul(r, a, M);
+  }
+  return r;
+}
+U256 m_inv(const U256& a, const Modulus& M) {  // Fermat: m is prime
+  U256 e, two = {{2, 0, 0, 0}};
+  u_sub(e, M.m, two);
+  return m_pow(a, e, M);
+}
+U256 from_be(const uint8_t* p) {
+  U256 r;
+  for (int i = 0; i < 4; ++i) {
+    uint64_t v = 0;
+    for (int j = 0; j < 8; ++j) v = (v << 8) | p[8 * (3 - i) + j];
+    r.w[i] = v;
+  }
+  return r;
+}
+void to_be(const U256& a, uint8_t* p) {
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 8; ++j) p[8 * (3 - i) + j] = uint8_t(a.w[i] >> (8 * (7 - j)));
+}
+
+// a point in Jacobian coordinates (x = X / Z^2, y = Y / Z^3); Z = 0 is infinity
+struct Jac {
+  U256 x, y, z;
+};
+Jac j_infinity() { return Jac{{{1, 0, 0, 0}}, {{1, 0, 0, 0}}, {{0, 0, 0, 0}}}; }
+Jac j_double(const Jac& p) {
+  if (u_is_zero(p.z)) return p;
+  const U256 a = m_mul(p.x, p.x, FP), b = m_mul(p.y, p.y, FP), c = m_mul(b, b, FP);
+  U256 d = m_add(p.x, b, FP);
+  d = m_sub(m_sub(m_mul(d, d, FP), a, FP), c, FP);
+  d = m_add(d, d, FP);
+  const U256 e = m_add(m_add(a, a, FP), a, FP), f = m_mul(e, e, FP);
+  Jac r;
+  r.x = m_sub(f, m_add(d, d, FP), FP);
+  U256 c8 = m_add(c, c, FP);
+  c8 = m_add(c8, c8, FP), c8 = m_add(c8, c8, FP);
+  r.y = m_sub(m_mul(e, m_sub(d, r.x, FP), FP), c8, FP);
+  r.z = m_mul(p.y, p.z, FP);
+  r.z = m_add(r.z, r.z, FP);
+  return r;
+}
+// p + (qx, qy), the second one affine and not infinity
+Jac j_add_affine(const Jac& p, const U256& qx, const U256& qy) {
+  if (u_is_zero(p.z)) return Jac{qx, qy, {{1, 0, 0, 0}}};
+  const U256 zz = m_mul(p.z, p.z, FP), u2 = m_mul(qx, zz, FP), s2 = m_mul(qy, m_mul(p.z, zz, FP), FP);
+  const U256 h = m_sub(u2, p.x, FP), rr = m_sub(s2, p.y, FP);
+  if (u_is_zero(h)) return u_is_zero(rr) ? j_double(p) : j_infinity();  // equal points; opposite points
+  const U256 hh = m_mul(h, h, FP), hhh = m_mul(h, hh, FP), v = m_mul(p.x, hh, FP);
+  Jac r;
+  r.x = m_sub(m_sub(m_mul(rr, rr, FP), hhh, FP), m_add(v, v, FP), FP);
+  r.y = m_sub(m_mul(rr, m_sub(v, r.x, FP), FP), m_mul(p.y, hhh, FP), FP);
+  r.z = m_mul(p.z, h, FP);
+  return r;
+}
+// k (px, py) by double-and-add from the top bit
+Jac j_mul(const U256& k, const U256& px, const U256& py) {
+  Jac r = j_infinity();
+  for (int i = 255; i >= 0; --i) {
+    r = j_double(r);
+    if ((k.w[i >> 6] >> (i & 63)) & 1u) r = j_add_affine(r, px, py);
+  }
+  return r;
+}
+bool j_affine(const Jac& p, U256& x, U256& y) {
+  if (u_is_zero(p.z)) return false;
+  const U256 zi = m_inv(p.z, FP), zi2 = m_mul(zi, zi, FP);
+  x = m_mul(p.x, zi2, FP);
+  y = m_mul(p.y, m_mul(zi, zi2, FP), FP);
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Q = r^-1 (s R - z G) as two products and one addition (the device interleaves them: pm_secp256k1.inc)
+int32_t pm_host_ecrecover(const uint8_t* hash32, const uint8_t* sig65, uint8_t* addr20) {
+  if (!hash32 || !sig65 || !addr20) return pm::set_error(PM_EINVAL, "null argument");
+  std::memset(addr20, 0, 20);
+  const uint8_t v = sig65[64];
+  if (v != 0 && v != 1 && v != 27 && v != 28) return pm::set_error(PM_EPARSE, "not a recovery id");
+  const unsigned parity = (v == 1 || v == 28) ? 1u : 0u;  // (0, 27: even; 1, 28: odd)
+  const U256 r = from_be(sig65), s = from_be(sig65 + 32);
+  if (u_is_zero(r) || u_is_zero(s) || !u_less(r, FN.m) || !u_less(s, FN.m)) return pm::set_error(PM_EPARSE, "r or s out of range");
+  // R: x = r itself, y = (x^3 + 7)^((p + 1) / 4) if that is a root
+  const U256 seven = {{7, 0, 0, 0}};
+  const U256 rhs = m_add(m_mul(m_mul(r, r, FP), r, FP), seven, FP);
+  const U256 exp = {{0xFFFFFFFFBFFFFF0Cull, 0xFFFFFFFFFFFFFFFFull, 0xFFFFFFFFFFFFFFFFull, 0x3FFFFFFFFFFFFFFFull}};
+  U256 y = m_pow(rhs, exp, FP);
+  if (!u_eq(m_mul(y, y, FP), rhs)) return pm::set_error(PM_EPARSE, "r is no x coordinate");
+  if ((y.w[0] & 1u) != parity) y = m_sub(U256{{0, 0, 0, 0}}, y, FP);
+  U256 z = from_be(hash32), t;
+  if (!u_less(z, FN.m)) u_sub(t, z, FN.m), z = t;
+  const U256 ri = m_inv(r, FN), u1 = m_mul(m_sub(U256{{0, 0, 0, 0}}, z, FN), ri, FN), u2 = m_mul(s, ri, FN);
+  Jac q = j_mul(u2, r, y);
+  U256 ax, ay;
+  if (j_affine(j_mul(u1, SECP_GX, SECP_GY), ax, ay)) q = j_add_affine(q, ax, ay);
+  U256 qx, qy;
+  if (!j_affine(q, qx, qy)) return pm::set_error(PM_EPARSE, "the key is the point at infinity");
+  uint8_t pub[64], digest[32];
+  to_be(qx, pub), to_be(qy, pub + 32);
+  pm_host_keccak256(pub, 64, digest);
+  std::memcpy(addr20, digest + 12, 20);
+  return PM_OK;
+}
+
 uint32_t pm_abi_version(void) { return PM_ABI_VERSION; }
 
 }  // extern "C"

@@ -238,6 +238,7 @@ EXPORTS = [
     "pm_group_directory",
     "pm_task_directory",
     "pm_addresses_enable", "pm_addresses_set", "pm_addresses_rank", "pm_addresses_text", "pm_invite_digests",
+    "pm_ecrecover_many", "pm_verify_requests", "pm_host_ecrecover",
 ]
 # ... and the declared names that carry a digit, which the header check's name pattern (letters and '_') does not take in
 EXPORTS_NUMBERED = ["pm_keccak256_many", "pm_host_keccak256", "pm_host_eip55"]
@@ -357,6 +358,9 @@ def lib() -> C.CDLL:
         L.pm_addresses_rank.argtypes = [vp, vp]
         L.pm_addresses_text.argtypes = [vp, vp, u32, vp]
         L.pm_invite_digests.argtypes = [vp, u32, u32, vp, u32, vp, vp, vp, vp]
+        L.pm_ecrecover_many.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+        L.pm_verify_requests.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.pm_host_ecrecover.argtypes = [vp, vp, vp]
         # (bound where the library has them: a test library that stubs EXPORTS alone lacks them, and a call then fails by name)
         numbered = {"pm_keccak256_many": [vp, vp, vp, u32, vp], "pm_host_keccak256": [vp, sz, vp], "pm_host_eip55": [vp, vp]}
         for name in EXPORTS_NUMBERED:
@@ -406,6 +410,24 @@ def host_eip55(addr20: bytes) -> str:
     check(lib().pm_host_eip55(buf.ctypes.data, out.ctypes.data))
     return out[:42].tobytes().decode("ascii")
 
+
+def host_ecrecover(hash32: bytes, sig65: bytes):
+    """pm_host_ecrecover: the signer's 20 bytes, or None where nothing is recovered"""
+    h, g = np.frombuffer(bytes(hash32), dtype=np.uint8), np.frombuffer(bytes(sig65), dtype=np.uint8)
+    assert len(h) == 32 and len(g) == 65
+    out = np.zeros(20, dtype=np.uint8)
+    rc = lib().pm_host_ecrecover(h.ctypes.data, g.ctypes.data, out.ctypes.data)
+    if rc == PM_EPARSE:
+        return None
+    check(rc)
+    return out.tobytes()
+
+
+# pm_rq_verdict, and the codes in the middleware's order
+RQ_VERDICT = np.dtype([("code", np.uint32), ("row", np.uint32), ("status", np.uint8), ("_pad", np.uint8, (3,)), ("address", np.uint8, (20,))])
+assert RQ_VERDICT.itemsize == 32
+RQ_BAD_SIGNATURE, RQ_NO_KEY, RQ_BAD_ADDRESS, RQ_MISMATCH, RQ_UNKNOWN, RQ_EJECTED, RQ_BANNED, RQ_OK, RQ_N_CODES = range(9)
+RQ_FLAG_BAD_ADDRESS = 1
 
 TICK_MANY_THREADS = 1
 
@@ -1168,6 +1190,30 @@ class Engine:
         check(lib().pm_invite_digests(self._h, domain_id, pool_id, rows.ctypes.data if n else None, n,
                                       nonces.ctypes.data if n else None, exp.ctypes.data if n else None, d.ctypes.data, s.ctypes.data))
         return d[:n], s[:n]
+
+    # ---- request gate (include/pm_engine.h "request gate")
+    def ecrecover_many(self, hashes, sigs, want_pub: bool = False):
+        """pm_ecrecover_many: hashes uint8 [n, 32], sigs uint8 [n, 65] -> (ok uint8 [n], addresses uint8 [n, 20]) and, when asked,
+        the keys uint8 [n, 64]"""
+        h = _arr(hashes, np.uint8).reshape(-1, 32)
+        g = _arr(sigs, np.uint8).reshape(-1, 65)
+        n = len(h)
+        assert len(g) == n
+        ok, addr = np.zeros(max(n, 1), dtype=np.uint8), np.zeros((max(n, 1), 20), dtype=np.uint8)
+        pub = np.zeros((max(n, 1), 64), dtype=np.uint8) if want_pub else None
+        check(lib().pm_ecrecover_many(self._h, h.ctypes.data if n else None, g.ctypes.data if n else None, n, addr.ctypes.data,
+                                      pub.ctypes.data if want_pub else None, ok.ctypes.data))
+        return (ok[:n], addr[:n], pub[:n]) if want_pub else (ok[:n], addr[:n])
+
+    def verify_requests(self, packed):
+        """pm_verify_requests: packed = protocol_amd.gate.pack_requests(...) -> (verdicts [n] of RQ_VERDICT, counts uint32 [RQ_N_CODES])"""
+        buf, off, sigs, claimed, flags = packed
+        n = len(off) - 1
+        out, counts = np.zeros(max(n, 1), dtype=RQ_VERDICT), np.zeros(RQ_N_CODES, dtype=np.uint32)
+        check(lib().pm_verify_requests(self._h, buf.ctypes.data if len(buf) else None, off.ctypes.data, sigs.ctypes.data if n else None,
+                                       claimed.ctypes.data if n else None, None if flags is None else flags.ctypes.data, n,
+                                       out.ctypes.data, counts.ctypes.data))
+        return out[:n], counts
 
     def debug_address_sorts(self) -> dict:
         """ranks the address book ended on its one-word / all-words sort since creation (pm_debug_carve_prof words 98, 99)"""

@@ -630,6 +630,29 @@ class GpuMatchPlugin : public SchedulerPlugin {
   std::vector<InviteDigest> invite_digests(uint32_t domain_id, uint32_t pool_id, const std::function<std::array<uint8_t, 32>()>& nonce,
                                            uint64_t expiration_s) const;
 
+  // ---- request gate (INTEGRATION.md "Request gate"; gpu_match_gate.cpp): pm_verify_requests.  ValidateSignature
+  // (auth_signature_middleware.rs:374-422) and the heartbeat handler's ban check (routes/heartbeat.rs:38-52) for a batch of
+  // requests in ONE engine call: `message` is path + payload string as the middleware formats it, `signature` and `address` the
+  // two header texts.  A signature text that is not an optional "0x" and 130 hex digits is PM_RQ_BAD_SIGNATURE (it travels with
+  // v = 0xFF, so the device's census counts it); an address text the book's parser refuses sets PM_RQ_FLAG_BAD_ADDRESS.  The
+  // verdict's row is the plugin's row: beat, report_task and beat_metrics can be fed from it.  The rate limit, the request's age
+  // and the nonce (:424-483) stay with the caller.  Needs enable_address_book: EngineError(PM_ESTATE) without.
+  struct GateRequest {
+    std::string message, signature, address;
+  };
+  struct GateVerdict {
+    uint32_t code = PM_RQ_BAD_SIGNATURE;
+    uint32_t row = 0xFFFFFFFFu;
+    uint8_t status = 0xFF;  // PM_NS_*, 0xFF: no row, or liveness is off
+    std::array<uint8_t, 20> address{};
+  };
+  struct GateResult {
+    std::vector<GateVerdict> verdicts;
+    std::array<uint32_t, PM_RQ_N_CODES> counts{};
+  };
+  GateResult verify_requests(const std::vector<GateRequest>& requests) const;
+  static bool parse_signature_text(const std::string& text, uint8_t out65[65]);
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());

@@ -253,6 +253,13 @@ int32_t pmx_enable_address_book(pmx_plugin*);
 int32_t pmx_invite_digests(pmx_plugin*, uint32_t domain_id, uint32_t pool_id, uint64_t nonce_seed, uint64_t expiration_s, char* out,
                            size_t cap, size_t* needed);
 
+/* ---- request gate (pm_plugin_gate_c.cpp): GpuMatchPlugin::verify_requests (needs pmx_enable_address_book).  requests: one line
+ * per request, "<signature text>\t<x-address text>\t<message>" (the message is path + payload string; it holds no line break in
+ * this face).  The text: per request "<code>\t<row or ->\t<status or ->\t0x<recovered address, 40 lower-case hex digits>", code
+ * one of bad_signature, no_key, bad_address, mismatch, unknown, ejected, banned, ok; then "counts" and the eight census words
+ * in that order. */
+int32_t pmx_verify_requests(pmx_plugin*, const char* requests, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

@@ -111,6 +111,26 @@ pub struct pm_task_soa {
 }
 
 /// include/pm_engine.h: one entry of the group life-cycle feed (kind 1 = created, 2 = destroyed)
+/// pm_verify_requests' answer for one request (include/pm_engine.h "request gate")
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct pm_rq_verdict {
+    pub code: u32,
+    pub row: u32,
+    pub status: u8,
+    pub _pad: [u8; 3],
+    pub address: [u8; 20],
+}
+pub const RQ_BAD_SIGNATURE: u32 = 0;
+pub const RQ_NO_KEY: u32 = 1;
+pub const RQ_BAD_ADDRESS: u32 = 2;
+pub const RQ_MISMATCH: u32 = 3;
+pub const RQ_UNKNOWN: u32 = 4;
+pub const RQ_EJECTED: u32 = 5;
+pub const RQ_BANNED: u32 = 6;
+pub const RQ_OK: u32 = 7;
+pub const RQ_N_CODES: usize = 8;
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct pm_group_event {
@@ -779,6 +799,12 @@ extern "C" {
                          expiration_s: *const u64, digest: *mut u8, signing_hash: *mut u8) -> i32;
     fn pm_host_keccak256(bytes: *const u8, len: usize, out32: *mut u8) -> i32;
     fn pm_host_eip55(addr20: *const u8, out43: *mut c_char) -> i32;
+    // request gate (include/pm_engine.h "request gate")
+    fn pm_ecrecover_many(e: *mut c_void, hash32: *const u8, sig65: *const u8, n: u32, addr20_out: *mut u8, pub64_out: *mut u8,
+                         ok_out: *mut u8) -> i32;
+    fn pm_verify_requests(e: *mut c_void, bytes: *const u8, offsets: *const u32, sig65: *const u8, claimed20: *const u8,
+                          flags: *const u8, n: u32, out: *mut pm_rq_verdict, counts: *mut u32) -> i32;
+    fn pm_host_ecrecover(hash32: *const u8, sig65: *const u8, addr20: *mut u8) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -1596,6 +1622,34 @@ impl GpuMatchPlugin {
             s.copy_from_slice(&signing[32 * k..32 * k + 32]);
             (t.address_strings[rows[k] as usize].clone(), nonces[k], d, s)
         }).collect())
+    }
+
+    /// ValidateSignature (auth_signature_middleware.rs:374-422) and the heartbeat handler's ban check (routes/heartbeat.rs:38-52)
+    /// for a batch of requests in ONE engine call: (message = path + payload string as the middleware formats it, the parsed
+    /// signature as its 65 bytes r | s | v, the parsed x-address).  alloy has parsed both headers before this is called, so no
+    /// flag is set here: INVALID_SIGNATURE_FORMAT and INVALID_ADDRESS_FORMAT of a header that does not parse are the caller's.
+    /// The verdict's row is the plugin's row: beat, report_task and beat_metrics can be fed from it.  The rate limit, the
+    /// request's age and the nonce (:424-483) stay with the caller.  Needs enable_address_book.
+    pub fn verify_requests(&self, requests: &[(&[u8], [u8; 65], Address)]) -> Result<(Vec<pm_rq_verdict>, [u32; RQ_N_CODES])> {
+        let t = self.nodes.read();
+        if !t.book_on { return Err(anyhow!("pm_engine error {PM_ESTATE}: the address book is off (enable_address_book)")); }
+        let n = requests.len();
+        let mut counts = [0u32; RQ_N_CODES];
+        if n == 0 { return Ok((Vec::new(), counts)); }
+        let (mut bytes, mut offsets) = (Vec::<u8>::new(), vec![0u32; n + 1]);
+        let (mut sig, mut claimed) = (Vec::<u8>::with_capacity(65 * n), Vec::<u8>::with_capacity(20 * n));
+        for (k, (message, signature, address)) in requests.iter().enumerate() {
+            bytes.extend_from_slice(message);
+            if bytes.len() > 0xFFFF_FF00 { return Err(anyhow!("pm_engine error {PM_ERANGE}: too many message bytes in one call")); }
+            offsets[k + 1] = bytes.len() as u32;
+            sig.extend_from_slice(signature);
+            let a: [u8; 20] = address.into_array();
+            claimed.extend_from_slice(&a);
+        }
+        let mut out = vec![pm_rq_verdict::default(); n];
+        check(unsafe { pm_verify_requests(self.engine, bytes.as_ptr(), offsets.as_ptr(), sig.as_ptr(), claimed.as_ptr(), std::ptr::null(),
+                                          n as u32, out.as_mut_ptr(), counts.as_mut_ptr()) })?;
+        Ok((out, counts))
     }
 
     /// rank of address.to_string() in byte order (BTreeSet<String>, mod.rs:424-434) among the first `known` rows:

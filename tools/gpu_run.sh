@@ -47,6 +47,9 @@
 #                            1 % appended a step — pm_addresses_set, pm_addresses_rank on both sort paths, a page of texts, the invite
 #                            digests — beside the set + rank pair what the plugin does today (an EIP-55 text per new address, the
 #                            sorted insert, the re-rank, pm_set_addr_ranks) -> r30_address_book.txt (copy it to profiles/)
+#   gate[:<args>]            tools/gate_probe.py [n ...] [--bench DIR]: pm_ecrecover_many and pm_verify_requests at 1,000, 10,000 and
+#                            100,000 requests over a book of 100,000 rows, the address index cold and warm, beside pm_host_ecrecover
+#                            on one host thread -> r32_request_gate.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -186,6 +189,9 @@ PY
     addresses)
       timeout -k 10 600 python tools/address_probe.py $arg --out "$out/r30_address_book.txt" > "$out/${n}_addresses.log" 2>&1; echo "addresses rc=$?"
       tail -40 "$out/${n}_addresses.log" ;;
+    gate)
+      timeout -k 10 500 python tools/gate_probe.py $arg --out "$out/r32_request_gate.txt" > "$out/${n}_gate.log" 2>&1; echo "gate rc=$?"
+      tail -30 "$out/${n}_gate.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
