@@ -1337,8 +1337,8 @@ int32_t pm_invite_digests(pm_engine*, uint32_t domain_id, uint32_t pool_id, cons
  * path + canonical JSON, the signer's address recovered from the 65-byte signature, the comparison with x-address, and the
  * node's row and liveness status from the address book.  The verdict carries the row, so the beats can be folded into the
  * liveness, metrics and rollout ledgers by row without a host-side address map.  Signing stays with the host: no private key
- * reaches the device.  What follows in the middleware (:424-483: the rate limit, the request's age, the nonce) needs the clock
- * and Redis and stays with the host, as does serialising the JSON.
+ * reaches the device.  What follows in the middleware (:424-483: the rate limit, the request's age, the nonce) is
+ * pm_admit_requests' ("request gate: admission" below); serialising the JSON stays with the host.
  *
  * Recovery, by alloy's rules through k256 as INTEGRATION.md "Request gate" records them: sig65 = r | s | v with r and s
  * big-endian; v 0 or 27 = R's y is even, 1 or 28 = odd, any other byte is no signature; 1 <= r < n and 1 <= s < n, else no
@@ -1385,6 +1385,73 @@ int32_t pm_ecrecover_many(pm_engine*, const uint8_t* hash32, const uint8_t* sig6
 int32_t pm_verify_requests(pm_engine*, const uint8_t* bytes, const uint32_t* offsets, const uint8_t* sig65,
                            const uint8_t* claimed20, const uint8_t* flags /* NULL = 0 */, uint32_t n, pm_rq_verdict* out,
                            uint32_t* counts /* PM_RQ_N_CODES */);
+
+/* ---- request gate: admission (kernels in pm_admission.inc) -------------------------------------------------------------------
+ * What the middleware does behind ADDRESS_NOT_AUTHORIZED (auth_signature_middleware.rs:424-483) and the heartbeat handler's
+ * stamp, with their state on the device beside the address book and the liveness ledger: the rate window per row (:142-157,
+ * :424-431: 100 requests per 60 s per address), the request's age (:433-447), the nonce's format (:135-140) and the replay set
+ * (:159-183, :449-483: Redis SET NX GET EX 60), and the beat column heartbeat_store.beat stamps and the liveness sweep reads.
+ * Signing stays with the host: no private key reaches the device.
+ *
+ * pm_admission_enable  off by default; on again starts all three ledgers over, on = 0 releases them.  Needs the address book
+ *                      (PM_ESTATE), not liveness (BANNED and EJECTED are then never given).
+ *   rate ledger        per worker row window_start_ms (u64) and count (u32); (0, 0) = no entry.
+ *   beat column        last_beat_ms per row, 0 = never.  Both: appended rows start empty; pm_upload_workers(keep_groups = 0)
+ *                      empties them (the row identities are gone), keep_groups = 1 and pm_append_workers keep them.
+ *   nonce set          global — it survives every worker upload: per entry the keccak-256 digest of the nonce's bytes and
+ *                      stored_ms.  Equal digests are taken as equal nonces.  A sorted array (by the digest's first 64 bits;
+ *                      equality is always decided on all 256), merged with each batch: results and ledgers are bit-identical
+ *                      from run to run.
+ * pm_admit_requests    pm_verify_requests' arguments and first stage (the same kernels, staging and index), then, as if the
+ *                      requests were handled one after another in batch order, all at now_ms, the FIRST of these that applies:
+ *                        codes 0 .. 5         BAD_SIGNATURE .. EJECTED as above; such a request touches nothing
+ *                        PM_RQ_RATE_LIMITED   the row has no entry, or now_ms - window_start_ms >= 60000 (now_ms below the
+ *                                             start counts as elapsed 0: duration_since saturates): the window becomes
+ *                                             (now_ms, 1).  Else count >= 100: refused, the entry stays.  Else count += 1.
+ *                                             The k-th request of a row sees what the earlier ones left: the first `room`
+ *                                             of a row pass.  A request refused further down has still used its slot.
+ *                        PM_RQ_EXPIRED        without PM_RQ_FLAG_NO_TIMESTAMP: now_ms / 1000 - timestamp_s[i] > 300 in WRAPPING
+ *                                             u64 arithmetic — a timestamp in the future expires, as in the reference's release
+ *                                             build (its workspace sets no overflow-checks)
+ *                        PM_RQ_NO_NONCE       PM_RQ_FLAG_NO_NONCE
+ *                        PM_RQ_BAD_NONCE      nonce i = nonce_bytes[nonce_offsets[i], nonce_offsets[i + 1]): not 16 .. 64 bytes
+ *                                             of ASCII letters, digits and '-'
+ *                        PM_RQ_REPLAY         a live entry holds the digest — or an earlier request of the batch that reached
+ *                                             this step; the entry's stored_ms is NOT refreshed (NX).  Otherwise the nonce is
+ *                                             stored at now_ms.  Live: now_ms < stored_ms or now_ms - stored_ms <=
+ *                                             PM_RQ_NONCE_TTL_MS (the liveness ledger's convention for Redis' edge
+ *                                             millisecond); entries that are not leave the set during the call.
+ *                        PM_RQ_BANNED, PM_RQ_OK   as above: a banned node's request has used its slot and its nonce (the
+ *                                             handler runs behind the middleware)
+ *                      An OK with PM_RQ_FLAG_BEAT sets last_beat_ms[row] = max(last_beat_ms[row], now_ms).  (In the numbering the
+ *                      new codes follow the gate's eight; in the precedence they stand between EJECTED and BANNED.)  row, status
+ *                      and address as pm_verify_requests fills them; counts [PM_AD_N_CODES] on the device.  Errors: those of
+ *                      pm_verify_requests; PM_ESTATE: admission is off; PM_EINVAL: nonce_offsets descend, or timestamp_s /
+ *                      nonce_bytes / nonce_offsets is NULL while a request lacks the matching flag.  A failing call changes no
+ *                      ledger; one synchronisation a call.
+ * pm_admission_rate_get / _set   rows idx[0, n): the windows (an index given twice takes its last entry); PM_ERANGE past W
+ * pm_admission_nonces  *n_live = entries live at now_ms, *n_held = entries held (counters only; nothing leaves the set)
+ * pm_beats_get / _set  the beat column, the same way
+ * pm_liveness_sweep_beats   pm_liveness_sweep in every respect, but a row's beat is the LATER of the device's column and
+ *                      last_beat_ms[w]; last_beat_ms NULL: the device's column alone, nothing of size W is uploaded.
+ *                      PM_ESTATE when admission is off. */
+enum { PM_RQ_RATE_LIMITED = 8, PM_RQ_EXPIRED = 9, PM_RQ_BAD_NONCE = 10, PM_RQ_REPLAY = 11, PM_RQ_NO_NONCE = 12, PM_AD_N_CODES = 13 };
+#define PM_RQ_FLAG_NO_TIMESTAMP 2u
+#define PM_RQ_FLAG_NO_NONCE 4u
+#define PM_RQ_FLAG_BEAT 8u
+#define PM_RQ_NONCE_TTL_MS 60000u
+int32_t pm_admission_enable(pm_engine*, uint32_t on);
+int32_t pm_admit_requests(pm_engine*, uint64_t now_ms, const uint8_t* bytes, const uint32_t* offsets, const uint8_t* sig65,
+                          const uint8_t* claimed20, const uint8_t* flags /* NULL = 0 */, const uint64_t* timestamp_s,
+                          const uint8_t* nonce_bytes, const uint32_t* nonce_offsets, uint32_t n, pm_rq_verdict* out,
+                          uint32_t* counts /* PM_AD_N_CODES */);
+int32_t pm_admission_rate_get(pm_engine*, const uint32_t* idx, uint32_t n, uint64_t* window_start_ms, uint32_t* count);
+int32_t pm_admission_rate_set(pm_engine*, const uint32_t* idx, const uint64_t* window_start_ms, const uint32_t* count, uint32_t n);
+int32_t pm_admission_nonces(pm_engine*, uint64_t now_ms, uint32_t* n_live, uint32_t* n_held);
+int32_t pm_beats_get(pm_engine*, const uint32_t* idx, uint32_t n, uint64_t* last_beat_ms);
+int32_t pm_beats_set(pm_engine*, const uint32_t* idx, const uint64_t* last_beat_ms, uint32_t n);
+int32_t pm_liveness_sweep_beats(pm_engine*, uint64_t now_ms, const uint64_t* last_beat_ms /* W, NULL ok */,
+                                const uint64_t* in_pool_bits, uint32_t apply, uint32_t* n_transitions, uint32_t* census);
 
 /* ------------------------------------------------------------------ host helpers (no GPU needed)
  * ComputeRequirements::from_str (shared/src/models/node.rs:180-374).  Fills cfg->flags/cpu/ram/

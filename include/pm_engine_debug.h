@@ -165,6 +165,12 @@ int32_t pm_debug_first_batch_get(pm_engine* e, uint32_t part, void* out, uint64_
  * returns all three to what they were before it was created (tests/test_gpu_lifetime.py). */
 void pm_debug_live_allocations(uint64_t out[3]);
 
+/* Test hook of the admission ledger's nonce set (pm_admission_enable): the standing array and each batch are sorted by the first
+ * k bits of a nonce's digest instead of the first 64, so that a handful of nonces makes long runs of equal keys — equality is
+ * still decided on all 256 bits over the run.  Not a call of its own: pm_admission_enable(e, PM_AD_DEBUG_PREFIX_BITS(k)) turns
+ * admission on with 1 <= k <= 64 (bits 8 .. 15 of `on`; 0 there, as in a plain on = 1, is 64).  PM_EINVAL above 64. */
+#define PM_AD_DEBUG_PREFIX_BITS(k) (1u | ((uint32_t)(k) << 8))
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,10 +14,10 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(HERE, "libpm_engine.so")
 SOURCES = ["pm_kernels.hip", "pm_engine.cpp", "pm_host.cpp"]
 HEADERS = ["pm_device.h", "pm_internal.h", "pm_members.h", "pm_owned.h", "pm_measure.inc", "pm_validate.inc", "pm_propose.inc",
-           "pm_prep.inc", "pm_carve_kernel.inc", "pm_stream.inc", "pm_report.inc", "pm_spread.inc", "pm_near.inc", "pm_probe.inc", "pm_changes.inc", "pm_liveness.inc", "pm_discovery.inc", "pm_metrics.inc", "pm_rollout.inc", "pm_directory.inc", "pm_groupdir.inc", "pm_taskdir.inc", "pm_keccak.inc", "pm_addresses.inc", "pm_secp256k1.inc", "pm_launch.inc",
+           "pm_prep.inc", "pm_carve_kernel.inc", "pm_stream.inc", "pm_report.inc", "pm_spread.inc", "pm_near.inc", "pm_probe.inc", "pm_changes.inc", "pm_liveness.inc", "pm_discovery.inc", "pm_metrics.inc", "pm_rollout.inc", "pm_directory.inc", "pm_groupdir.inc", "pm_taskdir.inc", "pm_keccak.inc", "pm_addresses.inc", "pm_secp256k1.inc", "pm_admission.inc", "pm_launch.inc",
            "pm_engine_types.inc", "pm_engine_state.inc", "pm_engine_groups.inc", "pm_engine_carve.inc", "pm_engine_match.inc",
            "pm_engine_merge.inc", "pm_engine_workers.inc", "pm_engine_tasks.inc", "pm_engine_api.inc", "pm_engine_adopt.inc",
-           "pm_engine_report.inc", "pm_engine_spread.inc", "pm_engine_near.inc", "pm_engine_probe.inc", "pm_engine_changes.inc", "pm_engine_liveness.inc", "pm_engine_discovery.inc", "pm_engine_metrics.inc", "pm_engine_rollout.inc", "pm_engine_directory.inc", "pm_engine_groupdir.inc", "pm_engine_taskdir.inc", "pm_engine_addresses.inc", "pm_engine_gate.inc",
+           "pm_engine_report.inc", "pm_engine_spread.inc", "pm_engine_near.inc", "pm_engine_probe.inc", "pm_engine_changes.inc", "pm_engine_liveness.inc", "pm_engine_discovery.inc", "pm_engine_metrics.inc", "pm_engine_rollout.inc", "pm_engine_directory.inc", "pm_engine_groupdir.inc", "pm_engine_taskdir.inc", "pm_engine_addresses.inc", "pm_engine_gate.inc", "pm_engine_admission.inc",
            "pm_engine_tick.inc",
            "pm_engine_dist.inc", "pm_engine_debug.inc", "pm_unicode_lower.inc"]
 
@@ -56,7 +56,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str | Non
 PLUGIN_DIR = os.path.join(HERE, "plugin")
 PLUGIN_LIB = os.path.join(HERE, "libpm_plugin.so")
 PLUGIN_SOURCES = ["gpu_match_plugin.cpp", "gpu_match_restore.cpp", "gpu_match_report.cpp", "gpu_match_spread.cpp", "gpu_match_near.cpp",
-                  "gpu_match_changes.cpp", "pm_plugin_changes_c.cpp", "gpu_match_liveness.cpp", "pm_plugin_liveness_c.cpp", "gpu_match_discovery.cpp", "pm_plugin_discovery_c.cpp", "gpu_match_metrics.cpp", "pm_plugin_metrics_c.cpp", "gpu_match_probe.cpp", "pm_plugin_probe_c.cpp", "gpu_match_rollout.cpp", "pm_plugin_rollout_c.cpp", "gpu_match_directory.cpp", "pm_plugin_directory_c.cpp", "gpu_match_groupdir.cpp", "pm_plugin_groupdir_c.cpp", "gpu_match_taskdir.cpp", "pm_plugin_taskdir_c.cpp", "gpu_match_addresses.cpp", "pm_plugin_addresses_c.cpp", "gpu_match_gate.cpp", "pm_plugin_gate_c.cpp",
+                  "gpu_match_changes.cpp", "pm_plugin_changes_c.cpp", "gpu_match_liveness.cpp", "pm_plugin_liveness_c.cpp", "gpu_match_discovery.cpp", "pm_plugin_discovery_c.cpp", "gpu_match_metrics.cpp", "pm_plugin_metrics_c.cpp", "gpu_match_probe.cpp", "pm_plugin_probe_c.cpp", "gpu_match_rollout.cpp", "pm_plugin_rollout_c.cpp", "gpu_match_directory.cpp", "pm_plugin_directory_c.cpp", "gpu_match_groupdir.cpp", "pm_plugin_groupdir_c.cpp", "gpu_match_taskdir.cpp", "pm_plugin_taskdir_c.cpp", "gpu_match_addresses.cpp", "pm_plugin_addresses_c.cpp", "gpu_match_gate.cpp", "pm_plugin_gate_c.cpp", "gpu_match_admission.cpp", "pm_plugin_admission_c.cpp",
                   "pm_plugin_c.cpp", "pm_plugin_restore_c.cpp", "pm_plugin_report_c.cpp", "pm_plugin_spread_c.cpp",
                   "pm_plugin_near_c.cpp"]
 PLUGIN_HEADERS = ["gpu_match_plugin.hpp", "group_id_text.hpp", "pm_plugin_c.h", "pm_plugin_c_internal.hpp"]

@@ -731,6 +731,62 @@ uint32_t launch_gate_index(const uint32_t* bytes, const uint8_t* set, uint32_t W
 void launch_gate_verdict(const uint32_t* addr, const uint8_t* ok, const uint8_t* sig, const uint32_t* claimed, const uint8_t* flags,
                          uint32_t n, const uint32_t* idx, uint32_t n_idx, const uint32_t* book, const uint8_t* status, uint32_t* out,
                          uint32_t* counts, hipStream_t s);
+// request gate: admission (pm_admission.inc; the argument blocks are declared there).  launch_ad_rate: the requests sorted by
+// row into b (returns the buffer), stage [n] by request; launch_ad_rate_commit: the heads of that order write the windows;
+// launch_ad_nonces: the batch's nonces sorted by key into b (returns the buffer), replay [n], keep_new [n], keep_old [N];
+// launch_ad_merge: the next standing array; launch_ad_final: the codes, the beats, counts [PM_AD_N_CODES] += the census
+struct AdRateArgs {
+  const uint64_t* key;    // [n] sorted: rows, W behind them
+  const uint32_t* val;    // [n] the requests
+  uint32_t n, W;
+  uint64_t now_ms;
+  const uint64_t* win;    // [W]
+  const uint32_t* cnt;    // [W]
+  const uint8_t* flags;   // [n] or null
+  const uint64_t* ts;     // [n] or null (every request carries NO_TIMESTAMP)
+  const uint8_t* nonce;   // the nonces' bytes
+  const uint32_t* noff;   // [n + 1] or null (every request carries NO_NONCE)
+  uint32_t* stage;        // [n] by request
+};
+struct AdNonceArgs {
+  const uint64_t* key;      // [n] the batch's keys, sorted
+  const uint32_t* val;      // [n] the requests
+  uint32_t n, N, kbits;
+  uint64_t now_ms;
+  const uint32_t* stage;    // [n] by request
+  const uint64_t* dig;      // [4 n] by request
+  const uint64_t* old_dig;  // [4 N] the standing set
+  const uint64_t* old_ms;   // [N]
+  uint32_t* replay;         // [n] by request
+  uint32_t* keep_new;       // [n] by sorted position
+};
+struct AdMergeArgs {
+  const uint64_t* key;       // [n] the batch's keys, sorted
+  const uint32_t* val;       // [n]
+  uint32_t n, N, kbits, cap; // cap: entries the next array has room for
+  uint64_t now_ms;
+  const uint64_t* dig;       // [4 n] by request
+  const uint32_t* keep_new;  // [n]
+  const uint32_t* rank_new;  // [n + 1] its exclusive scan
+  const uint64_t* old_dig;   // [4 N]
+  const uint64_t* old_ms;    // [N]
+  const uint32_t* keep_old;  // [N]
+  const uint32_t* rank_old;  // [N + 1]
+  uint64_t* out_dig;         // [4 cap]
+  uint64_t* out_ms;          // [cap]
+};
+uint32_t launch_ad_rate(AdRateArgs a, const uint32_t* verdict, const RoSortBufs& b, hipStream_t s);
+uint32_t launch_ad_nonces(AdNonceArgs a, const RoSortBufs& b, uint32_t* keep_old, hipStream_t s);
+void launch_ad_merge(const AdMergeArgs& a, hipStream_t s);
+void launch_ad_rate_commit(const uint64_t* key, uint32_t n, uint32_t W, uint64_t now_ms, uint64_t* win, uint32_t* cnt, hipStream_t s);
+void launch_ad_old_live(const uint64_t* old_ms, uint32_t N, uint64_t now_ms, uint32_t* keep_old, hipStream_t s);
+void launch_ad_final(uint32_t* verdict, uint32_t n, uint32_t W, const uint32_t* stage, const uint32_t* replay, const uint8_t* flags,
+                     uint64_t now_ms, uint64_t* beat, uint32_t* counts, hipStream_t s);
+void launch_ad_gather(const uint32_t* idx, uint32_t n, const uint64_t* a64, const uint32_t* a32, uint64_t* out64, uint32_t* out32,
+                      hipStream_t s);
+void launch_ad_scatter(const uint32_t* idx, uint32_t n, uint32_t W, const uint64_t* in64, const uint32_t* in32, uint64_t* a64,
+                       uint32_t* a32, hipStream_t s);
+void launch_ad_beat_max(const uint64_t* col, uint32_t W, uint64_t* out, hipStream_t s);
 void launch_geo(const double* lat, const double* lon, double* coslat, double* ux, double* uy, double* uz, uint32_t W,
                 hipStream_t s);
 void launch_triad(const double* b, const double* c, double* a, size_t n, hipStream_t s);

@@ -238,6 +238,7 @@ int32_t pm_set_enabled_mask(pm_engine* e, uint64_t enabled) {
 #include "pm_engine_taskdir.inc"
 #include "pm_engine_addresses.inc"
 #include "pm_engine_gate.inc"
+#include "pm_engine_admission.inc"
 
 extern "C" {
 #include "pm_engine_tick.inc"

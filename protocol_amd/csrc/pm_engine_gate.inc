@@ -33,6 +33,50 @@ static int32_t gate_stage_recovery(pm_engine* e, const uint8_t* sig65, uint32_t 
   return PM_OK;
 }
 
+// what a batch of requests must be before anything is queued for it (n > 0)
+static int32_t gate_check(const uint8_t* bytes, const uint32_t* offsets, uint32_t n) {
+  if (n > 0x01FFFFFFu) return set_error(PM_ERANGE, "too many requests in one call");
+  for (uint32_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return set_error(PM_EINVAL, "the offsets must not descend");
+  const uint32_t total = offsets[n];  // (the buffer goes up from its first byte, whatever offsets[0] is)
+  if (total && !bytes) return set_error(PM_EINVAL, "null argument");
+  if (total > 0xFFFFFF00u) return set_error(PM_ERANGE, "too many message bytes in one call");
+  return PM_OK;
+}
+
+// the gate's stages for a checked batch, queued: the index, the staging, the EIP-191 hashes, the recoveries and the verdicts —
+// g.out [8 n], behind them the census.  What pm_verify_requests copies out and pm_admit_requests goes on from.
+static int32_t gate_queue(pm_engine* e, const uint8_t* bytes, const uint32_t* offsets, const uint8_t* sig65, const uint8_t* claimed20,
+                          const uint8_t* flags, uint32_t n) {
+  int32_t rc;
+  const uint32_t total = offsets[n];
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if ((rc = addresses_prepare(e))) return rc;
+  const bool live = e->live.on && e->dist_world <= 1;
+  if (live && (rc = liveness_prepare(e))) return rc;
+  if ((rc = gate_index(e))) return rc;
+  Gate& g = e->gate;
+  HIPCHK(g.text.ensure(size_t(total) + 8));  // (the kernel reads whole aligned words: the last may end behind the last byte)
+  HIPCHK(g.off.ensure(size_t(n) + 1));
+  HIPCHK(g.hash.ensure(4 * size_t(n)));
+  HIPCHK(g.claimed.ensure(5 * size_t(n)));
+  HIPCHK(g.out.ensure(8 * size_t(n) + PM_RQ_N_CODES));
+  if (flags) HIPCHK(g.flags.ensure(n));
+  if ((rc = gate_stage_recovery(e, sig65, n, false))) return rc;
+  if (total) HIPCHK(hipMemcpyAsync(g.text.p, bytes, total, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(g.off.p, offsets, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipMemcpyAsync(g.claimed.p, claimed20, 20 * size_t(n), hipMemcpyHostToDevice, e->stream));
+  if (flags) HIPCHK(hipMemcpyAsync(g.flags.p, flags, n, hipMemcpyHostToDevice, e->stream));
+  uint32_t* d_counts = g.out.p + 8 * size_t(n);
+  HIPCHK(hipMemsetAsync(d_counts, 0, PM_RQ_N_CODES * sizeof(uint32_t), e->stream));
+  launch_eip191_many(g.text.p, g.off.p, n, g.hash.p, e->stream);
+  launch_ecrecover(g.hash.p, g.sig.p, n, g.addr.p, nullptr, g.ok.p, e->stream);
+  launch_gate_verdict(g.addr.p, g.ok.p, g.sig.p, g.claimed.p, flags ? g.flags.p : nullptr, n, g.sort.val[g.cur].p, g.n_idx, e->ab.bytes.p,
+                      live ? e->live.status.p : nullptr, g.out.p, d_counts, e->stream);
+  HIPCHK(hipGetLastError());
+  return PM_OK;
+}
+
 }  // namespace pm
 
 extern "C" {
@@ -69,36 +113,10 @@ int32_t pm_verify_requests(pm_engine* e, const uint8_t* bytes, const uint32_t* o
   int32_t rc = addresses_guard(e);
   if (rc) return rc;
   if (!n) return PM_OK;
-  if (n > 0x01FFFFFFu) return set_error(PM_ERANGE, "too many requests in one call");
-  for (uint32_t i = 0; i < n; ++i)
-    if (offsets[i + 1] < offsets[i]) return set_error(PM_EINVAL, "the offsets must not descend");
-  const uint32_t total = offsets[n];  // (the buffer goes up from its first byte, whatever offsets[0] is)
-  if (total && !bytes) return set_error(PM_EINVAL, "null argument");
-  if (total > 0xFFFFFF00u) return set_error(PM_ERANGE, "too many message bytes in one call");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  if ((rc = addresses_prepare(e))) return rc;
-  const bool live = e->live.on && e->dist_world <= 1;
-  if (live && (rc = liveness_prepare(e))) return rc;
-  if ((rc = gate_index(e))) return rc;
+  if ((rc = gate_check(bytes, offsets, n))) return rc;
+  if ((rc = gate_queue(e, bytes, offsets, sig65, claimed20, flags, n))) return rc;
   Gate& g = e->gate;
-  HIPCHK(g.text.ensure(size_t(total) + 8));  // (the kernel reads whole aligned words: the last may end behind the last byte)
-  HIPCHK(g.off.ensure(size_t(n) + 1));
-  HIPCHK(g.hash.ensure(4 * size_t(n)));
-  HIPCHK(g.claimed.ensure(5 * size_t(n)));
-  HIPCHK(g.out.ensure(8 * size_t(n) + PM_RQ_N_CODES));
-  if (flags) HIPCHK(g.flags.ensure(n));
-  if ((rc = gate_stage_recovery(e, sig65, n, false))) return rc;
-  if (total) HIPCHK(hipMemcpyAsync(g.text.p, bytes, total, hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(g.off.p, offsets, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipMemcpyAsync(g.claimed.p, claimed20, 20 * size_t(n), hipMemcpyHostToDevice, e->stream));
-  if (flags) HIPCHK(hipMemcpyAsync(g.flags.p, flags, n, hipMemcpyHostToDevice, e->stream));
   uint32_t* d_counts = g.out.p + 8 * size_t(n);
-  HIPCHK(hipMemsetAsync(d_counts, 0, PM_RQ_N_CODES * sizeof(uint32_t), e->stream));
-  launch_eip191_many(g.text.p, g.off.p, n, g.hash.p, e->stream);
-  launch_ecrecover(g.hash.p, g.sig.p, n, g.addr.p, nullptr, g.ok.p, e->stream);
-  launch_gate_verdict(g.addr.p, g.ok.p, g.sig.p, g.claimed.p, flags ? g.flags.p : nullptr, n, g.sort.val[g.cur].p, g.n_idx, e->ab.bytes.p,
-                      live ? e->live.status.p : nullptr, g.out.p, d_counts, e->stream);
-  HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out, g.out.p, sizeof(pm_rq_verdict) * size_t(n), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipMemcpyAsync(counts, d_counts, PM_RQ_N_CODES * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));

@@ -47,6 +47,75 @@ static int32_t liveness_guard(pm_engine* e) {
   return PM_OK;
 }
 
+// the sweep behind its guard, under the engine mutex.  A row's beat: last_beat_ms[w] from the host, or — dev_beats given
+// (pm_liveness_sweep_beats: a device column that covers the table) — the later of the two, or that column alone
+static int32_t liveness_sweep_locked(pm_engine* e, uint64_t now_ms, const uint64_t* last_beat_ms, const uint64_t* dev_beats,
+                                     const uint64_t* in_pool_bits, uint32_t apply, uint32_t* n_transitions, uint32_t* census) {
+  int32_t rc;
+  HIPCHK(hipSetDevice(e->cfg.device));
+  if ((rc = liveness_prepare(e))) return rc;
+  const uint32_t W = e->W, words = (W + 63u) / 64u;
+  HIPCHK(e->live.h_count.ensure(1 + PM_NS_N, 1 + PM_NS_N));
+  uint32_t* const h_count = e->live.h_count.p;
+  e->live.n = 0;
+  e->live.rows_host = false;
+  std::memset(h_count, 0, (1 + PM_NS_N) * sizeof(uint32_t));
+  if (W) {
+    HIPCHK(e->live.old.ensure(W));
+    HIPCHK(e->live.bitmap.ensure(words));
+    HIPCHK(e->live.prefix.ensure(words));
+    HIPCHK(e->live.rows.ensure(W));
+    HIPCHK(e->live.census.ensure(PM_NS_N));
+    HIPCHK(e->live.beat.ensure(size_t(W) + words));
+    if (last_beat_ms) HIPCHK(hipMemcpyAsync(e->live.beat.p, last_beat_ms, size_t(W) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    if (last_beat_ms && dev_beats) launch_ad_beat_max(dev_beats, W, e->live.beat.p, e->stream);
+    if (in_pool_bits)
+      HIPCHK(hipMemcpyAsync(e->live.beat.p + W, in_pool_bits, size_t(words) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(e->live.census.p, 0, PM_NS_N * sizeof(uint32_t), e->stream));
+    LiveSweepArgs a{};
+    a.W = W;
+    a.m = e->live.m;
+    a.now_ms = now_ms;
+    a.beat = last_beat_ms ? e->live.beat.p : dev_beats;
+    a.pool = in_pool_bits ? e->live.beat.p + W : nullptr;
+    a.status = e->live.status.p;
+    a.counter = e->live.counter.p;
+    a.old_status = e->live.old.p;
+    a.bitmap = e->live.bitmap.p;
+    a.census = e->live.census.p;
+    launch_liveness_sweep(a, e->stream);
+    launch_liveness_list(e->live.bitmap.p, words, e->live.old.p, e->live.status.p, e->live.counter.p, e->live.prefix.p,
+                         h_count, e->live.rows.p, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_count + 1, e->live.census.p, PM_NS_N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (h_count[0] > W) return set_error(PM_ESTATE, "liveness: more listed rows than rows");
+    e->live.n = h_count[0];
+    // (metrics on: the rows that became Dead lose their metrics, status_update/mod.rs:314-343 — on the device, from the list)
+    if (e->mx.on && e->live.n && (rc = metrics_clear_dead(e))) return rc;
+  }
+  if (n_transitions) *n_transitions = e->live.n;
+  if (census) std::copy(h_count + 1, h_count + 1 + PM_NS_N, census);
+  if (!apply || !e->live.n) return PM_OK;
+  // the list in list order through pm_on_worker_status_many's body (status_update_impl.rs:8-39 behind mod.rs:360-368), still
+  // under the engine mutex: nothing can come between the sweep and what it applies
+  const uint32_t n = e->live.n;
+  e->live.h_rows.resize(n);
+  HIPCHK(hipMemcpyAsync(e->live.h_rows.data(), e->live.rows.p, size_t(n) * sizeof(pm_live_row), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  e->live.rows_host = true;
+  std::vector<uint32_t> col(3 * size_t(n));
+  uint32_t* const workers = col.data(), * const flags_new = workers + n, * const dead = flags_new + n;
+  for (uint32_t k = 0; k < n; ++k) {
+    const pm_live_row& r = e->live.h_rows[k];
+    if (r.worker >= W) return set_error(PM_ESTATE, "liveness: a listed row the table does not hold");
+    workers[k] = r.worker;
+    flags_new[k] = r.new_status == PM_NS_HEALTHY ? (e->h_flags[r.worker] | PM_W_HEALTHY) : (e->h_flags[r.worker] & ~uint32_t(PM_W_HEALTHY));
+    dead[k] = r.new_status == PM_NS_DEAD ? 1u : 0u;
+  }
+  return worker_status_many_locked(e, workers, flags_new, dead, n);
+}
+
 }  // namespace pm
 
 extern "C" {
@@ -131,67 +200,7 @@ int32_t pm_liveness_sweep(pm_engine* e, uint64_t now_ms, const uint64_t* last_be
   int32_t rc = liveness_guard(e);
   if (rc) return rc;
   if (e->W && !last_beat_ms) return set_error(PM_EINVAL, "null beat column");
-  HIPCHK(hipSetDevice(e->cfg.device));
-  if ((rc = liveness_prepare(e))) return rc;
-  const uint32_t W = e->W, words = (W + 63u) / 64u;
-  HIPCHK(e->live.h_count.ensure(1 + PM_NS_N, 1 + PM_NS_N));
-  uint32_t* const h_count = e->live.h_count.p;
-  e->live.n = 0;
-  e->live.rows_host = false;
-  std::memset(h_count, 0, (1 + PM_NS_N) * sizeof(uint32_t));
-  if (W) {
-    HIPCHK(e->live.old.ensure(W));
-    HIPCHK(e->live.bitmap.ensure(words));
-    HIPCHK(e->live.prefix.ensure(words));
-    HIPCHK(e->live.rows.ensure(W));
-    HIPCHK(e->live.census.ensure(PM_NS_N));
-    HIPCHK(e->live.beat.ensure(size_t(W) + words));
-    HIPCHK(hipMemcpyAsync(e->live.beat.p, last_beat_ms, size_t(W) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    if (in_pool_bits)
-      HIPCHK(hipMemcpyAsync(e->live.beat.p + W, in_pool_bits, size_t(words) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemsetAsync(e->live.census.p, 0, PM_NS_N * sizeof(uint32_t), e->stream));
-    LiveSweepArgs a{};
-    a.W = W;
-    a.m = e->live.m;
-    a.now_ms = now_ms;
-    a.beat = e->live.beat.p;
-    a.pool = in_pool_bits ? e->live.beat.p + W : nullptr;
-    a.status = e->live.status.p;
-    a.counter = e->live.counter.p;
-    a.old_status = e->live.old.p;
-    a.bitmap = e->live.bitmap.p;
-    a.census = e->live.census.p;
-    launch_liveness_sweep(a, e->stream);
-    launch_liveness_list(e->live.bitmap.p, words, e->live.old.p, e->live.status.p, e->live.counter.p, e->live.prefix.p,
-                         h_count, e->live.rows.p, e->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_count + 1, e->live.census.p, PM_NS_N * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (h_count[0] > W) return set_error(PM_ESTATE, "liveness: more listed rows than rows");
-    e->live.n = h_count[0];
-    // (metrics on: the rows that became Dead lose their metrics, status_update/mod.rs:314-343 — on the device, from the list)
-    if (e->mx.on && e->live.n && (rc = metrics_clear_dead(e))) return rc;
-  }
-  if (n_transitions) *n_transitions = e->live.n;
-  if (census) std::copy(h_count + 1, h_count + 1 + PM_NS_N, census);
-  if (!apply || !e->live.n) return PM_OK;
-  // the list in list order through pm_on_worker_status_many's body (status_update_impl.rs:8-39 behind mod.rs:360-368), still
-  // under the engine mutex: nothing can come between the sweep and what it applies
-  const uint32_t n = e->live.n;
-  e->live.h_rows.resize(n);
-  HIPCHK(hipMemcpyAsync(e->live.h_rows.data(), e->live.rows.p, size_t(n) * sizeof(pm_live_row), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  e->live.rows_host = true;
-  std::vector<uint32_t> col(3 * size_t(n));
-  uint32_t* const workers = col.data(), * const flags_new = workers + n, * const dead = flags_new + n;
-  for (uint32_t k = 0; k < n; ++k) {
-    const pm_live_row& r = e->live.h_rows[k];
-    if (r.worker >= W) return set_error(PM_ESTATE, "liveness: a listed row the table does not hold");
-    workers[k] = r.worker;
-    flags_new[k] = r.new_status == PM_NS_HEALTHY ? (e->h_flags[r.worker] | PM_W_HEALTHY) : (e->h_flags[r.worker] & ~uint32_t(PM_W_HEALTHY));
-    dead[k] = r.new_status == PM_NS_DEAD ? 1u : 0u;
-  }
-  return worker_status_many_locked(e, workers, flags_new, dead, n);
+  return liveness_sweep_locked(e, now_ms, last_beat_ms, nullptr, in_pool_bits, apply, n_transitions, census);
 }
 
 int32_t pm_liveness_transitions(pm_engine* e, pm_live_row* rows, uint32_t cap, uint32_t* n) {

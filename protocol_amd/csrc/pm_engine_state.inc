@@ -190,6 +190,32 @@ struct Gate {
   DevBuf<uint32_t> out;       // [8 n] the verdicts, behind them [PM_RQ_N_CODES] the census
 };
 
+// ---- request gate: admission (pm_engine_admission.inc): the rate window and the last beat of every worker row, the standing
+// nonce set — a sorted array, two buffers that take turns: a call merges the batch into the other one — and a call's scratch
+struct Admission {
+  bool on = false;
+  bool reinit = false;        // an upload dropped the row identities: the next admission call empties the rate ledger and the beats
+  uint32_t W = 0;             // rows covered
+  uint32_t kbits = 64;        // bits of a digest that make its sort key (the debug header's hook narrows it)
+  DevBuf<uint64_t> win;       // [W] window_start_ms
+  DevBuf<uint32_t> cnt;       // [W] count
+  DevBuf<uint64_t> beat;      // [W] last_beat_ms
+  DevBuf<uint64_t> dig[2];    // [4 N] the standing digests, sorted by key
+  DevBuf<uint64_t> ms[2];     // [N] stored_ms
+  uint32_t cur = 0, N = 0;    // the buffer that holds the set; entries held
+  KeySort sort;               // a call's two sorts: by row, then by key
+  DevBuf<uint8_t> text;       // the batch's nonces
+  DevBuf<uint32_t> off;       // [n + 1]
+  DevBuf<uint64_t> ndig;      // [4 n] their digests
+  DevBuf<uint64_t> ts;        // [n]
+  DevBuf<uint32_t> stage, replay, keep_new, rank_new;  // [n] (+ 1)
+  DevBuf<uint32_t> keep_old, rank_old;                 // [N] (+ 1)
+  DevBuf<uint32_t> counts;    // [PM_AD_N_CODES]
+  DevBuf<uint32_t> idx, io32; // the hand-over calls' rows and counts
+  DevBuf<uint64_t> io64;
+  PinBuf<uint32_t> h_pin;     // [0] kept new entries, [1] kept standing entries
+};
+
 struct pm_engine {
   Stream stream_owned;  // created with the engine.  Declared first, so destroyed last: everything below may be freed on a live stream
   pm_engine_config cfg{};
@@ -430,4 +456,5 @@ struct pm_engine {
   TaskDir tdir;   // (the same)
   AddressBook ab;
   Gate gate;      // (the book's index and scratch: never switched)
+  Admission ad;
 };

@@ -124,6 +124,7 @@ int32_t pm_upload_workers(pm_engine* e, const pm_worker_soa* w, uint32_t keep_gr
     e->mx.reinit = true;    // (metrics: the next metrics call empties every worker row)
     e->ro.reinit = true;    // (rollout: the next rollout call empties every row)
     e->ab.reinit = true;    // (address book: the next book call clears every row's flag)
+    e->ad.reinit = true;    // (admission: the next admission call empties the rate ledger and the beats; the nonce set stays)
     reset_groups_locked(e);
   } else {
     e->h_group_of.resize(n, -1);  // (rows behind the known ones are new: in no group)

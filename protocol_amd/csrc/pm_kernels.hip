@@ -801,5 +801,6 @@ __global__ __launch_bounds__(256) void newest_kernel(const int64_t* __restrict__
 #include "pm_keccak.inc"        // keccak-256: the permutation in registers, the sponge, one message a lane
 #include "pm_addresses.inc"     // address book: EIP-55 case masks and text keys, the rank's two sort paths, texts, invite digests
 #include "pm_secp256k1.inc"     // request gate: secp256k1 recovery a lane, the EIP-191 hash, the address index and the verdicts
+#include "pm_admission.inc"     // request gate, admission: the rate windows, the nonce set's merge, the beats
 #include "pm_launch.inc"        // the launchers pm_engine.cpp calls
 }  // namespace pm

@@ -239,6 +239,8 @@ EXPORTS = [
     "pm_task_directory",
     "pm_addresses_enable", "pm_addresses_set", "pm_addresses_rank", "pm_addresses_text", "pm_invite_digests",
     "pm_ecrecover_many", "pm_verify_requests", "pm_host_ecrecover",
+    "pm_admission_enable", "pm_admit_requests", "pm_admission_rate_get", "pm_admission_rate_set", "pm_admission_nonces",
+    "pm_beats_get", "pm_beats_set", "pm_liveness_sweep_beats",
 ]
 # ... and the declared names that carry a digit, which the header check's name pattern (letters and '_') does not take in
 EXPORTS_NUMBERED = ["pm_keccak256_many", "pm_host_keccak256", "pm_host_eip55"]
@@ -361,6 +363,14 @@ def lib() -> C.CDLL:
         L.pm_ecrecover_many.argtypes = [vp, vp, vp, u32, vp, vp, vp]
         L.pm_verify_requests.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp]
         L.pm_host_ecrecover.argtypes = [vp, vp, vp]
+        L.pm_admission_enable.argtypes = [vp, u32]
+        L.pm_admit_requests.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]
+        L.pm_admission_rate_get.argtypes = [vp, vp, u32, vp, vp]
+        L.pm_admission_rate_set.argtypes = [vp, vp, vp, vp, u32]
+        L.pm_admission_nonces.argtypes = [vp, u64, C.POINTER(u32), C.POINTER(u32)]
+        L.pm_beats_get.argtypes = [vp, vp, u32, vp]
+        L.pm_beats_set.argtypes = [vp, vp, vp, u32]
+        L.pm_liveness_sweep_beats.argtypes = [vp, u64, vp, vp, u32, C.POINTER(u32), vp]
         # (bound where the library has them: a test library that stubs EXPORTS alone lacks them, and a call then fails by name)
         numbered = {"pm_keccak256_many": [vp, vp, vp, u32, vp], "pm_host_keccak256": [vp, sz, vp], "pm_host_eip55": [vp, vp]}
         for name in EXPORTS_NUMBERED:
@@ -428,6 +438,16 @@ RQ_VERDICT = np.dtype([("code", np.uint32), ("row", np.uint32), ("status", np.ui
 assert RQ_VERDICT.itemsize == 32
 RQ_BAD_SIGNATURE, RQ_NO_KEY, RQ_BAD_ADDRESS, RQ_MISMATCH, RQ_UNKNOWN, RQ_EJECTED, RQ_BANNED, RQ_OK, RQ_N_CODES = range(9)
 RQ_FLAG_BAD_ADDRESS = 1
+# ... and what admission appends (include/pm_engine.h "request gate: admission")
+RQ_RATE_LIMITED, RQ_EXPIRED, RQ_BAD_NONCE, RQ_REPLAY, RQ_NO_NONCE, AD_N_CODES = range(8, 14)
+RQ_FLAG_NO_TIMESTAMP, RQ_FLAG_NO_NONCE, RQ_FLAG_BEAT = 2, 4, 8
+RQ_NONCE_TTL_MS = 60000
+
+
+def ad_debug_prefix_bits(k: int) -> int:
+    """PM_AD_DEBUG_PREFIX_BITS(k) of include/pm_engine_debug.h: `on` for enable_admission with the nonce set's key narrowed to k bits"""
+    return 1 | (int(k) << 8)
+
 
 TICK_MANY_THREADS = 1
 
@@ -1214,6 +1234,71 @@ class Engine:
                                        claimed.ctypes.data if n else None, None if flags is None else flags.ctypes.data, n,
                                        out.ctypes.data, counts.ctypes.data))
         return out[:n], counts
+
+    # ---- request gate: admission (include/pm_engine.h "request gate: admission")
+    def enable_admission(self, on=True) -> None:
+        """pm_admission_enable (on: a bool, or ad_debug_prefix_bits(k))"""
+        check(lib().pm_admission_enable(self._h, int(on)))
+
+    def admit_requests(self, packed, now_ms: int):
+        """pm_admit_requests: packed = protocol_amd.admission.pack_admissions(...) -> (verdicts [n] of RQ_VERDICT, counts uint32
+        [AD_N_CODES])"""
+        buf, off, sigs, claimed, flags, ts, nbuf, noff = packed
+        n = len(off) - 1
+        out, counts = np.zeros(max(n, 1), dtype=RQ_VERDICT), np.zeros(AD_N_CODES, dtype=np.uint32)
+        check(lib().pm_admit_requests(self._h, int(now_ms), buf.ctypes.data if len(buf) else None, off.ctypes.data,
+                                      sigs.ctypes.data if n else None, claimed.ctypes.data if n else None,
+                                      None if flags is None else flags.ctypes.data, None if ts is None else ts.ctypes.data,
+                                      nbuf.ctypes.data if nbuf is not None and len(nbuf) else None,
+                                      None if noff is None else noff.ctypes.data, n, out.ctypes.data, counts.ctypes.data))
+        return out[:n], counts
+
+    def admission_rate_get(self, idx):
+        """pm_admission_rate_get -> (window_start_ms uint64 [n], count uint32 [n])"""
+        ix = _arr(idx, np.uint32)
+        n = len(ix)
+        win, cnt = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().pm_admission_rate_get(self._h, ix.ctypes.data if n else None, n, win.ctypes.data, cnt.ctypes.data))
+        return win[:n], cnt[:n]
+
+    def admission_rate_set(self, idx, window_start_ms, count) -> None:
+        ix, win, cnt = _arr(idx, np.uint32), _arr(window_start_ms, np.uint64), _arr(count, np.uint32)
+        assert len(win) == len(ix) == len(cnt)
+        n = len(ix)
+        check(lib().pm_admission_rate_set(self._h, ix.ctypes.data if n else None, win.ctypes.data if n else None,
+                                          cnt.ctypes.data if n else None, n))
+
+    def admission_nonces(self, now_ms: int):
+        """pm_admission_nonces -> (n_live at now_ms, n_held)"""
+        live, held = C.c_uint32(0), C.c_uint32(0)
+        check(lib().pm_admission_nonces(self._h, int(now_ms), C.byref(live), C.byref(held)))
+        return live.value, held.value
+
+    def beats_get(self, idx) -> np.ndarray:
+        ix = _arr(idx, np.uint32)
+        n = len(ix)
+        ms = np.zeros(max(n, 1), dtype=np.uint64)
+        check(lib().pm_beats_get(self._h, ix.ctypes.data if n else None, n, ms.ctypes.data))
+        return ms[:n]
+
+    def beats_set(self, idx, last_beat_ms) -> None:
+        ix, ms = _arr(idx, np.uint32), _arr(last_beat_ms, np.uint64)
+        assert len(ms) == len(ix)
+        n = len(ix)
+        check(lib().pm_beats_set(self._h, ix.ctypes.data if n else None, ms.ctypes.data if n else None, n))
+
+    def liveness_sweep_beats(self, now_ms: int, last_beat_ms=None, in_pool_bits=None, apply: bool = False):
+        """pm_liveness_sweep_beats -> (n_transitions, census uint32 [NS_N]): pm_liveness_sweep over the later of the device's beat
+        column and last_beat_ms (None: the device's column alone)"""
+        b = _arr(last_beat_ms, np.uint64) if last_beat_ms is not None else None
+        assert b is None or len(b) == self.W
+        p = _arr(in_pool_bits, np.uint64) if in_pool_bits is not None else None
+        assert p is None or len(p) == (self.W + 63) // 64
+        n, census = C.c_uint32(0), np.zeros(NS_N, dtype=np.uint32)
+        check(lib().pm_liveness_sweep_beats(self._h, int(now_ms), b.ctypes.data if b is not None and len(b) else None,
+                                            p.ctypes.data if p is not None and len(p) else None, int(apply), C.byref(n),
+                                            census.ctypes.data))
+        return n.value, census
 
     def debug_address_sorts(self) -> dict:
         """ranks the address book ended on its one-word / all-words sort since creation (pm_debug_carve_prof words 98, 99)"""

@@ -48,7 +48,9 @@ std::vector<GpuMatchPlugin::StatusTransition> GpuMatchPlugin::sweep_statuses(uin
       }
     }
     uint32_t n = 0;
-    check(pm_liveness_sweep(engine_, now_ms, W ? beats.data() : nullptr, pool.empty() ? nullptr : pool.data(), 1u, &n, nullptr));
+    // (admission on: the later of the device's beat column and this one, so beat() and admitted heartbeats both count)
+    check((sweep_call_ ? sweep_call_ : pm_liveness_sweep)(engine_, now_ms, W ? beats.data() : nullptr, pool.empty() ? nullptr : pool.data(), 1u, &n,
+                                                          nullptr));
     std::vector<pm_live_row> rows(n ? n : 1u);
     uint32_t got = 0;
     check(pm_liveness_transitions(engine_, rows.data(), uint32_t(rows.size()), &got));

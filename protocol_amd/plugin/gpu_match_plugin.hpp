@@ -653,6 +653,25 @@ class GpuMatchPlugin : public SchedulerPlugin {
   GateResult verify_requests(const std::vector<GateRequest>& requests) const;
   static bool parse_signature_text(const std::string& text, uint8_t out65[65]);
 
+  // ---- request gate: admission (INTEGRATION.md "Request gate: admission"; gpu_match_admission.cpp): pm_admit_requests.  The
+  // whole of the middleware behind its signature check (auth_signature_middleware.rs:424-483: rate limit, age, nonce) and the
+  // heartbeat handler's stamp, for a batch in ONE engine call, handled as if one after another in batch order, all at now_ms.
+  // `timestamp` and `nonce` are what the middleware reads from the payload or the query (:301-372; none, or a timestamp that is
+  // no u64: the middleware skips the age / answers MISSING_NONCE).  `heartbeat`: the route is /heartbeat — an OK stamps the row's beat on the device.  enable_admission needs enable_address_book
+  // (EngineError(PM_ESTATE) without); from then on sweep_statuses sweeps over the later of the device's column and the plugin's
+  // own (pm_liveness_sweep_beats), so beat() keeps working.
+  struct AdmitRequest {
+    std::string message, signature, address;
+    std::optional<std::string> timestamp, nonce;
+    bool heartbeat = false;
+  };
+  struct AdmitResult {
+    std::vector<GateVerdict> verdicts;
+    std::array<uint32_t, PM_AD_N_CODES> counts{};
+  };
+  void enable_admission();
+  AdmitResult admit_requests(const std::vector<AdmitRequest>& requests, uint64_t now_ms) const;
+
   // chrono::Utc::now() for NodeGroup.created_at, milliseconds since the epoch (tests inject their own)
   std::function<int64_t()> clock = [] {
     return int64_t(std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count());
@@ -735,6 +754,10 @@ class GpuMatchPlugin : public SchedulerPlugin {
   // against an engine without the liveness exports): handle_status_change's write to the ledger
   void (*liveness_note_)(const GpuMatchPlugin&, uint32_t row, NodeStatus status) = nullptr;
   static void liveness_note(const GpuMatchPlugin& self, uint32_t row, NodeStatus status);
+  // set by enable_admission to pm_liveness_sweep_beats (gpu_match_admission.cpp; a pointer, so that gpu_match_liveness.cpp stays
+  // linkable against an engine without the admission exports): what sweep_statuses calls instead of pm_liveness_sweep
+  int32_t (*sweep_call_)(pm_engine*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint32_t*, uint32_t*) = nullptr;
+  bool admission_on_ = false;  // (under the node lock)
   // address book (gpu_match_addresses.cpp; under the node lock): the rows' 20 bytes, bytes -> row, and how many rows render the
   // device's text.  book_sync_ is set by enable_address_book to book_sync (a pointer, as liveness_note_ is): sync_nodes' engine
   // calls — the bytes of the rows [first, end) or of every row, the rank, the texts of the rows that have none yet

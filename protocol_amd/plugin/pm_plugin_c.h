@@ -260,6 +260,13 @@ int32_t pmx_invite_digests(pmx_plugin*, uint32_t domain_id, uint32_t pool_id, ui
  * in that order. */
 int32_t pmx_verify_requests(pmx_plugin*, const char* requests, char* out, size_t cap, size_t* needed);
 
+/* ---- request gate: admission (pm_plugin_admission_c.cpp): GpuMatchPlugin::enable_admission / admit_requests (needs
+ * pmx_enable_address_book).  requests: one line per request, "<signature text>\t<x-address text>\t<timestamp or ->\t<nonce
+ * or ->\t<1 = /heartbeat, else 0>\t<message>".  The text: pmx_verify_requests' lines, the code one of its eight or
+ * rate_limited, expired, bad_nonce, replay, no_nonce; then "counts" and the thirteen census words in that order. */
+int32_t pmx_enable_admission(pmx_plugin*);
+int32_t pmx_admit_requests(pmx_plugin*, const char* requests, uint64_t now_ms, char* out, size_t cap, size_t* needed);
+
 /* ---- discovery sync (pm_plugin_discovery_c.cpp): GpuMatchPlugin::set_endpoint / sync_discovery (needs pmx_enable_liveness).  The
  * text of pmx_sync_discovery: one line per sighting, in order: "<address>\tadmitted\t<cnt>", "<address>\tskipped\t<cnt>" or
  * "<address>\tsynced\t<cnt>\t<old status>\t<final status>\t<ops>\t<old>><new>,..." — cnt = the Healthy other nodes on the sighting's

@@ -130,6 +130,16 @@ pub const RQ_EJECTED: u32 = 5;
 pub const RQ_BANNED: u32 = 6;
 pub const RQ_OK: u32 = 7;
 pub const RQ_N_CODES: usize = 8;
+// ... and what pm_admit_requests appends (include/pm_engine.h "request gate: admission")
+pub const RQ_RATE_LIMITED: u32 = 8;
+pub const RQ_EXPIRED: u32 = 9;
+pub const RQ_BAD_NONCE: u32 = 10;
+pub const RQ_REPLAY: u32 = 11;
+pub const RQ_NO_NONCE: u32 = 12;
+pub const AD_N_CODES: usize = 13;
+pub const RQ_FLAG_NO_TIMESTAMP: u8 = 2;
+pub const RQ_FLAG_NO_NONCE: u8 = 4;
+pub const RQ_FLAG_BEAT: u8 = 8;
 
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -805,6 +815,13 @@ extern "C" {
     fn pm_verify_requests(e: *mut c_void, bytes: *const u8, offsets: *const u32, sig65: *const u8, claimed20: *const u8,
                           flags: *const u8, n: u32, out: *mut pm_rq_verdict, counts: *mut u32) -> i32;
     fn pm_host_ecrecover(hash32: *const u8, sig65: *const u8, addr20: *mut u8) -> i32;
+    // request gate: admission (include/pm_engine.h "request gate: admission")
+    fn pm_admission_enable(e: *mut c_void, on: u32) -> i32;
+    fn pm_admit_requests(e: *mut c_void, now_ms: u64, bytes: *const u8, offsets: *const u32, sig65: *const u8, claimed20: *const u8,
+                         flags: *const u8, timestamp_s: *const u64, nonce_bytes: *const u8, nonce_offsets: *const u32, n: u32,
+                         out: *mut pm_rq_verdict, counts: *mut u32) -> i32;
+    fn pm_liveness_sweep_beats(e: *mut c_void, now_ms: u64, last_beat_ms: *const u64, in_pool_bits: *const u64, apply: u32,
+                               n_transitions: *mut u32, census: *mut u32) -> i32;
 }
 
 /// RCCL (librccl.so, rccl/rccl.h): the one collective the multi-GPU tick issues
@@ -920,6 +937,7 @@ struct NodeTable {
     /// address book (enable_address_book): the rows' 20 bytes, bytes -> row, how many rows render the device's text, and the
     /// ranks pm_addresses_rank gave last (a rewritten row is sent with the rank it has).  by_address is not kept then.
     book_on: bool,
+    admission_on: bool,
     book_bytes: Vec<u8>,
     book_by_bytes: HashMap<[u8; 20], u32>,
     book_texts: usize,
@@ -1649,6 +1667,55 @@ impl GpuMatchPlugin {
         let mut out = vec![pm_rq_verdict::default(); n];
         check(unsafe { pm_verify_requests(self.engine, bytes.as_ptr(), offsets.as_ptr(), sig.as_ptr(), claimed.as_ptr(), std::ptr::null(),
                                           n as u32, out.as_mut_ptr(), counts.as_mut_ptr()) })?;
+        Ok((out, counts))
+    }
+
+    /// Turns the engine's admission ledger on (pm_admission_enable): the rate windows, the nonce set and the beat column on the
+    /// device.  From then on sweep_statuses sweeps over the later of the device's column and the plugin's own
+    /// (pm_liveness_sweep_beats), so beat() keeps working.  Needs enable_address_book.
+    pub fn enable_admission(&self) -> Result<()> {
+        let mut t = self.nodes.write();       // (LOCK ORDER: nodes, the engine)
+        if !t.book_on { return Err(anyhow!("pm_engine error {PM_ESTATE}: the address book is off (enable_address_book)")); }
+        check(unsafe { pm_admission_enable(self.engine, 1) })?;
+        t.admission_on = true;
+        Ok(())
+    }
+
+    /// The whole of the middleware behind its signature check (auth_signature_middleware.rs:424-483: rate limit, age, nonce) and
+    /// the heartbeat handler's stamp, for a batch in ONE engine call, handled as if one after another in batch order, all at
+    /// now_ms: (message, signature, x-address, the timestamp the middleware read or None, the nonce or None, the route is
+    /// /heartbeat).  An OK heartbeat stamps its row's beat on the device.  Needs enable_admission.
+    #[allow(clippy::type_complexity)]
+    pub fn admit_requests(&self, requests: &[(&[u8], [u8; 65], Address, Option<u64>, Option<&str>, bool)], now_ms: u64)
+                          -> Result<(Vec<pm_rq_verdict>, [u32; AD_N_CODES])> {
+        let t = self.nodes.read();
+        if !t.book_on { return Err(anyhow!("pm_engine error {PM_ESTATE}: the address book is off (enable_address_book)")); }
+        if !t.admission_on { return Err(anyhow!("pm_engine error {PM_ESTATE}: admission is off (enable_admission)")); }
+        let n = requests.len();
+        let mut counts = [0u32; AD_N_CODES];
+        if n == 0 { return Ok((Vec::new(), counts)); }
+        let (mut bytes, mut offsets) = (Vec::<u8>::new(), vec![0u32; n + 1]);
+        let (mut nonces, mut nonce_offsets) = (Vec::<u8>::new(), vec![0u32; n + 1]);
+        let (mut sig, mut claimed) = (Vec::<u8>::with_capacity(65 * n), Vec::<u8>::with_capacity(20 * n));
+        let (mut flags, mut timestamps) = (vec![0u8; n], vec![0u64; n]);
+        for (k, (message, signature, address, timestamp, nonce, heartbeat)) in requests.iter().enumerate() {
+            bytes.extend_from_slice(message);
+            if bytes.len() > 0xFFFF_FF00 { return Err(anyhow!("pm_engine error {PM_ERANGE}: too many message bytes in one call")); }
+            offsets[k + 1] = bytes.len() as u32;
+            sig.extend_from_slice(signature);
+            let a: [u8; 20] = address.into_array();
+            claimed.extend_from_slice(&a);
+            match timestamp { Some(ts) => timestamps[k] = *ts, None => flags[k] |= RQ_FLAG_NO_TIMESTAMP }
+            match nonce { Some(text) => nonces.extend_from_slice(text.as_bytes()), None => flags[k] |= RQ_FLAG_NO_NONCE }
+            if nonces.len() > 0xFFFF_FF00 { return Err(anyhow!("pm_engine error {PM_ERANGE}: too many nonce bytes in one call")); }
+            nonce_offsets[k + 1] = nonces.len() as u32;
+            if *heartbeat { flags[k] |= RQ_FLAG_BEAT; }
+        }
+        nonces.push(0);  // (never read: a batch without a nonce still has an address)
+        let mut out = vec![pm_rq_verdict::default(); n];
+        check(unsafe { pm_admit_requests(self.engine, now_ms, bytes.as_ptr(), offsets.as_ptr(), sig.as_ptr(), claimed.as_ptr(),
+                                         flags.as_ptr(), timestamps.as_ptr(), nonces.as_ptr(), nonce_offsets.as_ptr(), n as u32,
+                                         out.as_mut_ptr(), counts.as_mut_ptr()) })?;
         Ok((out, counts))
     }
 
@@ -2398,9 +2465,13 @@ impl GpuMatchPlugin {
             }
         }
         let mut n = 0u32;
-        check(unsafe { pm_liveness_sweep(self.engine, now_ms, if w_rows != 0 { beats.as_ptr() } else { std::ptr::null() },
-                                         if pool.is_empty() { std::ptr::null() } else { pool.as_ptr() }, 1, &mut n,
-                                         std::ptr::null_mut()) })?;
+        // (admission on: the later of the device's beat column and this one, so beat() and admitted heartbeats both count)
+        let beats_ptr = if w_rows != 0 { beats.as_ptr() } else { std::ptr::null() };
+        let pool_ptr = if pool.is_empty() { std::ptr::null() } else { pool.as_ptr() };
+        check(unsafe {
+            if t.admission_on { pm_liveness_sweep_beats(self.engine, now_ms, beats_ptr, pool_ptr, 1, &mut n, std::ptr::null_mut()) }
+            else { pm_liveness_sweep(self.engine, now_ms, beats_ptr, pool_ptr, 1, &mut n, std::ptr::null_mut()) }
+        })?;
         let mut rows = vec![pm_live_row::default(); n.max(1) as usize];
         let mut got = 0u32;
         check(unsafe { pm_liveness_transitions(self.engine, rows.as_mut_ptr(), rows.len() as u32, &mut got) })?;

@@ -50,6 +50,9 @@
 #   gate[:<args>]            tools/gate_probe.py [n ...] [--bench DIR]: pm_ecrecover_many and pm_verify_requests at 1,000, 10,000 and
 #                            100,000 requests over a book of 100,000 rows, the address index cold and warm, beside pm_host_ecrecover
 #                            on one host thread -> r32_request_gate.txt (copy it to profiles/)
+#   admission[:<args>]       tools/admission_probe.py [n ...] [--bench DIR]: pm_admit_requests beside pm_verify_requests at 1,000 and 10,000
+#                            requests over standing nonce sets of 0, 100,000 and 1,000,000 entries, and pm_liveness_sweep_beats(NULL)
+#                            beside pm_liveness_sweep at W = 100,000 -> r33_admission.txt (copy it to profiles/)
 #   py:<script and args>     python tools/<script and args> (anything else)
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -192,6 +195,9 @@ PY
     gate)
       timeout -k 10 500 python tools/gate_probe.py $arg --out "$out/r32_request_gate.txt" > "$out/${n}_gate.log" 2>&1; echo "gate rc=$?"
       tail -30 "$out/${n}_gate.log" ;;
+    admission)
+      timeout -k 10 500 python tools/admission_probe.py $arg --out "$out/r33_admission.txt" > "$out/${n}_admission.log" 2>&1; echo "admission rc=$?"
+      tail -30 "$out/${n}_admission.log" ;;
     py)
       timeout 1800 python tools/$arg > "$out/${n}_py.log" 2>&1; echo "py rc=$?"; tail -40 "$out/${n}_py.log" ;;
     *) echo "unknown step '$step'" ;;
